@@ -12,7 +12,14 @@ Contract: python bench.py --gpus N --steps K --warmup W  -> rank 0 prints ONE JS
   `--gpus N` with N > 1 and no rendezvous environment: this process stays a plain launcher (it never imports
   torch, never touches the GPU) and starts N ranks of itself (n3dt/launch.py); under `torch.distributed.run`
   (WORLD_SIZE set) it is one of the ranks and WORLD_SIZE must equal --gpus.
-Extra objects in the line:
+  A plain run sets up, warms up W steps, times K steps and prints the line (headline, `ms_per_step`, `roofline`);
+  `--full` adds everything else below (`cpu_baseline`, `parity_check`, `trained`, `parity_grade`, `sustained`, `extra`,
+  `summary`), each as it is described there.
+  `--dump-outputs DIR` (rank 0): after the timed steps, what the last one computed -- render: `merge_img` and `bg_img`
+  (reading N: the feature stage's maps); train / fit: the images, the loss terms and the updated parameters / fitted
+  variables -- as DIR/<name>.npy in float32, at most 64 MiB in all (a larger set is cut to a fixed, seeded sample).
+  Inputs and weights are seeded, so two runs or two builds with the same arguments can be compared array by array.
+Extra objects in the line (`roofline` in every run, the others with --full):
   roofline      the fused MLP kernel: algorithmic FLOP (2 702 592 per sample point) / its average launch time
                 (hipEvents recorded around that launch on its stream, inside the timed region) against the dense bf16 MFMA
                 peak; `traffic` = HBM bytes per launch from profiles/traffic.json with the hash of the build it was taken on
@@ -186,7 +193,7 @@ def run_render(ctx, config, precision, batch, rays, steps, warmup, prof=True, ke
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            out = step()
         ctx.barrier()
         elapsed = time.perf_counter() - t0
     ms = (ctypes.c_float * steps)()
@@ -207,7 +214,10 @@ def run_render(ctx, config, precision, batch, rays, steps, warmup, prof=True, ke
     n_rays = d["batch_xy"].shape[-1]
     points = batch * n_rays * ns
     achieved = points * FLOP_PER_POINT / (kern_ms * 1e-3) / 1e12
+    # what the last timed step handed its caller: forward("test")'s images (reading R) or the feature stage's maps (reading N)
+    outputs = dict(out["coarse_dict"]) if rays == "R" else {k: v for k, v in out.items() if torch.is_tensor(v)}
     return {
+        "outputs": outputs,
         "kernel_ms_all": [ms[i] for i in range(n_rec.value)] if keep_kernel_ms else None,
         "opt": opt, "sd": sd, "elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps,
         "frames_per_s": ctx.world * batch * steps / elapsed, "kern_ms": kern_ms, "points": points, "n_rays": n_rays,
@@ -282,6 +292,8 @@ def run_train(ctx, config, train_precision, batch, steps, warmup, audio2style_bu
         optim.step()
         if optim_a2s is not None:
             optim_a2s.step()
+        # detached: the step kept for --dump-outputs must not keep its autograd graph alive into the next one
+        return {k: v.detach() for k, v in pred_["coarse_dict"].items()}, {k: v.detach() for k, v in t.items()}
 
     if graph:
         from n3dt.train import GraphedTrainStep
@@ -295,7 +307,7 @@ def run_train(ctx, config, train_precision, batch, steps, warmup, audio2style_bu
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     t_enqueued = time.perf_counter() - t0  # host time to ENQUEUE the steps (no synchronisation inside the loop)
     ctx.barrier()
     elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
@@ -328,7 +340,12 @@ def run_train(ctx, config, train_precision, batch, steps, warmup, audio2style_bu
         roof["traffic"] = tr.get(key)
         roof["traffic_lib_sha16"] = tr.get("_train_lib_sha16") if tr.get(key) is not None else None
         roof["lib_sha16"] = lib_sha16()
+    # what the last timed step leaves its caller: the predicted images, the loss terms and the updated parameters
+    outputs = dict(out[0])
+    outputs.update(out[1])
+    outputs["params_flat"] = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
     return {
+        "outputs": outputs,
         "elapsed": elapsed, "ms_per_step": ms_per_step, "frames_per_s": ctx.world * batch * steps / elapsed,
         "host_enqueue_ms_per_step": 1e3 * t_enqueued / steps, "roofline": roof, "graph": bool(graph),
         "optimizers": 2 if optim_a2s is not None else 1,
@@ -357,19 +374,54 @@ def run_fit(ctx, config, train_precision, steps, warmup):
     mask = disk_mask(1, pred).to(ctx.dev)
 
     def step():
-        fitting.fit_step(net, st, optim, sched, d["batch_xy"], d["batch_uv"], d["audiostyle"], gt, mask, data_losses)
+        pred, terms, _ = fitting.fit_step(net, st, optim, sched, d["batch_xy"], d["batch_uv"], d["audiostyle"], gt, mask, data_losses)
+        return {k: v.detach() for k, v in pred["coarse_dict"].items()}, {k: v.detach() for k, v in terms.items()}
 
     for _ in range(warmup):
         step()
     ctx.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     ctx.barrier()
     elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
-    return {"elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps, "frames_per_s": ctx.world * steps / elapsed,
+    # what the last timed step leaves its caller: the rendered images, the loss terms and the fitted variables
+    outputs = dict(out[0])
+    outputs.update(out[1])
+    outputs.update({n: v.detach() for n, v in zip(("iden_offset", "expr_offset", "appea_offset", "delta_EulurAngles", "delta_Tvecs"),
+                                                  st.variables())})
+    return {"outputs": outputs, "elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps, "frames_per_s": ctx.world * steps / elapsed,
             "workload": "%s fitting: 1 head/step, %dx%d rays x %d samples -> %dx%d, gradients to codes + camera, Adam on 5 tensors" % (
                 config, fs, fs, ns, pred, pred)}
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SEED = 0
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of the last timed step as `<path>/<name>.npy`, float32 (float64 stays float64).  Above 64 MiB
+    in all, each array keeps the same fraction of its entries: a sorted sample of its flattened indices drawn from a fixed seed,
+    so two runs (or two builds) with the same arguments write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            v = (v if v.dtype == torch.float64 else v.float()).cpu().numpy()
+        a = np.asarray(v)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, DUMP_LIMIT_BYTES / float(max(total, 1)))
+    for name, a in host.items():
+        if keep < 1.0:
+            n = int(a.size * keep)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(host)
 
 
 def cpu_info():
@@ -591,11 +643,19 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg4", "cfg5"],
                     help="BASELINE.json geometry: cfg2 (headline: 64x64 rays x 64 samples -> 512^2; cfg3 with --mode train), "
                          "cfg4 (32x32 rays x 64 samples -> 256^2, 4 heads per GPU), cfg5 (HR: 32x32 rays x 96 samples -> 1024^2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `extra` sub-records (N = 1 render runs carry them by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: cpu_baseline, parity_check, sustained, extra, "
+                         "parity_grade, summary (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline` and `parity_check`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip `sustained` and the `extra` sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MiB in all; rank 0; "
+                         "bench_outputs/ is git-ignored)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     # ---- launcher: no torch, no GPU in this process ---------------------------------------------------------------
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -617,6 +677,8 @@ def main():
         tp = "bf16" if args.precision == "bf16" else "fp32"
         r = run_fit(ctx, args.config, tp, args.steps, args.warmup)
         if ctx.rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, r["outputs"])
             fs, ns, pred = GEOMETRY[args.config]
             print(json.dumps({"metric": "fitting iterations/sec @%d^2 x %d samples/ray" % (pred, ns), "value": r["frames_per_s"], "unit": "iterations/s",
                               "n_gpus": ctx.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -629,6 +691,8 @@ def main():
         B = args.batch   # config 3: 2 heads per step, config 4: 4 per GPU (BASELINE.json), unless --batch says otherwise
         r = run_train(ctx, args.config, tp, B, args.steps, args.warmup, graph=args.graph)
         if ctx.rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, r["outputs"])
             fs, ns, pred = GEOMETRY[args.config]
             print(json.dumps({
                 "metric": "trained frames/sec @%d^2 x %d samples/ray (fwd+bwd+Adam)" % (pred, ns),
@@ -652,6 +716,8 @@ def main():
     r = run_render(ctx, args.config, args.precision, args.batch, args.rays, args.steps, args.warmup)
     res = None
     if ctx.rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r.pop("outputs"))
         fs, ns, pred = GEOMETRY[args.config]
         tr = load_traffic()
         traffic = tr.get("%s_%s_b%d" % (args.rays, args.precision, args.batch))
@@ -688,8 +754,9 @@ def main():
                 "executed_tflops": r["executed_tflops"],
             },
         }
+    r.pop("outputs", None)
     parity_ok = True
-    if ctx.world == 1:
+    if ctx.world == 1 and args.full:
         if not args.no_cpu_baseline:
             res["cpu_baseline"], ref = cpu_baseline(r["opt"], r["sd"], args.rays)
             if args.rays == "R" and args.config == "cfg2":
