@@ -294,6 +294,34 @@ int n3dt_loss_fwd(int batch, int pixels, const float* merge_img, const float* bg
 int n3dt_loss_bwd(int batch, int pixels, const float* merge_img, const float* bg_img, const float* gt, const float* mask,
                   float bg_value, const float* acc, const float* g, const float* g_total, float* d_merge, float* d_bg, void* stream);
 
+/* ---- VGG16 perceptual loss term (Utils/HeadNeRFLossUtils.py:23-64, 140-154) --------------------------------------------
+ * The fourth data term of the reference's objective: input = nan_to_num(merge_img), target = gt with bg_value wherever
+ * mask < 0.5, both ImageNet-normalised and resized to 224^2 (bilinear, align_corners=False), through torchvision
+ * vgg16().features[:23] in four blocks [:4] [4:9] [9:16] [16:23]; the term is the sum over blocks of mean |f_b(x) - f_b(y)|.
+ * The VGG weights are frozen: the backward produces d_merge only.
+ *   n3dt_vgg_pack      re-lays the ten convs' fp32 weights (weight[l] [C_out, C_in, 3, 3], bias[l] [C_out], torchvision order)
+ *                      into MFMA fragment order, forward and transposed-flipped (input gradient); once per weight set
+ *   n3dt_vgg_loss_fwd  merge_img, gt [B,3,P,P], mask [B,1,P,P] (NULL: gt is used as given) -> terms[5] = the four block
+ *                      terms and their sum ((t0 + t1) + t2) + t3; keeps the activations in `saved` for the backward
+ *   n3dt_vgg_loss_bwd  g_total [1] (device) = dL/d(sum) -> d_merge [B,3,P,P] (overwritten; 0 where merge_img is not finite);
+ *                      `saved` from the forward with the same batch, img_size, precision and packed weights
+ * precision N3DT_F32 (split-bf16 operands, three products: ~16 mantissa bits) or N3DT_BF16; 1 <= batch <= 64,
+ * 16 <= img_size <= 2048. */
+#define N3DT_VGG_CONVS 10   /* torchvision vgg16().features indices 0,2,5,7,10,12,14,17,19,21 */
+typedef struct N3dtVggParams {
+    const float* weight[N3DT_VGG_CONVS];
+    const float* bias[N3DT_VGG_CONVS];
+} N3dtVggParams;
+size_t n3dt_vgg_packed_bytes(int precision);
+int n3dt_vgg_pack(int precision, const N3dtVggParams* p, void* packed, void* stream);
+size_t n3dt_vgg_saved_bytes(int batch, int precision);
+size_t n3dt_vgg_workspace_bytes(int batch, int img_size, int precision);
+int n3dt_vgg_loss_fwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* gt,
+                      const float* mask, float bg_value, float* terms, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                      void* stream);
+int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* g_total,
+                      const void* saved, size_t saved_bytes, float* d_merge, void* ws, size_t ws_bytes, void* stream);
+
 /* [C, N_r] (NCHW parameter) -> [N_r, C]; used to feed bg_featmap to the renderer */
 int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream);
 

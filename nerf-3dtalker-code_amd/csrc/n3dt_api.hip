@@ -70,6 +70,12 @@ void n3dt_launch_nr_bwd(const N3dtGeom*, int, const N3dtRenderParams*, const N3d
                         float*, float*, int, hipStream_t);
 void n3dt_launch_neural_render(const N3dtGeom*, int, int, const N3dtRenderParams*, const float*, float*, float*, int, hipStream_t);
 void n3dt_launch_stage(const N3dtStageCopy*, hipStream_t);
+size_t n3dt_vgg_packed_layout_bytes(int);
+size_t n3dt_vgg_saved_floats(int);
+size_t n3dt_vgg_ws_floats(int);
+void n3dt_launch_vgg_pack(int, const N3dtVggParams*, void*, hipStream_t);
+void n3dt_launch_vgg_fwd(int, int, int, const void*, const float*, const float*, const float*, float, float*, void*, void*, hipStream_t);
+void n3dt_launch_vgg_bwd(int, int, int, const void*, const float*, const float*, const void*, float*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -390,6 +396,72 @@ extern "C" int n3dt_neural_render_pack(const N3dtGeom* g, int nb, int precision,
 extern "C" int n3dt_neural_render_fwd_reuse(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const float* featmap,
                                             float* img, void* workspace, size_t workspace_bytes, void* stream) {
     return neural_render_common(g, nb, precision, p, featmap, img, workspace, workspace_bytes, 1, stream, "n3dt_neural_render_fwd_reuse");
+}
+
+// ---- VGG16 perceptual term (csrc/vgg_loss.hip) ----
+static int check_vgg(const char* who, int batch, int img_size, int precision) {
+    char m[160];
+    if (precision != N3DT_F32 && precision != N3DT_BF16) {
+        snprintf(m, sizeof(m), "%s: unsupported precision %d (N3DT_F32 or N3DT_BF16)", who, precision);
+        return fail(N3DT_EINVAL, m);
+    }
+    if (batch < 1 || batch > 64) {
+        snprintf(m, sizeof(m), "%s: batch %d outside 1..64", who, batch);
+        return fail(N3DT_EINVAL, m);
+    }
+    if (img_size < 16 || img_size > 2048) {
+        snprintf(m, sizeof(m), "%s: img_size %d outside 16..2048", who, img_size);
+        return fail(N3DT_EINVAL, m);
+    }
+    return N3DT_OK;
+}
+
+extern "C" size_t n3dt_vgg_packed_bytes(int precision) {
+    if (check_vgg("n3dt_vgg_packed_bytes", 1, 224, precision)) return 0;
+    return n3dt_vgg_packed_layout_bytes(precision);
+}
+
+extern "C" size_t n3dt_vgg_saved_bytes(int batch, int precision) {
+    if (check_vgg("n3dt_vgg_saved_bytes", batch, 224, precision)) return 0;
+    return n3dt_vgg_saved_floats(batch) * sizeof(float);
+}
+
+extern "C" size_t n3dt_vgg_workspace_bytes(int batch, int img_size, int precision) {
+    if (check_vgg("n3dt_vgg_workspace_bytes", batch, img_size, precision)) return 0;
+    return n3dt_vgg_ws_floats(batch) * sizeof(float);
+}
+
+extern "C" int n3dt_vgg_pack(int precision, const N3dtVggParams* p, void* packed, void* stream) {
+    int rc = check_vgg("n3dt_vgg_pack", 1, 224, precision);
+    if (rc) return rc;
+    if (!p || !packed) return fail(N3DT_EINVAL, "n3dt_vgg_pack: NULL argument");
+    for (int l = 0; l < N3DT_VGG_CONVS; ++l)
+        if (!p->weight[l] || !p->bias[l]) return fail(N3DT_EINVAL, "n3dt_vgg_pack: NULL parameter pointer");
+    n3dt_launch_vgg_pack(precision, p, packed, (hipStream_t)stream);
+    return check_hip("n3dt_vgg_pack");
+}
+
+extern "C" int n3dt_vgg_loss_fwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* gt,
+                                 const float* mask, float bg_value, float* terms, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    int rc = check_vgg("n3dt_vgg_loss_fwd", batch, img_size, precision);
+    if (rc) return rc;
+    if (!packed || !merge_img || !gt || !terms || !saved || !ws) return fail(N3DT_EINVAL, "n3dt_vgg_loss_fwd: NULL argument");
+    if (saved_bytes < n3dt_vgg_saved_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_fwd: saved buffer too small");
+    if (ws_bytes < n3dt_vgg_ws_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_fwd: workspace too small");
+    n3dt_launch_vgg_fwd(batch, img_size, precision, packed, merge_img, gt, mask, bg_value, terms, saved, ws, (hipStream_t)stream);
+    return check_hip("n3dt_vgg_loss_fwd");
+}
+
+extern "C" int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* g_total,
+                                 const void* saved, size_t saved_bytes, float* d_merge, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_vgg("n3dt_vgg_loss_bwd", batch, img_size, precision);
+    if (rc) return rc;
+    if (!packed || !merge_img || !g_total || !saved || !d_merge || !ws) return fail(N3DT_EINVAL, "n3dt_vgg_loss_bwd: NULL argument");
+    if (saved_bytes < n3dt_vgg_saved_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_bwd: saved buffer too small");
+    if (ws_bytes < n3dt_vgg_ws_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_bwd: workspace too small");
+    n3dt_launch_vgg_bwd(batch, img_size, precision, packed, merge_img, g_total, saved, d_merge, ws, (hipStream_t)stream);
+    return check_hip("n3dt_vgg_loss_bwd");
 }
 
 extern "C" int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream) {

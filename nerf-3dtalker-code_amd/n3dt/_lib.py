@@ -29,6 +29,13 @@ class Geom(ctypes.Structure):
     ]
 
 
+VGG_CONVS = 10
+
+
+class VggParams(ctypes.Structure):
+    _fields_ = [("weight", ctypes.c_void_p * VGG_CONVS), ("bias", ctypes.c_void_p * VGG_CONVS)]
+
+
 class MlpParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * MLP_LAYERS), ("bias", ctypes.c_void_p * MLP_LAYERS)]
 
@@ -52,6 +59,7 @@ EXPORTS = [
     "n3dt_img_to_uint8", "n3dt_sample_points", "n3dt_embed", "n3dt_mlp_points_workspace_bytes", "n3dt_mlp_points", "n3dt_composite",
     "n3dt_ray_vd_bias", "n3dt_embed_freqs",
     "n3dt_neural_render_pack", "n3dt_neural_render_fwd_reuse", "n3dt_stage_inputs", "n3dt_graph_begin", "n3dt_graph_end", "n3dt_graph_launch", "n3dt_graph_destroy",
+    "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd",
 ]
 
 STAGE_MAX = 12
@@ -151,6 +159,18 @@ def lib():
     L.n3dt_graph_launch.argtypes = [vp, vp]
     L.n3dt_graph_destroy.restype = ci
     L.n3dt_graph_destroy.argtypes = [vp]
+    L.n3dt_vgg_packed_bytes.restype = sz
+    L.n3dt_vgg_packed_bytes.argtypes = [ci]
+    L.n3dt_vgg_pack.restype = ci
+    L.n3dt_vgg_pack.argtypes = [ci, ctypes.POINTER(VggParams), vp, vp]
+    L.n3dt_vgg_saved_bytes.restype = sz
+    L.n3dt_vgg_saved_bytes.argtypes = [ci, ci]
+    L.n3dt_vgg_workspace_bytes.restype = sz
+    L.n3dt_vgg_workspace_bytes.argtypes = [ci, ci, ci]
+    L.n3dt_vgg_loss_fwd.restype = ci
+    L.n3dt_vgg_loss_fwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, sz, vp, sz, vp]
+    L.n3dt_vgg_loss_bwd.restype = ci
+    L.n3dt_vgg_loss_bwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, sz, vp, vp, sz, vp]
     if L.n3dt_abi_version() != 5:
         raise N3dtError("libn3dt.so ABI version mismatch")
     _LIB = L

@@ -319,3 +319,24 @@ def train_sharp_head(opt, dev, steps=400, lr=1e-3, batch=2, train_precision="fp3
     info.update({"steps": done, "lr": lr, "batch": batch, "train_precision": train_precision, "loss_first": loss0, "loss_last": lossv,
                  "target": "disk of a seeded colour pattern on white, bg + head + nonhead MSE terms"})
     return net, info
+
+
+# torchvision vgg16 (configuration "D") feature extractor: conv widths, "M" = 2x2 max-pool
+VGG16_CFG = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M")
+
+
+def vgg16_features_state_dict(seed=0):
+    """Seeded stand-in for torchvision's pretrained vgg16 `features.*` weights (the real ones cannot be fetched offline): the
+    13 convolutions at torchvision's indices, He-normal weights std = sqrt(2 / (9 C_in)) and small non-zero biases."""
+    gen = torch.Generator().manual_seed(seed)
+    sd, idx, cin = {}, 0, 3
+    for v in VGG16_CFG:
+        if v == "M":
+            idx += 1
+            continue
+        std = math.sqrt(2.0 / (9 * cin))
+        sd["features.%d.weight" % idx] = torch.randn(v, cin, 3, 3, generator=gen) * std
+        sd["features.%d.bias" % idx] = (torch.rand(v, generator=gen) - 0.5) * 0.02
+        idx += 2  # conv, ReLU
+        cin = v
+    return sd

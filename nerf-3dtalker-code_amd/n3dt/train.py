@@ -18,7 +18,7 @@ def disk_mask(batch, size, radius=0.35):
 
 def data_losses(coarse, gt_rgb, mask, bg_value=1.0):
     """The three MSE data terms of the reference loss (Utils/HeadNeRFLossUtils.py:125-146,196-236); the VGG
-    perceptual term needs pretrained weights that cannot be fetched offline and is left to the caller."""
+    perceptual term is HeadNeRFLossUtils(vgg_weights=...) / n3dt.perceptual."""
     bg_img = coarse["bg_img"]
     bg_loss = torch.mean((bg_img - bg_value) * (bg_img - bg_value))
     res = torch.nan_to_num(coarse["merge_img"], nan=0.0)
@@ -93,21 +93,32 @@ class HeadNeRFLossUtils(object):
     """Drop-in for the reference's loss object (Utils/HeadNeRFLossUtils.py:66-236) on the fused HIP loss tail: same
     constructor, same `calc_total_loss(delta_cam_info, opt_code_dict, pred_dict, gt_rgb, mask_tensor, disp_pred_dict)` call,
     same result keys -- including the reference's spelling `nonhaed_loss` -- so the trainer's and the fitting script's loss lines
-    (talker_trainer.py:1058, FittingSingleImage_new.py:894) stay as they are.  The VGG perceptual term needs torchvision's
-    pretrained VGG16, which is outside the accelerated path: `use_vgg_loss=True` is refused, add that term in the caller."""
+    (talker_trainer.py:1058, FittingSingleImage_new.py:894) stay as they are.  The VGG perceptual term (`use_vgg_loss=True`, the
+    reference's default) runs on libn3dt's VGG kernels (n3dt.perceptual) with the caller's torchvision vgg16 weights: pass
+    `vgg_weights` (a state dict or the path of one; nothing is downloaded).  `vgg_precision` follows train_precision: "fp32" is the
+    parity mode, "bf16" the fast one."""
 
-    def __init__(self, bg_type="white", use_vgg_loss=True, device=None):
+    def __init__(self, bg_type="white", use_vgg_loss=True, device=None, vgg_weights=None, vgg_precision="fp32"):
         if bg_type == "white":
             self.bg_value = 1.0
         elif bg_type == "black":
             self.bg_value = 0.0
         else:
             raise ValueError("Error BG type. ")  # the reference prints this and exit(0)s
+        self.vgg_loss_func = None
         if use_vgg_loss:
-            raise NotImplementedError("the VGG perceptual term is not part of the accelerated path: construct with "
-                                      "use_vgg_loss=False and add the reference's VGGPerceptualLoss to total_loss yourself")
-        self.use_vgg_loss = False
+            if vgg_weights is None:
+                raise NotImplementedError("use_vgg_loss=True needs vgg_weights: pass torchvision's vgg16 state dict (or the path of its "
+                                          "checkpoint) as vgg_weights -- pretrained weights are never downloaded -- or construct "
+                                          "with use_vgg_loss=False")
+            from .perceptual import VGGPerceptualLoss
+            self.vgg_loss_func = VGGPerceptualLoss(vgg_weights, precision=vgg_precision)
+        self.use_vgg_loss = bool(use_vgg_loss)
         self.device = device
+
+    def _vgg(self, merge_img, gt_rgb, mask):
+        # the reference: vgg_loss_func(nan_to_num(merge_img), gt with bg_value where mask < 0.5) (:137, :148-153)
+        return self.vgg_loss_func.masked(merge_img, gt_rgb, mask, self.bg_value)
 
     def calc_data_loss(self, data_dict, gt_rgb, head_mask_c1b, nonhead_mask_c1b):
         """The reference passes the two boolean masks of `mask >= 0.5` / `mask < 0.5` (:200-201); the kernel takes the mask itself."""
@@ -115,17 +126,25 @@ class HeadNeRFLossUtils(object):
             raise TypeError("calc_data_loss expects the boolean masks calc_total_loss builds")
         if bool((head_mask_c1b == nonhead_mask_c1b).any()):
             raise ValueError("head and non-head masks must be complementary (the fused kernel classifies each pixel once)")
-        t = fused_data_losses(data_dict, gt_rgb, head_mask_c1b.to(gt_rgb.dtype), self.bg_value)
-        return {"bg_loss": t["bg_loss"], "head_loss": t["head_loss"], "nonhaed_loss": t["nonhead_loss"]}
+        mask = head_mask_c1b.to(gt_rgb.dtype)
+        t = fused_data_losses(data_dict, gt_rgb, mask, self.bg_value)
+        res = {"bg_loss": t["bg_loss"], "head_loss": t["head_loss"], "nonhaed_loss": t["nonhead_loss"]}
+        if self.use_vgg_loss:
+            res["vgg"] = self._vgg(data_dict["merge_img"], gt_rgb, mask)
+        return res
 
     def calc_total_loss(self, delta_cam_info, opt_code_dict, pred_dict, gt_rgb, mask_tensor, disp_pred_dict, eye_mask_tensor=None):
-        """bg + head + non-head data terms and their sum (:196-236; the camera / code / eye / displacement terms are commented
+        """bg + head + non-head data terms (+ vgg) and their sum (:196-236; the camera / code / eye / displacement terms are commented
         out in the reference, so the first two and the last two arguments are accepted and unused, as there)."""
         t = fused_data_losses(pred_dict["coarse_dict"], gt_rgb, mask_tensor, self.bg_value)
         loss_dict = {"bg_loss": t["bg_loss"], "head_loss": t["head_loss"], "nonhaed_loss": t["nonhead_loss"]}
-        # the reference adds the entries up in dict order (0.0 + bg + head + nonhead, :228-231); the kernel forms the same
-        # sum in the same order, so the autograd graph has one node instead of three additions
-        loss_dict["total_loss"] = t["total_loss"]
+        # the reference adds the entries up in dict order (0.0 + bg + head + nonhead [+ vgg], :228-231); the kernel forms the first
+        # three in the same order, so the autograd graph has one node instead of three additions
+        total = t["total_loss"]
+        if self.use_vgg_loss:
+            loss_dict["vgg"] = self._vgg(pred_dict["coarse_dict"]["merge_img"], gt_rgb, mask_tensor)
+            total = total + loss_dict["vgg"]
+        loss_dict["total_loss"] = total
         return loss_dict
 
 
@@ -136,12 +155,16 @@ def make_optimizer(net, lr=1e-4):
     return opt, sched
 
 
-def train_step(net, optimizer, inputs, gt_rgb, mask, t_rand=None, extra_optimizers=(), fused_loss=True):
-    """One reference-shaped step: forward("train") -> losses -> zero_grad -> backward -> step."""
+def train_step(net, optimizer, inputs, gt_rgb, mask, t_rand=None, extra_optimizers=(), fused_loss=True, loss_utils=None):
+    """One reference-shaped step: forward("train") -> losses -> zero_grad -> backward -> step.  `loss_utils`: a HeadNeRFLossUtils
+    whose calc_total_loss forms the losses instead (the reference's own objective, e.g. with the VGG term)."""
     pred = net("train", inputs["batch_xy"], inputs["batch_uv"], inputs["audiostyle"], bg_code=None,
                shape_code=inputs["shape_code"], appea_code=inputs["appea_code"], batch_Rmats=inputs["batch_Rmats"],
                batch_Tvecs=inputs["batch_Tvecs"], batch_inv_inmats=inputs["batch_inv_inmats"], t_rand=t_rand)
-    terms = (fused_data_losses if fused_loss else data_losses)(pred["coarse_dict"], gt_rgb, mask)
+    if loss_utils is not None:
+        terms = loss_utils.calc_total_loss(None, None, pred, gt_rgb, mask, None)
+    else:
+        terms = (fused_data_losses if fused_loss else data_losses)(pred["coarse_dict"], gt_rgb, mask)
     total = terms["total_loss"] if "total_loss" in terms else terms["bg_loss"] + terms["head_loss"] + terms["nonhead_loss"]
     for o in extra_optimizers:
         o.zero_grad()
