@@ -322,6 +322,39 @@ int n3dt_vgg_loss_fwd(int batch, int img_size, int precision, const void* packed
 int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* g_total,
                       const void* saved, size_t saved_bytes, float* d_merge, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Audio2style encoder (talker_trainer.py:407-461) ------------------------------------------------------------------
+ * mel [T, 1280] (each frame's 80x16 window, row-major) is ONE sequence of T frames through
+ * nn.LSTM(1280, 640, num_layers=2, bidirectional=True) (h0 = c0 = 0, gate order i, f, g, o), then
+ * out = drop(lrelu(drop(lrelu(drop(lrelu(H W1^T + b1)) W2^T + b2)) W3^T + b3)) -> [T, 64], lrelu slope 0.2.
+ * Dropout (p = 0.5): masks[k] are keep masks of 0 / 1 ([T,640], [T,320], [T,64]); a kept value is scaled by 2.  masks NULL:
+ * no dropout (eval).  fp32 throughout.  1 <= T <= 256.
+ *   n3dt_a2s_fwd  -> out [T, 64]; keeps what the backward needs in `saved` (mel included)
+ *   n3dt_a2s_bwd  g_out [T, 64] -> every parameter gradient, OVERWRITTEN, into grad_arena (layout below); no input gradient.
+ *                 No atomics, no split-K: the result is bitwise reproducible.
+ * Parameter index k = 2 * layer + direction (weight_ih_l0, _l0_reverse, _l1, _l1_reverse).  The grad arena holds, each
+ * contiguous and in this order (the state-dict order without RNNModel.fc1, which forward never reads):
+ *   for k in 0..3: dW_ih[k] [2560, 1280], dW_hh[k] [2560, 640], db_ih[k] [2560], db_hh[k] [2560];
+ *   then dW1 [640, 1280], db1 [640], dW2 [320, 640], db2 [320], dW3 [64, 320], db3 [64]. */
+#define N3DT_A2S_IN 1280
+#define N3DT_A2S_HIDDEN 640
+#define N3DT_A2S_OUT 64
+#define N3DT_A2S_MAX_T 256
+#define N3DT_A2S_GRAD_FLOATS 20726784
+typedef struct N3dtA2sParams {
+    const float* w_ih[4];  /* [2560, 1280] */
+    const float* w_hh[4];  /* [2560, 640] */
+    const float* b_ih[4];  /* [2560] */
+    const float* b_hh[4];  /* [2560] */
+    const float* lin_w[3]; /* linear1.0 [640, 1280], linear2.0 [320, 640], linear3.0 [64, 320] */
+    const float* lin_b[3];
+} N3dtA2sParams;
+size_t n3dt_a2s_saved_bytes(int T);
+size_t n3dt_a2s_workspace_bytes(int T);
+int n3dt_a2s_fwd(int T, const N3dtA2sParams* p, const float* mel, const float* mask1, const float* mask2, const float* mask3,
+                 float* out, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream);
+int n3dt_a2s_bwd(int T, const N3dtA2sParams* p, const float* g_out, const void* saved, size_t saved_bytes, float* grad_arena,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* [C, N_r] (NCHW parameter) -> [N_r, C]; used to feed bg_featmap to the renderer */
 int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream);
 

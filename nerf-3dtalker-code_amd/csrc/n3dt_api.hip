@@ -76,6 +76,10 @@ size_t n3dt_vgg_ws_floats(int);
 void n3dt_launch_vgg_pack(int, const N3dtVggParams*, void*, hipStream_t);
 void n3dt_launch_vgg_fwd(int, int, int, const void*, const float*, const float*, const float*, float, float*, void*, void*, hipStream_t);
 void n3dt_launch_vgg_bwd(int, int, int, const void*, const float*, const float*, const void*, float*, void*, hipStream_t);
+size_t n3dt_a2s_saved_floats(int);
+size_t n3dt_a2s_ws_floats(int);
+void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* const[3], float*, void*, void*, hipStream_t);
+void n3dt_launch_a2s_bwd(int, const N3dtA2sParams*, const float*, const void*, float*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -462,6 +466,104 @@ extern "C" int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const v
     if (ws_bytes < n3dt_vgg_ws_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_bwd: workspace too small");
     n3dt_launch_vgg_bwd(batch, img_size, precision, packed, merge_img, g_total, saved, d_merge, ws, (hipStream_t)stream);
     return check_hip("n3dt_vgg_loss_bwd");
+}
+
+// ---- Audio2style encoder (csrc/audio_lstm.hip) ----
+static int a2s_fail(const char* who, const char* what) {
+    char m[200];
+    snprintf(m, sizeof(m), "%s: %s", who, what);
+    return fail(N3DT_EINVAL, m);
+}
+
+static int check_a2s_T(const char* who, int T) {
+    if (T < 1 || T > N3DT_A2S_MAX_T) {
+        char m[160];
+        snprintf(m, sizeof(m), "%s: T = %d outside 1..%d", who, T, N3DT_A2S_MAX_T);
+        return fail(N3DT_EINVAL, m);
+    }
+    return N3DT_OK;
+}
+
+static bool a2s_aligned(const void* q) { return (((size_t)q) & 15) == 0; }
+
+// every parameter pointer non-NULL and 16-byte aligned (the step kernels read W_hh with 16-byte loads)
+static int check_a2s_params(const char* who, const N3dtA2sParams* p) {
+    if (!p) return a2s_fail(who, "params is NULL");
+    static const char* names[4] = {"w_ih", "w_hh", "b_ih", "b_hh"};
+    const float* const* lstm[4] = {p->w_ih, p->w_hh, p->b_ih, p->b_hh};
+    char m[96];
+    for (int a = 0; a < 4; ++a)
+        for (int k = 0; k < 4; ++k) {
+            if (!lstm[a][k] || !a2s_aligned(lstm[a][k])) {
+                snprintf(m, sizeof(m), "params->%s[%d] is NULL or not 16-byte aligned", names[a], k);
+                return a2s_fail(who, m);
+            }
+        }
+    for (int k = 0; k < 3; ++k) {
+        if (!p->lin_w[k] || !a2s_aligned(p->lin_w[k])) {
+            snprintf(m, sizeof(m), "params->lin_w[%d] is NULL or not 16-byte aligned", k);
+            return a2s_fail(who, m);
+        }
+        if (!p->lin_b[k] || !a2s_aligned(p->lin_b[k])) {
+            snprintf(m, sizeof(m), "params->lin_b[%d] is NULL or not 16-byte aligned", k);
+            return a2s_fail(who, m);
+        }
+    }
+    return N3DT_OK;
+}
+
+static int check_a2s_buf(const char* who, const char* name, const void* q, size_t have, size_t need) {
+    char m[160];
+    if (!q || !a2s_aligned(q)) {
+        snprintf(m, sizeof(m), "%s is NULL or not 16-byte aligned", name);
+        return a2s_fail(who, m);
+    }
+    if (have < need) {
+        snprintf(m, sizeof(m), "%s_bytes = %zu, %zu needed", name, have, need);
+        return a2s_fail(who, m);
+    }
+    return N3DT_OK;
+}
+
+extern "C" size_t n3dt_a2s_saved_bytes(int T) {
+    if (check_a2s_T("n3dt_a2s_saved_bytes", T)) return 0;
+    return n3dt_a2s_saved_floats(T) * sizeof(float);
+}
+
+extern "C" size_t n3dt_a2s_workspace_bytes(int T) {
+    if (check_a2s_T("n3dt_a2s_workspace_bytes", T)) return 0;
+    return n3dt_a2s_ws_floats(T) * sizeof(float);
+}
+
+extern "C" int n3dt_a2s_fwd(int T, const N3dtA2sParams* p, const float* mel, const float* mask1, const float* mask2, const float* mask3,
+                            float* out, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "n3dt_a2s_fwd";
+    int rc = check_a2s_T(who, T);
+    if (!rc) rc = check_a2s_params(who, p);
+    if (rc) return rc;
+    if (!mel || !a2s_aligned(mel)) return a2s_fail(who, "mel is NULL or not 16-byte aligned");
+    if (!out) return a2s_fail(who, "out is NULL");
+    const float* masks[3] = {mask1, mask2, mask3};
+    if ((mask1 != nullptr) != (mask2 != nullptr) || (mask1 != nullptr) != (mask3 != nullptr))
+        return a2s_fail(who, "mask1, mask2 and mask3 must be all given or all NULL");
+    if ((rc = check_a2s_buf(who, "saved", saved, saved_bytes, n3dt_a2s_saved_floats(T) * sizeof(float)))) return rc;
+    if ((rc = check_a2s_buf(who, "ws", ws, ws_bytes, n3dt_a2s_ws_floats(T) * sizeof(float)))) return rc;
+    n3dt_launch_a2s_fwd(T, p, mel, masks, out, saved, ws, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_a2s_bwd(int T, const N3dtA2sParams* p, const float* g_out, const void* saved, size_t saved_bytes, float* grad_arena,
+                            void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "n3dt_a2s_bwd";
+    int rc = check_a2s_T(who, T);
+    if (!rc) rc = check_a2s_params(who, p);
+    if (rc) return rc;
+    if (!g_out) return a2s_fail(who, "g_out is NULL");
+    if (!grad_arena || !a2s_aligned(grad_arena)) return a2s_fail(who, "grad_arena is NULL or not 16-byte aligned");
+    if ((rc = check_a2s_buf(who, "saved", saved, saved_bytes, n3dt_a2s_saved_floats(T) * sizeof(float)))) return rc;
+    if ((rc = check_a2s_buf(who, "ws", ws, ws_bytes, n3dt_a2s_ws_floats(T) * sizeof(float)))) return rc;
+    n3dt_launch_a2s_bwd(T, p, g_out, saved, grad_arena, ws, (hipStream_t)stream);
+    return check_hip(who);
 }
 
 extern "C" int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream) {

@@ -36,6 +36,15 @@ class VggParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * VGG_CONVS), ("bias", ctypes.c_void_p * VGG_CONVS)]
 
 
+class A2sParams(ctypes.Structure):
+    _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
+                ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
+
+
+A2S_MAX_T = 256
+A2S_GRAD_FLOATS = 20726784
+
+
 class MlpParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * MLP_LAYERS), ("bias", ctypes.c_void_p * MLP_LAYERS)]
 
@@ -60,6 +69,7 @@ EXPORTS = [
     "n3dt_ray_vd_bias", "n3dt_embed_freqs",
     "n3dt_neural_render_pack", "n3dt_neural_render_fwd_reuse", "n3dt_stage_inputs", "n3dt_graph_begin", "n3dt_graph_end", "n3dt_graph_launch", "n3dt_graph_destroy",
     "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd",
+    "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
 ]
 
 STAGE_MAX = 12
@@ -171,6 +181,14 @@ def lib():
     L.n3dt_vgg_loss_fwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, sz, vp, sz, vp]
     L.n3dt_vgg_loss_bwd.restype = ci
     L.n3dt_vgg_loss_bwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.n3dt_a2s_saved_bytes.restype = sz
+    L.n3dt_a2s_saved_bytes.argtypes = [ci]
+    L.n3dt_a2s_workspace_bytes.restype = sz
+    L.n3dt_a2s_workspace_bytes.argtypes = [ci]
+    L.n3dt_a2s_fwd.restype = ci
+    L.n3dt_a2s_fwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
+    L.n3dt_a2s_bwd.restype = ci
+    L.n3dt_a2s_bwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, sz, vp, vp, sz, vp]
     if L.n3dt_abi_version() != 5:
         raise N3dtError("libn3dt.so ABI version mismatch")
     _LIB = L

@@ -36,17 +36,34 @@ def extend_for_gaze(state_dict, eye_gaze_dim):
     return out
 
 
-def save_checkpoint(path, net, opt, epoch=0, optimizer=None, scheduler=None, extra=None):
+def save_checkpoint(path, net, opt, epoch=0, optimizer=None, scheduler=None, extra=None, audio2style=None,
+                    audio2style_optimizer=None):
+    """`audio2style` / `audio2style_optimizer`: the co-trained encoder and its Adam, under the reference's keys `audio2style` and
+    `optim_style` (talker_trainer.py:913-937)."""
     state = {"epoch": epoch, "net": net.state_dict(), "para": opt.para() if hasattr(opt, "para") else {
         "featmap_size": opt.featmap_size, "featmap_nc": opt.featmap_nc, "pred_img_size": opt.pred_img_size}}
     if optimizer is not None:
         state["optim_state"] = optimizer.state_dict()
     if scheduler is not None:
         state["scheule_state"] = scheduler.state_dict()  # (sic) the reference's key
+    if audio2style is not None:
+        state["audio2style"] = audio2style.state_dict()
+    if audio2style_optimizer is not None:
+        state["optim_style"] = audio2style_optimizer.state_dict()
     if extra:
         state.update(extra)
     torch.save(state, path)
     return state
+
+
+def load_audio2style(path_or_dict, audio2style, optimizer=None, strict=True):
+    """Restore the encoder (key `audio2style`) and, if given, its optimizer (key `optim_style`) from a checkpoint, as
+    talker_trainer.py:754-762 does.  Returns the checkpoint dict."""
+    ck = torch.load(path_or_dict, map_location="cpu") if isinstance(path_or_dict, str) else path_or_dict
+    audio2style.load_state_dict(ck["audio2style"], strict=strict)
+    if optimizer is not None and "optim_style" in ck:
+        optimizer.load_state_dict(ck["optim_style"])
+    return ck
 
 
 def build_from_checkpoint(path_or_dict, include_gaze=False, eye_gaze_dim=2, strict=True, **net_kwargs):

@@ -346,9 +346,10 @@ def broadcast_parameters(module, src=0, group=None, force=False):
 
 
 class FlatBucket(torch.nn.Module):
-    """A flat fp32 parameter standing in for a co-trained module's gradients in the step's all-reduce.  The reference
-    trains an Audio2style LSTM next to the renderer (talker_trainer.py:428-473, second Adam at :665): 21.5 M parameters,
-    86 MB of fp32 gradients reduced next to HeadNeRFNet's 11-14 MB."""
+    """A flat fp32 parameter standing in for a co-trained module's gradients in the step's all-reduce (bench.py's training
+    step).  The reference trains an Audio2style LSTM next to the renderer (talker_trainer.py:428-473, second Adam at :665):
+    21.5 M parameters, 86 MB of fp32 gradients reduced next to HeadNeRFNet's 11-14 MB.  The real module is
+    n3dt.Audio2style; its grad_arena() is the bucket this stands in for."""
 
     AUDIO2STYLE_PARAMS = 21_546_624  # nn.LSTM(1280, 640, 2 layers, bidirectional) + RNNModel.fc1 (1280->640, unused in forward but a parameter) + Linear 1280-640-320-64 (talker_trainer.py:408-461)
 

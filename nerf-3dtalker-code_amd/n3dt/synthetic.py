@@ -340,3 +340,10 @@ def vgg16_features_state_dict(seed=0):
         idx += 2  # conv, ReLU
         cin = v
     return sd
+
+
+def mel_batch(B, seed=0):
+    """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
+    range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 256, (B, 80, 16), generator=gen, dtype=torch.uint8).float() / 32.0 - 4.0

@@ -155,10 +155,14 @@ def make_optimizer(net, lr=1e-4):
     return opt, sched
 
 
-def train_step(net, optimizer, inputs, gt_rgb, mask, t_rand=None, extra_optimizers=(), fused_loss=True, loss_utils=None):
+def train_step(net, optimizer, inputs, gt_rgb, mask, t_rand=None, extra_optimizers=(), fused_loss=True, loss_utils=None,
+               audio2style=None):
     """One reference-shaped step: forward("train") -> losses -> zero_grad -> backward -> step.  `loss_utils`: a HeadNeRFLossUtils
-    whose calc_total_loss forms the losses instead (the reference's own objective, e.g. with the VGG term)."""
-    pred = net("train", inputs["batch_xy"], inputs["batch_uv"], inputs["audiostyle"], bg_code=None,
+    whose calc_total_loss forms the losses instead (the reference's own objective, e.g. with the VGG term).  `audio2style`: the
+    co-trained encoder (n3dt.Audio2style); audiostyle = audio2style(inputs["mel_batch"]) then feeds the render
+    (talker_trainer.py:1002-1008), and its optimizer belongs in `extra_optimizers`."""
+    audiostyle = inputs["audiostyle"] if audio2style is None else audio2style(inputs["mel_batch"])
+    pred = net("train", inputs["batch_xy"], inputs["batch_uv"], audiostyle, bg_code=None,
                shape_code=inputs["shape_code"], appea_code=inputs["appea_code"], batch_Rmats=inputs["batch_Rmats"],
                batch_Tvecs=inputs["batch_Tvecs"], batch_inv_inmats=inputs["batch_inv_inmats"], t_rand=t_rand)
     if loss_utils is not None:
