@@ -516,10 +516,7 @@ template <class T>
 static void launch_to_rgb_wgrad(int nb, int HW, int co, const float* d_rgb, const T* net, float* dW, hipStream_t s, float* db = nullptr) {
     // pixels per workgroup: as many as leave ~512 workgroups (every workgroup ends in 3 co
     // same-address atomics: 1 536 workgroups x 96 atomics on 96 addresses were a third of the 44 us this took at 3 x 512^2)
-    static const int target = [] {
-        const char* e = getenv("N3DT_NR_RGBW_WGS");
-        return e ? atoi(e) : 512;
-    }();
+    const int target = 512;
     long pix = ((long)nb * HW + target - 1) / target;
     pix = (pix + 63) / 64 * 64;  // small maps (2 x 32^2 at 256 channels): 64-pixel workgroups instead of four of 512
     const int chunks = (int)((HW + pix - 1) / pix);

@@ -8,8 +8,9 @@
 //             2. compositing adjoint per ray                  train16_composite_bwd_kernel  -> d sigma per sample
 //             3. the dX chain, fused over all layers          nerf_bwd_x16_kernel: per block dZ_l = (W_{l+1}^T dZ_{l+1}) * relu'(H_l)
 //                kept in registers as MFMA operands; every dZ_l is also written as tile images (dzT)
-//             4. weight gradients dW_l = sum_samples dZ_l (x) X_l   dw_x16_kernel: both operands are pieces, streamed
-//                HBM -> LDS once per 12 x 6 tile block; bias gradients are the row sums of the same pieces
+//             4. weight gradients dW_l = sum_samples dZ_l (x) X_l   dw_x16_body: both operands are pieces, streamed HBM -> LDS
+//                once per block of tiles; bias gradients are the row sums of the same pieces.  Three launches: dw_x16_kernel
+//                (the merged RGB product), dw_x16_flat_kernel twice (the seven hidden products, then the two PE products)
 //             5. un-merge RGB_layer_0 / RGB_layer_1, density row, latent folding adjoint
 // RGB_layer_0 and RGB_layer_1 run merged (W_m = Wr1[:, :384] Wr0, no activation between them, models.py:79-81);
 // the chain rule through the product gives dWr1a = dW_m Wr0^T + db_m (x) br0, dWr0 = Wr1a^T dW_m, dbr0 = Wr1a^T db_m.
@@ -25,9 +26,7 @@
 // with camera gradients two more stages ride in the stream: d PE = W5[:, 0:63]^T dZ5 and W0[:, 0:63]^T dZ0 (48 pieces each)
 #define T16_BWD_PIECES_CAM (T16_BWD_PIECES + 2 * 48)
 #define T16_BWD_NCHUNK_CAM (T16_BWD_PIECES_CAM / X16_CH)
-#ifndef T16_BWD_WAVES
 #define T16_BWD_WAVES 4
-#endif
 
 extern "C" void n3dt_launch_nerf_fwd_x16_train(const N3dtGeom*, const void*, const float*, const float*, const float*, const float*,
                                                const float*, const float*, float*, float*, void*, void*, float*, void*, hipStream_t);
@@ -293,7 +292,7 @@ __device__ __forceinline__ void x16_bwd_pe_stage(WS& ws, const bf16x8 (&hin)[24]
     });
 }
 
-// (two waves per SIMD in either shape -- 8 waves in one workgroup or two 4-wave workgroups per CU -- i.e. a 256-register budget)
+// (two 4-wave workgroups per CU, two waves per SIMD: a 256-register budget)
 template <int WAVES, bool CAM>
 __global__ __launch_bounds__(WAVES * 64, 2) void nerf_bwd_x16_kernel(N3dtGeom g, const unsigned char* __restrict__ packT,
                                                                      const unsigned* __restrict__ gates,
@@ -529,14 +528,13 @@ struct DwArgs {
     float* rowsum;  // + frame * rs_stride, row index; nullptr: none
     long rs_stride;
     int blocks_per_frame, slices_per_frame, frames, gy;
+    unsigned* pace;  // PACE: progress counters of the workgroups that share a slice, [slice][gy] (zeroed by the caller); else unused
     // Row-major operands (the 2-D renderer's weight gradients, train_nr.hip): rowmajor != 0 -> A and B are 16-bit matrices
     // [pixel][channel] with ldA / ldB elements per row; a "block" is 32 consecutive pixels and piece (tile t, half s) of it is
     // the 16 x 32 sub-block rows 16 s .., channels 32 t ..: lane l fetches the 16 bytes at row l / 4, channel 8 (l % 4), which
     // lands in LDS as the same [sample][channel] image the MLP's producers store.  A may be several planes side by side
     // (a_plane_tiles tiles each, a_plane_bytes apart): the four sub-pixel planes of a gradient as one wide operand.
     // row_perm > 0: output row r (= q * row_perm + c) belongs at row 4 c + q of `out` / `rowsum` (pixel_shuffle's channel order).
-    int pace_lead, pace_sleeps;  // PACE tuning: blocks of lead tolerated, sleeps of ~0.25 us per block beyond it (max)
-    unsigned* pace;  // PACE: progress counters of the workgroups that share a slice, [slice][gy] (zeroed by the caller); else unused
     int rowmajor;
     long ldA, ldB;
     int a_plane_tiles;
@@ -549,14 +547,14 @@ struct DwArgs {
 #endif
 #define DW_NBUF(npp) (((DW_STAGES) * (npp) * X16_PIECE <= 160 * 1024) ? (DW_STAGES) : 3)
 
+// One product, one workgroup: the body of dw_x16_kernel (a launch of its own) and of dw_x16_flat_kernel (several products in one
+// launch, which picks the workgroup's place itself: y_in, slice_in).  `a` is __restrict__: without it the epilogue re-reads
+// its fields from the kernel arguments behind every atomic (300 scalar loads and waits in the 9-tile kernel).
 // RM: row-major operands (a compile-time switch: as run-time branches on a.rowmajor the extra live values cost the 12-tile
 // MLP kernel its last registers -- 132 bytes of scratch, 210 -> 650 us)
-// `list[0 .. n)`: products of ONE shape and plan walked by the same workgroup one after the other (n = 1: a single product).  With
-// n > 1 the launch is PERSISTENT: one workgroup per CU for the whole launch, so the gy workgroups that share a slice start together
-// and stay together (their second reads of the shared operand hit L2 without any pacing), and a product's epilogue -- 144 atomic
-// instructions per wave -- drains while the first stages of the NEXT product are already on their way into LDS.
 // In-kernel stamps (diagnostic build only: hipcc ... -DN3DT_DW_STAMPS -c csrc/train_mlp.hip, linked into a library of its own and
-// picked with N3DT_LIB; never timed, never shipped): where a block's cycles go, per wave of one workgroup (DESIGN 3.6b).
+// picked with N3DT_LIB; never timed, never shipped): where a block's cycles go, per wave of one workgroup -- the source of the
+// two constants of launch_dw_multi's cost model (docs/tuning_log.md, round 4).
 #ifdef N3DT_DW_STAMPS
 #define DW_STAMP(k)                                                                \
     {                                                                              \
@@ -570,16 +568,13 @@ struct DwArgs {
 #else
 #define DW_STAMP(k)
 #endif
-// EARLY (round 4): stage b + NBUF - 1 is issued DURING block b, one LDS-DMA piece after every second MFMA of its first half, instead of
-// stage b + NBUF in one burst behind the barrier that ends block b.  Its buffer, (b - 1) % NBUF, was left by every wave at the
-// PREVIOUS barrier, so nothing has to be waited for; the same two stages are in flight at every stage wait (the counted vmcnt is
-// unchanged).  Why: behind the barrier all eight waves issue their 4 - 5 pieces at once and stall in the vector-memory issue for
-// 350 - 650 cycles each with nothing queued on the matrix pipe (in-kernel stamps, DESIGN 3.6b); spread between MFMAs a wave's stall
-// hides under the MFMAs both waves of its SIMD have in flight.
-template <int WO, int WI, int TO, int TI, bool RM = false, int NTM = 0, bool PACE = false, bool EARLY = false>
-__device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, const int n_products, const int y_in = -1, const int slice_in = -1) {
+// PACE: the two workgroups of a gy = 2 slice keep in step (see below).  DW_PACE_LEAD: blocks of lead tolerated; DW_PACE_SLEEPS: the
+// most sleeps of ~0.25 us taken per check, one per block of lead beyond that.
+#define DW_PACE_LEAD 0
+#define DW_PACE_SLEEPS 12
+template <int WO, int WI, int TO, int TI, bool RM = false, bool PACE = false>
+__device__ __forceinline__ void dw_x16_body(const DwArgs& __restrict__ a, const int y_in = -1, const int slice_in = -1) {
     static_assert(WO * WI == 8, "8 waves");
-    const DwArgs& a = list[0];  // (the plan -- slices, blocks, tile counts -- is the same for every product of the list)
     // NBUF stages of one block's pieces in LDS, NBUF - 1 of them in flight.  The kernel is HBM-latency bound (one workgroup
     // per CU, 36-40 KiB per block): the bytes in flight set the bandwidth.  4 stages where they fit the 160 KiB of LDS.
     constexpr int NA = WO * TO, NBT = WI * TI, NP = 2 * (NA + NBT), NPP = (NP + 7) / 8 * 8, PPW = NPP / 8;
@@ -607,35 +602,29 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
     // this wave's share of a stage: pieces q = wave + 8 i
     const unsigned char* src[PPW];
     size_t stride[PPW];
-    auto setup = [&](const DwArgs& pa) {
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            int q = wave + 8 * i;
-            if (q >= NP) q = NP - 1;  // padding slots re-load the last piece
-            const bool isA = q < 2 * NA;
-            const int qq = isA ? q : q - 2 * NA;
-            int tile = (isA ? oy * NA : iy * NBT) + (qq >> 1);
-            const int nt = isA ? pa.nA : pa.nB;
-            if (tile >= nt) tile = nt - 1;  // dead tiles re-load a valid one; their results are not written
-            if constexpr (RM) {
-                const long ld = isA ? pa.ldA : pa.ldB;
-                const int t = (isA ? pa.a_tile0 : pa.b_tile0) + tile;
-                size_t off = ((size_t)(16 * (qq & 1) + (lane >> 2)) * ld + 8 * (lane & 3)) * 2;
-                if (isA && pa.a_plane_tiles > 0) off += (size_t)(t / pa.a_plane_tiles) * pa.a_plane_bytes + (size_t)(t % pa.a_plane_tiles) * 64;
-                else off += (size_t)t * 64;
-                src[i] = (isA ? pa.A : pa.B) + off;
-                stride[i] = (size_t)32 * ld * 2;
-            } else {
-                const size_t off = ((size_t)((isA ? pa.a_tile0 : pa.b_tile0) + tile) * 2 + (qq & 1)) * X16_PIECE;
-                src[i] = (isA ? pa.A : pa.B) + off + lane * 16;
-                stride[i] = isA ? pa.strideA : pa.strideB;
-            }
+    for (int i = 0; i < PPW; ++i) {
+        int q = wave + 8 * i;
+        if (q >= NP) q = NP - 1;  // padding slots re-load the last piece
+        const bool isA = q < 2 * NA;
+        const int qq = isA ? q : q - 2 * NA;
+        int tile = (isA ? oy * NA : iy * NBT) + (qq >> 1);
+        const int nt = isA ? a.nA : a.nB;
+        if (tile >= nt) tile = nt - 1;  // dead tiles re-load a valid one; their results are not written
+        if constexpr (RM) {
+            const long ld = isA ? a.ldA : a.ldB;
+            const int t = (isA ? a.a_tile0 : a.b_tile0) + tile;
+            size_t off = ((size_t)(16 * (qq & 1) + (lane >> 2)) * ld + 8 * (lane & 3)) * 2;
+            if (isA && a.a_plane_tiles > 0) off += (size_t)(t / a.a_plane_tiles) * a.a_plane_bytes + (size_t)(t % a.a_plane_tiles) * 64;
+            else off += (size_t)t * 64;
+            src[i] = (isA ? a.A : a.B) + off;
+            stride[i] = (size_t)32 * ld * 2;
+        } else {
+            const size_t off = ((size_t)((isA ? a.a_tile0 : a.b_tile0) + tile) * 2 + (qq & 1)) * X16_PIECE;
+            src[i] = (isA ? a.A : a.B) + off + lane * 16;
+            stride[i] = isA ? a.strideA : a.strideB;
         }
-    };
-    setup(a);
-    // NTM (experiment, N3DT_DW_NT): cache policy of the stream.  The B pieces are read by ONE workgroup, the A pieces by the gy
-    // workgroups of a slice (the second reader is meant to hit L2): 1 = B non-temporal, so that what is read once does not evict
-    // what is read twice; 2 = everything non-temporal.  (Which operand a piece belongs to depends on i alone when 2 NA % 8 == 0.)
+    }
     // A stage has NP real pieces in NPP = 8 PPW slots: the last slot of waves >= LAST_REAL is padding, and they do not load it.  What
     // a CU can take into LDS is what bounds this kernel (tools/lds_fill_probe.hip: 23 B/clk per CU by LDS-DMA, 25 - 28 through
     // registers, L2-resident source; the seven-product launch moves 20), so the 4 padding pieces of a 36-piece stage were 10 % of
@@ -646,24 +635,22 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
         unsigned char* dst = lds + (size_t)(b % NBUF) * STAGE;
         static_for<0, PPW>([&](auto i_c) {
             constexpr int i = decltype(i_c)::value;
-            constexpr bool is_b = (2 * NA) % 8 == 0 && 8 * i >= 2 * NA;
-            constexpr int aux = (NTM == 2 || (NTM == 1 && is_b)) ? 2 : 0;
             if (i < PPW - 1 || full)
                 __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src[i] + (size_t)b * stride[i]),
-                                                 (LDS_AS void*)(dst + (wave + 8 * i) * X16_PIECE), 16, 0, aux);
+                                                 (LDS_AS void*)(dst + (wave + 8 * i) * X16_PIECE), 16, 0, 0);
         });
     };
 
     f32x16 acc[TO][TI];
     float rs[TO];
-    bool do_rs = false;  // (per product)
+    bool do_rs = false;
     const unsigned tr_off = RM ? x16_tr_lane_offset_natural(lane) : x16_tr_lane_offset(lane);
     const unsigned lds_base = (unsigned)(size_t)(LDS_AS unsigned char*)lds;
 
     // PACE: the gy = 2 workgroups of a slice stream the SAME A pieces; the second reader hits L2 only while it stays within a few
     // microseconds of the first (a line lives ~6 us in an XCD's 4 MiB at 700 GB/s), and the two drift apart: measured 1.42x the
     // algorithmic bytes fetched (1.5x = no sharing at all).  Every four blocks wave 0 publishes the workgroup's progress and looks
-    // at its partner's (same XCD, same L2: a plain store and a glc scalar load); whoever is more than PACE_LEAD blocks ahead sleeps
+    // at its partner's (same XCD, same L2: a plain store and a glc scalar load); whoever is more than DW_PACE_LEAD blocks ahead sleeps
     // a little before the stage barrier.  Purely a pacing heuristic: a stale or missing value only changes who sleeps, never a
     // result, and every sleep is bounded, so a partner that is not resident yet cannot hold anyone up for long.
     unsigned* pace_mine = nullptr;
@@ -716,46 +703,6 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
             }
         }
     };
-    // EARLY: the 9 (TO x TI) MFMAs of a half block with the PPW pieces of stage `bi` issued between them
-    auto mfma_half_issue = [&](const Half& hf, const long bi, const bool do_issue) {
-        bf16x8 fa[TO], fb[TI];
-#pragma unroll
-        for (int i = 0; i < TO; ++i) fa[i] = __builtin_bit_cast(bf16x8, x16_u32x4{hf.a[i][0][0], hf.a[i][0][1], hf.a[i][1][0], hf.a[i][1][1]});
-#pragma unroll
-        for (int j = 0; j < TI; ++j) fb[j] = __builtin_bit_cast(bf16x8, x16_u32x4{hf.b[j][0][0], hf.b[j][0][1], hf.b[j][1][0], hf.b[j][1][1]});
-        unsigned char* dst = lds + (size_t)(bi % NBUF) * STAGE;
-        static_for<0, TO * TI>([&](auto k_c) {
-            constexpr int k = decltype(k_c)::value;
-            constexpr int i = k / TI, j = k % TI;
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-            // piece q after MFMA 2 q + 1 (PPW <= 5 pieces over 9 MFMAs); with fewer MFMAs than that the rest go out at the end
-            constexpr int q = (k % 2 == 1) ? k / 2 : -1;
-            if constexpr (q >= 0 && q < PPW) {
-                if (do_issue && (q < PPW - 1 || full)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src[q] + (size_t)bi * stride[q]),
-                                                     (LDS_AS void*)(dst + (wave + 8 * q) * X16_PIECE), 16, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        });
-        constexpr int done = (TO * TI) / 2;  // pieces 0 .. done - 1 went out above
-        static_for<(done < PPW ? done : PPW), PPW>([&](auto q_c) {
-            constexpr int q = decltype(q_c)::value;
-            if (do_issue && (q < PPW - 1 || full))
-                __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src[q] + (size_t)bi * stride[q]),
-                                                 (LDS_AS void*)(dst + (wave + 8 * q) * X16_PIECE), 16, 0, 0);
-        });
-        if (do_rs) {
-#pragma unroll
-            for (int i = 0; i < TO; ++i) {
-                float t = 0.0f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) t += (float)fa[i][j];
-                rs[i] += t;
-            }
-        }
-    };
     // Stage s has landed when at most the loads of the younger stages in flight are outstanding (loads return in order);
     // near the end fewer stages follow: wait for everything (uniform branch).  Then everyone's pieces of it are visible and
     // everyone has left the buffer the next issue() refills.  A raw s_barrier: __syncthreads() carries a workgroup release
@@ -781,8 +728,6 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
     for (int i = 0; i < NBUF - 1; ++i)
         if (b0 + i < b1) issue(b0 + i);
     const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & (DW_XCDS - 1);  // HW_REG_XCC_ID, bits 3:0 (see the epilogue)
-    for (int kp = 0; kp < n_products; ++kp) {
-    const DwArgs& pa = list[kp];
 #pragma unroll
     for (int i = 0; i < TO; ++i) {
         rs[i] = 0.0f;
@@ -791,14 +736,14 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     }
-    do_rs = pa.rowsum != nullptr && iy == 0 && wi == 0;
+    do_rs = a.rowsum != nullptr && iy == 0 && wi == 0;
     Half cur, nxt;
 #ifdef N3DT_DW_STAMPS
     unsigned long long st_sum[7] = {0, 0, 0, 0, 0, 0, 0}, st_prev = 0, st_begin;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_begin)::"memory");
 #endif
     stage_ready(b0);
-    if (!EARLY && b0 + NBUF - 1 < b1) issue(b0 + NBUF - 1);
+    if (b0 + NBUF - 1 < b1) issue(b0 + NBUF - 1);
     read_half(cur, buf_of(b0), std::integral_constant<int, 0>{});
     x16_tr_settle();
     pin_half(cur);
@@ -806,9 +751,9 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
         if (PACE && pace_mine && wave == 0) {
             const unsigned mine = (unsigned)(b - b0);
             if ((mine & 3u) == 1u) {  // the value requested at the previous multiple of four has landed (the settle below waited)
-                const int lead = (int)mine - (int)other_progress - a.pace_lead;
+                const int lead = (int)mine - (int)other_progress - DW_PACE_LEAD;
                 if (lead > 0) {
-                    const int n = lead < a.pace_sleeps ? lead : a.pace_sleeps;
+                    const int n = lead < DW_PACE_SLEEPS ? lead : DW_PACE_SLEEPS;
                     for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(8);  // 8 x 64 cycles = ~0.25 us each
                 }
             }
@@ -820,8 +765,7 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
         // second half of block b on its way; first half through the matrix pipe
         DW_STAMP(0)
         read_half(nxt, buf_of(b), std::integral_constant<int, 1>{});
-        if constexpr (EARLY) mfma_half_issue(cur, b + NBUF - 1, b + NBUF - 1 < b1);  // into the buffer of block b - 1: free since the last barrier
-        else mfma_half(cur);
+        mfma_half(cur);
         x16_tr_settle();
         pin_half(nxt);
         DW_STAMP(1)
@@ -830,7 +774,7 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
         if (more) {
             stage_ready(b + 1);
             DW_STAMP(2)
-            if (!EARLY && b + NBUF < b1) issue(b + NBUF);
+            if (b + NBUF < b1) issue(b + NBUF);
             DW_STAMP(3)
         }
         // first half of block b + 1 on its way (the last block re-reads its own buffer: the read is unconditional, because a
@@ -840,14 +784,6 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
         x16_tr_settle();
         pin_half(cur);
         DW_STAMP(4)
-    }
-    // (persistent form) every wave has settled its last reads of this product's stages past this barrier: the ring is free for the
-    // next product's first stages, issued after the epilogue.  All of this product's loads have landed (the last stage_ready
-    // waited for vmcnt(0)); the wait is written out so that every barrier of an LDS-DMA kernel has one (tests/test_host_cpu.py).
-    if (kp + 1 < n_products) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
     }
     // Combine across slices.  Device-scope fp32 atomics from 256 workgroups onto one 384 x 384 result cost 60-70 us of a
     // 250 us launch (measured by disabling them): the eight XCDs' L2s are not coherent with each other, so those atomics
@@ -861,80 +797,62 @@ __device__ __forceinline__ void dw_x16_body(const DwArgs* __restrict__ list, con
     // never the scope but the eight-fold spread of the same-address traffic.  XCC_ID names the XCC a wave runs on in every
     // partition mode of this part (SPX: 0..7; DPX / QPX: 0..3 / 0..1; CPX: one XCC per device, id 0): `& 7` never aliases,
     // and whichever buffer a workgroup picks, the sum over the eight buffers is the gradient.
-    float* const part = pa.part + (size_t)xcc * pa.rows_valid * pa.cols_valid;
-    // (opaque copies: inside the product loop the compiler would otherwise hoist the ~50 row / column indices below out of the
-    //  loop as invariants and keep them in registers through the main loop -- the 9-tile kernel then spills)
-    int he = h, ce = c;
-    asm volatile("" : "+v"(he), "+v"(ce));
+    float* const part = a.part + (size_t)xcc * a.rows_valid * a.cols_valid;
 #pragma unroll
     for (int i = 0; i < TO; ++i) {
         const int to = oy * NA + wo * TO + i;
-        if (to >= pa.nA) continue;
+        if (to >= a.nA) continue;
 #pragma unroll
         for (int j = 0; j < TI; ++j) {
             const int ti = iy * NBT + wi * TI + j;
-            if (ti >= pa.nB) continue;
-            const int col = ti * 32 + ce;
+            if (ti >= a.nB) continue;
+            const int col = ti * 32 + c;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = to * 32 + (r & 3) + 8 * (r >> 2) + 4 * he;
-                if (row < pa.rows_valid && col < pa.cols_valid)
-                    __hip_atomic_fetch_add(part + (size_t)row * pa.cols_valid + col, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int row = to * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (row < a.rows_valid && col < a.cols_valid)
+                    __hip_atomic_fetch_add(part + (size_t)row * a.cols_valid + col, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         if (do_rs) {
             const float t = rs[i] + __shfl_xor(rs[i], 32, 64);
-            const int row = to * 32 + ce;
-            const int rrow = (RM && pa.row_perm > 0) ? 4 * (row % pa.row_perm) + row / pa.row_perm : row;
-            if (he == 0 && row < pa.rows_valid) atomicAdd(pa.rowsum + (size_t)f * pa.rs_stride + rrow, t);
+            const int row = to * 32 + c;
+            const int rrow = (RM && a.row_perm > 0) ? 4 * (row % a.row_perm) + row / a.row_perm : row;
+            if (h == 0 && row < a.rows_valid) atomicAdd(a.rowsum + (size_t)f * a.rs_stride + rrow, t);
         }
     }
 #ifdef N3DT_DW_STAMPS
     DW_STAMP(5)  // epilogue issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     DW_STAMP(6)  // ... and drained
-    if (TO == 3 && TI == 3 && blockIdx.x == 9 && (gridDim.y == 1 || blockIdx.y == 3) && lane == 0)
+    if (TO == 3 && TI == 3 && blockIdx.x == 9 && lane == 0)
         printf("dw stamps wave %d blocks %ld: half0 %llu ready %llu issue %llu half1 %llu | epilogue issue %llu drain %llu | whole %llu\n", wave,
                (long)(b1 - b0), st_sum[1], st_sum[2], st_sum[3], st_sum[4], st_sum[5], st_sum[6], st_prev - st_begin);
 #endif
-    if (kp + 1 < n_products) {
-        // the NEXT product's first stages travel while the atomics above drain (issued after them: the stage addresses would
-        // otherwise live through the epilogue, and the 9-tile kernel has no registers left for that)
-        setup(list[kp + 1]);
-#pragma unroll
-        for (int i = 0; i < NBUF - 1; ++i)
-            if (b0 + i < b1) issue(b0 + i);
-    }
-    }  // products
 }
 
 template <int WO, int WI, int TO, int TI, bool RM = false>
 __global__ __launch_bounds__(512, 1) void dw_x16_kernel(DwArgs a) {
-    dw_x16_body<WO, WI, TO, TI, RM>(&a, 1);
+    dw_x16_body<WO, WI, TO, TI, RM>(a);
 }
-// Several weight-gradient products of one shape in ONE launch (blockIdx.y picks the product): the seven 384 x 384 hidden
-// layers used to be seven launches of 256 workgroups, each ending in its atomic phase with the HBM idle; in one grid the
+// Several weight-gradient products of one shape in ONE launch, as one flat, XCD-balanced list of workgroups: the seven 384 x 384
+// hidden layers used to be seven launches of 256 workgroups, each ending in its atomic phase with the HBM idle; in one grid the
 // workgroups of the next product stream while the previous one's atomics drain (different resources: L2 atomics vs HBM).
+// Workgroup L runs on XCD L % 8 whatever the grid's shape (the dispatcher deals workgroup ids round-robin over the eight XCDs), so a
+// (workgroups, products) grid balances the XCDs only when the real workgroups of EVERY product are a multiple of 8 x gy: with the
+// slice count padded to a multiple of 8 the padding lands on the same XCDs in every product (36 workgroups per product = 18
+// slices: XCDs 0 and 1 get 42 workgroups, the others 28 -- two rounds on a quarter of the chip).  Here unit k (a pair of column
+// halves when gy = 2, else one workgroup) of the n x slices units goes to XCD k % 8:
+// L = 16 (k / 8) + 8 y + k % 8 (gy = 2) or L = k (gy = 1); every XCD gets the same number of real workgroups to within one unit, and
+// the two halves of a pair still sit 8 ids apart on one XCD.  With that, ONE round of long slices is possible: a workgroup's
+// fixed cost (first stages, 144 atomic instructions per wave: ~45 k cycles, 16 % of a 128-block slice) is paid once per CU
+// instead of seven times.
 #define DW_MULTI_MAX 8
 struct DwArgsN {
     DwArgs a[DW_MULTI_MAX];
     int n;
 };
-template <int WO, int WI, int TO, int TI, int NTM = 0, bool PACE = false>
-__global__ __launch_bounds__(512, 1) void dw_x16_multi_kernel(DwArgsN m) {
-    dw_x16_body<WO, WI, TO, TI, false, NTM, PACE>(&m.a[blockIdx.y], 1);
-}
-// The same products as ONE flat, XCD-balanced list of workgroups (round 4).  Workgroup L runs on XCD L % 8 whatever the grid's shape
-// (the dispatcher deals workgroup ids round-robin over the eight XCDs), so the (workgroups, products) grid above balances the
-// XCDs only when the real workgroups of EVERY product are a multiple of 8 x gy: with the slice count padded to a multiple of 8
-// the padding lands on the same XCDs in every product (36 workgroups per product = 18 slices: XCDs 0 and 1 get 42 workgroups,
-// the others 28 -- two rounds on a quarter of the chip, which is what made every "fewer, longer workgroups" experiment of round 3
-// look slower).  Here unit k (a pair of column halves when gy = 2, else one workgroup) of the n x slices units goes to XCD k % 8:
-// L = 16 (k / 8) + 8 y + k % 8 (gy = 2) or L = k (gy = 1); every XCD gets the same number of real workgroups to within one unit, and
-// the two halves of a pair still sit 8 ids apart on one XCD.  With that, ONE round of long slices is possible: a workgroup's
-// fixed cost (first stages, 144 atomic instructions per wave: ~45 k cycles, 16 % of a 128-block slice) is paid once per CU
-// instead of seven times.
-template <int WO, int WI, int TO, int TI, int NTM = 0, bool PACE = false, bool EARLY = false>
+template <int WO, int WI, int TO, int TI, bool PACE>
 __global__ __launch_bounds__(512, 1) void dw_x16_flat_kernel(DwArgsN m) {
     const int L = blockIdx.x;
     const int gy = m.a[0].gy;  // 1 or 2
@@ -942,137 +860,68 @@ __global__ __launch_bounds__(512, 1) void dw_x16_flat_kernel(DwArgsN m) {
     const int y = gy == 2 ? (L >> 3) & 1 : 0;
     const int total = m.a[0].slices_per_frame * m.a[0].frames;
     if (k >= m.n * total) return;
-    dw_x16_body<WO, WI, TO, TI, false, NTM, PACE, EARLY>(&m.a[k / total], 1, y, k % total);
-}
-// the persistent form: one workgroup per CU walks all n products (see dw_x16_body)
-template <int WO, int WI, int TO, int TI>
-__global__ __launch_bounds__(512, 1) void dw_x16_persist_kernel(DwArgsN m) {
-    dw_x16_body<WO, WI, TO, TI, false, 0, false>(m.a, m.n);
+    dw_x16_body<WO, WI, TO, TI, false, PACE>(m.a[k / total], y, k % total);
 }
 
-template <int WO, int WI, int TO, int TI>
-static void dw_plan(const N3dtGeom* g, DwArgs& a, int& wgs, size_t& lds_bytes, int target_override = 0) {
-    constexpr int NA = WO * TO, NBT = WI * TI, NPP = (2 * (NA + NBT) + 7) / 8 * 8;
-    const int bpr = (g->n_samples + 31) / 32;
-    a.blocks_per_frame = g->n_rays * bpr;
-    const int gy = ((a.nA + NA - 1) / NA) * ((a.nB + NBT - 1) / NBT);
-    static const int env_wgs = [] {
-        const char* e = getenv("N3DT_DW_WGS");
-        return e ? atoi(e) : 256;
-    }();
-    const int target_wgs = target_override > 0 ? target_override : env_wgs;
-    int spf = (target_wgs + g->batch * gy - 1) / (g->batch * gy);
-    if (spf > a.blocks_per_frame / 8) spf = a.blocks_per_frame / 8;
-    if (spf < 1) spf = 1;
-    a.slices_per_frame = spf;
-    a.frames = g->batch;
-    a.gy = gy;
-    wgs = (spf * g->batch + 7) / 8 * 8 * gy;
-    lds_bytes = (size_t)DW_NBUF(NPP) * NPP * X16_PIECE;
-}
-// n products of the same shape (and therefore the same plan) in one launch
-template <int WO, int WI, int TO, int TI>
-static void launch_dw_multi(const N3dtGeom* g, DwArgs* list, int n, hipStream_t s) {
+// n products of the same shape (and therefore the same plan) in one launch.  GY: the workgroups that share a slice, i.e. the
+// products' tiles over a workgroup's -- 2 for 12 x 12 tiles in 12 x 6, 1 for 12 x 2 in 12 x 2; the flat kernel knows no other.
+template <int WO, int WI, int TO, int TI, int GY>
+static void launch_dw_multi(const N3dtGeom* g, const DwArgs* list, int n, hipStream_t s) {
+    static_assert(GY == 1 || GY == 2, "one workgroup per slice, or a paced pair");
+    constexpr int NA = WO * TO, NBT = WI * TI, NPP = (2 * (NA + NBT) + 7) / 8 * 8, gy = GY;
+    const int bpf = g->n_rays * ((g->n_samples + 31) / 32), B = g->batch;
+    const size_t lds_bytes = (size_t)DW_NBUF(NPP) * NPP * X16_PIECE;
+    // slices per frame: the count that minimises rounds x (blocks per slice x cycles per block + a workgroup's fixed cost);
+    // a round = 256 workgroups, one per CU (measured, in-kernel stamps: ~2 450 cycles per block, ~45 000 per workgroup)
+    int best = 1;
+    double best_t = 1e30;
+    const int max_spf = bpf / 8 > 1 ? bpf / 8 : 1;
+    for (int spf = 1; spf <= max_spf && (long)n * B * spf * gy <= 8 * 256; ++spf) {
+        const long units = (long)n * B * spf, wg = units * gy;
+        const long rounds = (wg + 255) / 256;
+        const double t = (double)rounds * ((double)((bpf + spf - 1) / spf) * 2450.0 + 45000.0);
+        if (t < best_t * 0.995) best_t = t, best = spf;   // (ties go to the smaller count: fewer atomics)
+    }
     DwArgsN m;
-    int wgs = 0;
-    size_t lds_bytes = 0;
-    // N3DT_DW_WGS7: workgroups per product of the seven-product launch ONLY (N3DT_DW_WGS applies to every weight-gradient launch,
-    // so with it the single-product launches shrink too and confound the comparison)
-    static const int wgs7 = [] {
-        const char* e = getenv("N3DT_DW_WGS7");
-        return e ? atoi(e) : 0;
-    }();
-    for (int i = 0; i < n; ++i) {
-        dw_plan<WO, WI, TO, TI>(g, list[i], wgs, lds_bytes, n >= 3 ? wgs7 : 0);
-        m.a[i] = list[i];
-    }
-    static const int ntm = [] {
-        const char* e = getenv("N3DT_DW_NT");
-        return e ? atoi(e) : 0;
-    }();
-    // Round 3 (the (workgroups, products) grid, 128-block slices), where it was off: the pacing does what it is for -- FETCH_SIZE of the seven-product launch falls from 7.99 GB
-    // to 6.26 GB (1.42x -> 1.11x the algorithmic 5.64 GB) -- and the launch takes exactly as long (1.40 ms; config 3 step 6.06
-    // against 6.06 - 6.10 ms over six lead / sleep settings): the kernel is not bound by HBM bytes but by its own per-block
-    // sequence (stage wait, barrier, 96 KiB of transposed LDS reads, then 18 MFMAs per wave, all eight waves in step).
-    // Round 4: ON for the flat long-slice form (N3DT_DW_PACE=0 switches it off).  There a pair walks ~900 blocks and drifts apart
-    // completely without it (FETCH_SIZE 8.30 GB = 1.47x the algorithmic bytes: no sharing at all); with lead 0 it fetches 6.51 GB
-    // (1.15x) in the same time (profiles/r04_d_*: step 6.03 against 6.03 ms) -- 1.8 GB of HBM reads per step for nothing.
-    static const int pace = [] {
-        const char* e = getenv("N3DT_DW_PACE");
-        return e ? atoi(e) : 1;
-    }();
     m.n = n;
-    static const int persist = [] {
-        const char* e = getenv("N3DT_DW_PERSIST");
-        return e ? atoi(e) : 0;
-    }();
-    // (experiment, off: measured 6.17 ms against 6.02 ms per config-3 step -- with the (workgroups x products) grid the dispatcher
-    //  hands a CU the next product's workgroup the moment its own finishes, which balances the tail better than a fixed walk)
-    if (persist && n > 1) {
-        auto pk = dw_x16_persist_kernel<WO, WI, TO, TI>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(pk, dim3(wgs), dim3(512), lds_bytes, s, m);
-        return;
+    for (int i = 0; i < n; ++i) {
+        m.a[i] = list[i];
+        m.a[i].blocks_per_frame = bpf;
+        m.a[i].slices_per_frame = best;
+        m.a[i].frames = B;
+        m.a[i].gy = gy;
     }
-    const bool paced = pace && list[0].pace != nullptr && list[0].gy == 2;
-    static const int flat = [] {
-        const char* e = getenv("N3DT_DW_FLAT");
-        return e ? atoi(e) : 1;
-    }();
-    if (flat && ntm == 0 && wgs7 == 0 && (list[0].gy == 1 || list[0].gy == 2)) {
-        // slices per frame: the count that minimises rounds x (blocks per slice x cycles per block + a workgroup's fixed cost);
-        // a round = 256 workgroups, one per CU (measured, in-kernel stamps: ~2 450 cycles per block, ~45 000 per workgroup)
-        const int gy = list[0].gy, bpf = list[0].blocks_per_frame, B = g->batch;
-        int best = 1;
-        double best_t = 1e30;
-        const int max_spf = bpf / 8 > 1 ? bpf / 8 : 1;
-        for (int spf = 1; spf <= max_spf && (long)n * B * spf * gy <= 8 * 256; ++spf) {
-            const long units = (long)n * B * spf, wg = units * gy;
-            const long rounds = (wg + 255) / 256;
-            const double t = (double)rounds * ((double)((bpf + spf - 1) / spf) * 2450.0 + 45000.0);
-            if (t < best_t * 0.995) best_t = t, best = spf;   // (ties go to the smaller count: fewer atomics)
-        }
-        for (int i = 0; i < n; ++i) m.a[i].slices_per_frame = best;
-        const long units = (long)n * B * best;
-        const int grid = gy == 2 ? (int)((units + 7) / 8) * 16 : (int)units;
-        static const int early = [] {
-            const char* e = getenv("N3DT_DW_EARLY");
-            return e ? atoi(e) : 0;
-        }();
-        auto fk = early ? (paced ? dw_x16_flat_kernel<WO, WI, TO, TI, 0, true, true> : dw_x16_flat_kernel<WO, WI, TO, TI, 0, false, true>)
-                        : (paced ? dw_x16_flat_kernel<WO, WI, TO, TI, 0, true> : dw_x16_flat_kernel<WO, WI, TO, TI, 0, false>);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(fk, dim3(grid), dim3(512), lds_bytes, s, m);
-        return;
-    }
-    auto kern = paced ? dw_x16_multi_kernel<WO, WI, TO, TI, 0, true>
-                      : (ntm == 1 ? dw_x16_multi_kernel<WO, WI, TO, TI, 1> : (ntm == 2 ? dw_x16_multi_kernel<WO, WI, TO, TI, 2> : dw_x16_multi_kernel<WO, WI, TO, TI, 0>));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(wgs, n), dim3(512), lds_bytes, s, m);
+    const long units = (long)n * B * best;
+    const int grid = gy == 2 ? (int)((units + 7) / 8) * 16 : (int)units;
+    // Paced where two workgroups share a slice: a pair walks ~900 blocks and drifts apart completely without it (FETCH_SIZE 8.30 GB =
+    // 1.47x the algorithmic bytes: no sharing at all); paced it fetches 6.51 GB (1.15x) in the same time -- 1.8 GB of HBM reads per
+    // step for nothing.  (In the same time: the kernel is bound by its per-block sequence, not by HBM bytes.)
+    auto fk = dw_x16_flat_kernel<WO, WI, TO, TI, GY == 2>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(fk, dim3(grid), dim3(512), lds_bytes, s, m);
 }
 
+// Slices of a single-product launch: about one workgroup per CU in total (the fp32 atomics that combine the slices cost ~0.1 ms
+// per launch per extra 256 workgroups), at least 8 blocks per slice.  Fills the plan in; returns the grid (slices padded to 8, x gy).
+static int dw_plan_slices(DwArgs& a, int blocks_per_frame, int frames, int gy) {
+    int spf = (256 + frames * gy - 1) / (frames * gy);
+    if (spf > blocks_per_frame / 8) spf = blocks_per_frame / 8;
+    if (spf < 1) spf = 1;
+    a.blocks_per_frame = blocks_per_frame;
+    a.slices_per_frame = spf;
+    a.frames = frames;
+    a.gy = gy;
+    return (spf * frames + 7) / 8 * 8 * gy;
+}
 template <int WO, int WI, int TO, int TI>
 static void launch_dw(const N3dtGeom* g, DwArgs a, hipStream_t s) {
     constexpr int NA = WO * TO, NBT = WI * TI, NPP = (2 * (NA + NBT) + 7) / 8 * 8;
-    const int bpr = (g->n_samples + 31) / 32;
-    a.blocks_per_frame = g->n_rays * bpr;
     const int gy = ((a.nA + NA - 1) / NA) * ((a.nB + NBT - 1) / NBT);
-    // about one workgroup per CU in total (N3DT_DW_WGS overrides), at least 8 blocks per slice
-    static const int target_wgs = [] {
-        const char* e = getenv("N3DT_DW_WGS");
-        return e ? atoi(e) : 256;  // one workgroup per CU: the fp32 atomics that combine the slices cost ~0.1 ms per launch per extra 256 workgroups
-    }();
-    int spf = (target_wgs + g->batch * gy - 1) / (g->batch * gy);
-    if (spf > a.blocks_per_frame / 8) spf = a.blocks_per_frame / 8;
-    if (spf < 1) spf = 1;
-    a.slices_per_frame = spf;
-    a.frames = g->batch;
-    a.gy = gy;
-    const int slices8 = (spf * g->batch + 7) / 8 * 8;
+    const int grid = dw_plan_slices(a, g->n_rays * ((g->n_samples + 31) / 32), g->batch, gy);
     const size_t lds_bytes = (size_t)DW_NBUF(NPP) * NPP * X16_PIECE;
     auto kern = dw_x16_kernel<WO, WI, TO, TI>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(slices8 * gy), dim3(512), lds_bytes, s, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, s, a);
 }
 
 // out[row][col] += sum over the XCDs' partial buffers, for every weight-gradient launch of the step in one pass
@@ -1336,21 +1185,11 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
     // ---- fused dX chain
     const int span_dx = n3dt_prof_span_begin(s);  // span 2 of 3
     {
-        static const int waves = [] {
-            const char* e = getenv("N3DT_T16_BWD_WAVES");
-            return e ? atoi(e) : T16_BWD_WAVES;
-        }();
-        const size_t lds_base_bytes = (size_t)X16_NBUF * X16_CH * X16_PIECE;
-        auto go = [&](auto kern, const int wv) {
-            const size_t lds_bytes = lds_base_bytes + (size_t)wv * T16_GATE_SLOT;  // ring + one gate-word slot per wave
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(kern, dim3((unsigned)((blocks + wv - 1) / wv)), dim3(wv * 64), lds_bytes, s, *g, packT,
-                               reinterpret_cast<const unsigned*>(sb + sv.gates), gS, weight, dsig,
-                               dgray, dzT, dpe5, dpe0, bpr, blocks);
-        };
-        if (cam) go(nerf_bwd_x16_kernel<4, true>, 4);
-        else if (waves == 8) go(nerf_bwd_x16_kernel<8, false>, 8);
-        else go(nerf_bwd_x16_kernel<4, false>, 4);
+        const size_t lds_bytes = (size_t)X16_NBUF * X16_CH * X16_PIECE + (size_t)T16_BWD_WAVES * T16_GATE_SLOT;  // ring + one gate-word slot per wave
+        auto kern = cam ? nerf_bwd_x16_kernel<T16_BWD_WAVES, true> : nerf_bwd_x16_kernel<T16_BWD_WAVES, false>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((blocks + T16_BWD_WAVES - 1) / T16_BWD_WAVES)), dim3(T16_BWD_WAVES * 64), lds_bytes, s, *g, packT,
+                           reinterpret_cast<const unsigned*>(sb + sv.gates), gS, weight, dsig, dgray, dzT, dpe5, dpe0, bpr, blocks);
     }
     n3dt_prof_span_end(span_dx, s);
     if (d_ray_bias)  // include_vd: per-ray sums of the merged RGB rows of dZ (the caller's autograd turns them into d W_vd, d R)
@@ -1373,14 +1212,11 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
         launch_fold_bwd(p, gp, S, A, U, B, shape, appea, audio, dfold, d_shape, d_appea, d_audio, s, /*codes_zeroed=*/true);
         return;
     }
-    // ---- weight gradients (per-XCD partial sums, reduced once at the end: see dw_x16_kernel)
+    // ---- weight gradients (per-XCD partial sums, reduced once at the end: see dw_x16_body)
     const size_t strideX = (size_t)X16_XT_TILES * 2 * X16_PIECE, strideZ = (size_t)T16_DZ_TILES * 2 * X16_PIECE;
     float* dwpart = reinterpret_cast<float*>(ws + wl.dwpart);
     DwReduce red;
     red.n = 0;
-    const char* pl_env = getenv("N3DT_DW_PACE_LEAD");
-    const char* ps_env = getenv("N3DT_DW_PACE_SLEEPS");
-    const int pace_lead = pl_env ? atoi(pl_env) : 0, pace_sleeps = ps_env ? atoi(ps_env) : 12;
     auto args = [&](int a_tile0, int nA, int b_tile0, int nB, float* out, long ld, int rows, int cols, float* rowsum, long rs_stride) {
         DwArgs a;
         a.A = dzT; a.strideA = strideZ; a.a_tile0 = a_tile0; a.nA = nA;
@@ -1388,7 +1224,6 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
         a.out = out; a.ld = ld; a.rows_valid = rows; a.cols_valid = cols;
         a.part = dwpart + (size_t)red.n * DW_XCDS * 384 * 384;
         a.pace = reinterpret_cast<unsigned*>(ws + wl.pace) + (size_t)red.n * DW_PACE_SLOTS;
-        a.pace_lead = pace_lead; a.pace_sleeps = pace_sleeps;
         red.part[red.n] = a.part; red.out[red.n] = out; red.ld[red.n] = ld; red.rows[red.n] = rows; red.cols[red.n] = cols;
         red.perm[red.n] = 0;
         ++red.n;
@@ -1412,13 +1247,13 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
             else
                 hid[n++] = args(zl(l), 12, xh(l - 1), 12, gp->weight[l], 384, 384, 384, dfold + n3dt_bias_offset(l), N3DT_FOLD_STRIDE);
         }
-        launch_dw_multi<4, 2, 3, 3>(g, hid, n, s);
+        launch_dw_multi<4, 2, 3, 3, 2>(g, hid, n, s);
     }
     // the PE columns of the skip layer and layer 0 (two products of one shape)
     {
         DwArgs pe[2] = {args(zl(5), 12, 0, 2, gp->weight[5], in5, 384, N3DT_PE_DIM, nullptr, 0),
                         args(zl(0), 12, 0, 2, gp->weight[0], in0, 384, N3DT_PE_DIM, dfold + n3dt_bias_offset(0), N3DT_FOLD_STRIDE)};
-        launch_dw_multi<4, 2, 3, 1>(g, pe, 2, s);
+        launch_dw_multi<4, 2, 3, 1, 1>(g, pe, 2, s);
     }
     hipLaunchKernelGGL(dw_reduce_kernel, dim3(72, red.n), dim3(256), 0, s, red);
     n3dt_prof_span_end(span_dw, s);
@@ -1453,18 +1288,11 @@ template <int WO, int WI, int TO, int TI>
 static void launch_dw_rm(DwArgs a, long blocks, hipStream_t s) {
     constexpr int NA = WO * TO, NBT = WI * TI, NPP = (2 * (NA + NBT) + 7) / 8 * 8;
     const int gy = ((a.nA + NA - 1) / NA) * ((a.nB + NBT - 1) / NBT);
-    long spf = (256 + gy - 1) / gy;  // about one workgroup per CU in total, at least 8 blocks per slice
-    if (spf > blocks / 8) spf = blocks / 8;
-    if (spf < 1) spf = 1;
-    a.blocks_per_frame = (int)blocks;
-    a.slices_per_frame = (int)spf;
-    a.frames = 1;
-    a.gy = gy;
-    const int slices8 = ((int)spf + 7) / 8 * 8;
+    const int grid = dw_plan_slices(a, (int)blocks, 1, gy);
     const size_t lds_bytes = (size_t)DW_NBUF(NPP) * NPP * X16_PIECE;
     auto kern = dw_x16_kernel<WO, WI, TO, TI, true>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(slices8 * gy), dim3(512), lds_bytes, s, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, s, a);
 }
 // zero every product's partial buffers (one memset) / launch product `index` / reduce them all into their outputs (one launch)
 extern "C" void n3dt_launch_dw_rowmajor_zero(const N3dtDwRm* e, int n, float* part, hipStream_t s) {
@@ -1478,7 +1306,7 @@ extern "C" void n3dt_launch_dw_rowmajor_one(const N3dtDwRm* e, int index, float*
     a.out = q.out; a.ld = q.ld_out; a.rows_valid = q.rows; a.cols_valid = q.cols;
     a.part = part + n3dt_dw_rowmajor_part_bytes(e, index) / sizeof(float);
     a.rowsum = q.rowsum; a.rs_stride = 0;
-    a.pace = nullptr; a.pace_lead = 0; a.pace_sleeps = 0;
+    a.pace = nullptr;
     a.rowmajor = 1; a.ldA = q.ldA; a.ldB = q.ldB;
     a.a_plane_tiles = q.a_planes > 1 ? (q.rows / q.a_planes) / 32 : 0;
     a.a_plane_bytes = q.a_plane_elems * 2;
