@@ -265,6 +265,20 @@ int n3dt_render_bwd(const N3dtGeom* g, int precision, const N3dtMlpParams* p, co
                     const float* xy, const float* R, const float* T, const float* Kinv, const float* t_rand,
                     float* d_R, float* d_T,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* n3dt_render_bwd_cam: n3dt_render_bwd plus the gradients of the other two inputs of ray generation (n3dt_render_bwd is this
+ * call with both NULL).  With c = Kinv [x, y, 1] and gc = R^T dL/d(R c) per ray:
+ *   d_Kinv [B,3,3] (nullable) is ACCUMULATED into (the caller zeroes it): d_Kinv[b][i][j] += sum over rays of gc[i] [x, y, 1][j];
+ *   d_xy [B,2,N_r] (nullable, contiguous whatever the strides of xy) is overwritten: d_xy[b][k][ray] = sum_i gc[i] Kinv[b][i][k].
+ * Either one needs xy, R, T, Kinv like d_R / d_T; each of the four camera gradients may be NULL on its own.  With include_vd the
+ * share that reaches Kinv and xy through ray_bias is the caller's (d_ray_bias), as it is for R. */
+int n3dt_render_bwd_cam(const N3dtGeom* g, int precision, const N3dtMlpParams* p, const N3dtMlpGrads* grads,
+                        const float* shape, const float* appea, const float* audio, const float* bg_featmap,
+                        const float* d_merge_feat, const float* d_fg_feat, const float* d_bg_alpha,
+                        const void* saved, size_t saved_bytes,
+                        float* d_bg_featmap, float* d_shape, float* d_appea, float* d_audio, float* d_ray_bias,
+                        const float* xy, const float* R, const float* T, const float* Kinv, const float* t_rand,
+                        float* d_R, float* d_T, float* d_Kinv, float* d_xy,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Neural renderer with saved activations, and its backward (differentiates NetWorks/neural_renderer.py:72-91,
  * NetWorks/PixelShuffleUpsample.py:36-45).  d_featmap [nb,fs,fs,C] is overwritten; parameter gradients accumulate. */

@@ -48,8 +48,8 @@ void n3dt_launch_train_fwd(const N3dtGeom*, const N3dtMlpParams*, const float*, 
                            float*, const float* /*ray_bias*/, hipStream_t);
 void n3dt_launch_train_bwd(const N3dtGeom*, const N3dtMlpParams*, const N3dtMlpGrads*, const float*, const float*, const float*,
                            const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
-                           const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float* /*d_ray_bias*/,
-                           hipStream_t);
+                           const float*, const float*, const float*, const float*, const float*, float*, float*, float* /*d_Kinv*/,
+                           float* /*d_xy*/, float*, float* /*d_ray_bias*/, hipStream_t);
 size_t n3dt_train16_saved_bytes(const N3dtGeom*);
 size_t n3dt_train16_ws_bytes(const N3dtGeom*);
 void n3dt_launch_train16_fwd(const N3dtGeom*, const N3dtMlpParams*, const void*, const float*, const float*, const float*, const float*,
@@ -57,8 +57,8 @@ void n3dt_launch_train16_fwd(const N3dtGeom*, const N3dtMlpParams*, const void*,
                              float*, void*, void*, const float* /*ray_bias*/, hipStream_t);
 void n3dt_launch_train16_bwd(const N3dtGeom*, const N3dtMlpParams*, const N3dtMlpGrads*, const float*, const float*, const float*,
                              const float*, const float*, const float*, const float*, const void*, float*, float*, float*, float*,
-                             const float*, const float*, const float*, const float*, const float*, float*, float*, void*, float* /*d_ray_bias*/,
-                             hipStream_t);
+                             const float*, const float*, const float*, const float*, const float*, float*, float*, float* /*d_Kinv*/,
+                             float* /*d_xy*/, void*, float* /*d_ray_bias*/, hipStream_t);
 void n3dt_launch_img_to_uint8(int, int, const float*, unsigned char*, hipStream_t);
 void n3dt_launch_loss_fwd(int, int, const float*, const float*, const float*, const float*, float, float*, float*, hipStream_t);
 void n3dt_launch_loss_bwd(int, int, const float*, const float*, const float*, const float*, float, const float*, const float*, const float*, float*,
@@ -619,37 +619,50 @@ extern "C" int n3dt_render_train_fwd(const N3dtGeom* g, int precision, const voi
     return check_hip("n3dt_render_train_fwd");
 }
 
+extern "C" int n3dt_render_bwd_cam(const N3dtGeom* g, int precision, const N3dtMlpParams* p, const N3dtMlpGrads* grads, const float* shape,
+                                   const float* appea, const float* audio, const float* bg_featmap, const float* d_merge_feat,
+                                   const float* d_fg_feat, const float* d_bg_alpha, const void* saved, size_t saved_bytes,
+                                   float* d_bg_featmap, float* d_shape, float* d_appea, float* d_audio, float* d_ray_bias, const float* xy,
+                                   const float* R, const float* T, const float* Kinv, const float* t_rand, float* d_R, float* d_T,
+                                   float* d_Kinv, float* d_xy, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_train_geom(g);
+    if (rc) return rc;
+    if ((rc = check_ray_bias(g, d_ray_bias, "n3dt_render_bwd_cam")) != N3DT_OK) return rc;
+    if (precision != N3DT_F32 && precision != N3DT_BF16) return fail(N3DT_EINVAL, "training precision must be N3DT_F32 or N3DT_BF16");
+    if (!p || !shape || !appea || !saved || !workspace) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: NULL argument");
+    if (!d_merge_feat && !d_fg_feat && !d_bg_alpha) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: no incoming gradient");
+    if (d_merge_feat && !bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: d_merge_feat needs bg_featmap");
+    if (g->audio_dim > 0 && !audio) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: audio is NULL but audio_dim > 0");
+    // grads == NULL: the network is frozen (single-image fitting) -- no parameter gradient is computed, only d codes / d cameras
+    if (grads)
+        for (int l = 0; l < N3DT_MLP_LAYERS; ++l)
+            if (!grads->weight[l] || !grads->bias[l]) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: NULL gradient pointer");
+    if (!grads && d_bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: grads == NULL (frozen network) but d_bg_featmap given");
+    if (saved_bytes < n3dt_render_train_saved_bytes(g)) return fail(N3DT_EWORKSPACE, "n3dt_render_bwd_cam: saved buffer too small");
+    if (workspace_bytes < n3dt_render_train_workspace_bytes(g)) return fail(N3DT_EWORKSPACE, "n3dt_render_bwd_cam: workspace too small");
+    if ((d_R || d_T || d_Kinv || d_xy) && (!xy || !R || !T || !Kinv))
+        return fail(N3DT_EINVAL, "n3dt_render_bwd_cam: camera gradients need xy, R, T, Kinv");
+    if (precision == N3DT_BF16) {
+        n3dt_launch_train16_bwd(g, p, grads, shape, appea, audio, bg_featmap, d_merge_feat, d_fg_feat, d_bg_alpha, saved, d_bg_featmap,
+                                d_shape, d_appea, d_audio, xy, R, T, Kinv, t_rand, d_R, d_T, d_Kinv, d_xy, workspace, d_ray_bias, (hipStream_t)stream);
+        return check_hip("n3dt_render_bwd_cam");
+    }
+    n3dt_launch_train_bwd(g, p, grads, shape, appea, audio, bg_featmap, d_merge_feat, d_fg_feat, d_bg_alpha, (const float*)saved,
+                          d_bg_featmap, d_shape, d_appea, d_audio, xy, R, T, Kinv, t_rand, d_R, d_T, d_Kinv, d_xy, (float*)workspace, d_ray_bias,
+                          (hipStream_t)stream);
+    return check_hip("n3dt_render_bwd_cam");
+}
+
+// the entry point of ABI 5 as it was: no gradient to the intrinsics or the ray coordinates
 extern "C" int n3dt_render_bwd(const N3dtGeom* g, int precision, const N3dtMlpParams* p, const N3dtMlpGrads* grads, const float* shape,
                                const float* appea, const float* audio, const float* bg_featmap, const float* d_merge_feat,
                                const float* d_fg_feat, const float* d_bg_alpha, const void* saved, size_t saved_bytes,
                                float* d_bg_featmap, float* d_shape, float* d_appea, float* d_audio, float* d_ray_bias, const float* xy,
                                const float* R, const float* T, const float* Kinv, const float* t_rand, float* d_R, float* d_T, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    int rc = check_train_geom(g);
-    if (rc) return rc;
-    if ((rc = check_ray_bias(g, d_ray_bias, "n3dt_render_bwd")) != N3DT_OK) return rc;
-    if (precision != N3DT_F32 && precision != N3DT_BF16) return fail(N3DT_EINVAL, "training precision must be N3DT_F32 or N3DT_BF16");
-    if (!p || !shape || !appea || !saved || !workspace) return fail(N3DT_EINVAL, "n3dt_render_bwd: NULL argument");
-    if (!d_merge_feat && !d_fg_feat && !d_bg_alpha) return fail(N3DT_EINVAL, "n3dt_render_bwd: no incoming gradient");
-    if (d_merge_feat && !bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_bwd: d_merge_feat needs bg_featmap");
-    if (g->audio_dim > 0 && !audio) return fail(N3DT_EINVAL, "n3dt_render_bwd: audio is NULL but audio_dim > 0");
-    // grads == NULL: the network is frozen (single-image fitting) -- no parameter gradient is computed, only d codes / d cameras
-    if (grads)
-        for (int l = 0; l < N3DT_MLP_LAYERS; ++l)
-            if (!grads->weight[l] || !grads->bias[l]) return fail(N3DT_EINVAL, "n3dt_render_bwd: NULL gradient pointer");
-    if (!grads && d_bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_bwd: grads == NULL (frozen network) but d_bg_featmap given");
-    if (saved_bytes < n3dt_render_train_saved_bytes(g)) return fail(N3DT_EWORKSPACE, "n3dt_render_bwd: saved buffer too small");
-    if (workspace_bytes < n3dt_render_train_workspace_bytes(g)) return fail(N3DT_EWORKSPACE, "n3dt_render_bwd: workspace too small");
-    if ((d_R || d_T) && (!xy || !R || !T || !Kinv)) return fail(N3DT_EINVAL, "n3dt_render_bwd: camera gradients need xy, R, T, Kinv");
-    if (precision == N3DT_BF16) {
-        n3dt_launch_train16_bwd(g, p, grads, shape, appea, audio, bg_featmap, d_merge_feat, d_fg_feat, d_bg_alpha, saved, d_bg_featmap,
-                                d_shape, d_appea, d_audio, xy, R, T, Kinv, t_rand, d_R, d_T, workspace, d_ray_bias, (hipStream_t)stream);
-        return check_hip("n3dt_render_bwd");
-    }
-    n3dt_launch_train_bwd(g, p, grads, shape, appea, audio, bg_featmap, d_merge_feat, d_fg_feat, d_bg_alpha, (const float*)saved,
-                          d_bg_featmap, d_shape, d_appea, d_audio, xy, R, T, Kinv, t_rand, d_R, d_T, (float*)workspace, d_ray_bias,
-                          (hipStream_t)stream);
-    return check_hip("n3dt_render_bwd");
+    return n3dt_render_bwd_cam(g, precision, p, grads, shape, appea, audio, bg_featmap, d_merge_feat, d_fg_feat, d_bg_alpha, saved, saved_bytes,
+                               d_bg_featmap, d_shape, d_appea, d_audio, d_ray_bias, xy, R, T, Kinv, t_rand, d_R, d_T, nullptr, nullptr,
+                               workspace, workspace_bytes, stream);
 }
 
 static int check_nr(const N3dtGeom* g, int nb) {

@@ -345,17 +345,21 @@ static inline int n3dt_cam_rays_per_block(int n_rays, int batch) {
 //   PE rows: [p, sin(2^k p), cos(2^k p)]  ->  dp = dPE_p + sum_k 2^k (cos * dPE_sin - sin * dPE_cos)
 // every sample edge moves 1:1 with T_z (utils.py:125-126,142 and the convex jitter of :73-78), so dist does not
 // depend on T and the edge term of the points is dp . (d l).
+template <bool KX>
 __global__ void train_camera_bwd_kernel(N3dtGeom g, const float* __restrict__ xy, const float* __restrict__ R,
                                         const float* __restrict__ T, const float* __restrict__ Kinv,
                                         const float* __restrict__ t_rand, const float* __restrict__ cat5,
                                         const float* __restrict__ dpe, const float* __restrict__ dxr, float* __restrict__ d_R,
-                                        float* __restrict__ d_T, const int cam_rays) {
+                                        float* __restrict__ d_T, float* __restrict__ d_Kinv, float* __restrict__ d_xy,
+                                        const int cam_rays) {
     // block = cam_rays (<= CAM_RAYS) consecutive rays of ONE frame (blockIdx.y), 4 waves taking rays in turn; the 12 results are summed
-    // in registers and LDS and leave as 12 atomics per block (one block per 4 rays meant 2 048 atomics per address)
-    __shared__ float cam_red[4][12];
+    // in registers and LDS and leave as 12 atomics per block (one block per 4 rays meant 2 048 atomics per address).
+    // KX (d_Kinv and / or d_xy wanted): nine more sums for d_Kinv leave the same way, d_xy is one store per ray
+    __shared__ float cam_red[4][21];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y, Ns = g.n_samples;
     float sum_R[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sum_T[3] = {0.f, 0.f, 0.f};
+    float sum_K[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int ray_end = min(g.n_rays, (int)(blockIdx.x + 1) * cam_rays);
     for (int ray = blockIdx.x * cam_rays + wave; ray < ray_end; ray += 4) {
     const long rayg = (long)b * g.n_rays + ray;
@@ -419,11 +423,31 @@ __global__ void train_camera_bwd_kernel(N3dtGeom g, const float* __restrict__ xy
         const float gl = g_l + g_dl[0] * dh[0] + g_dl[1] * dh[1] + g_dl[2] * dh[2];
         float g_dh[3] = {g_dl[0] * l, g_dl[1] * l, g_dl[2] * l + gl * l * l};
         const float dot = g_dh[0] * dh[0] + g_dh[1] * dh[1] + g_dh[2] * dh[2];
+        [[maybe_unused]] float gwv[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const float gw = (g_dh[i] - dh[i] * dot) / n;
 #pragma unroll
             for (int j = 0; j < 3; ++j) sum_R[i * 3 + j] += gw * c[j];
+            if constexpr (KX) gwv[i] = gw;
+        }
+        if constexpr (KX) {
+            // gradient at c = Kinv [x, y, 1]: gc = R^T gw (gw carries |w|, l and the sample distances already), then
+            // d Kinv[i][j] = gc[i] h[j] with h = [x, y, 1] and d (x, y) = the first two columns of Kinv against gc
+            float gc[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gc[j] = Rb[j] * gwv[0] + Rb[3 + j] * gwv[1] + Rb[6 + j] * gwv[2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                sum_K[i * 3 + 0] += gc[i] * x;
+                sum_K[i * 3 + 1] += gc[i] * y;
+                sum_K[i * 3 + 2] += gc[i];
+            }
+            if (d_xy && lane == 0) {
+                float* o = d_xy + (size_t)b * 2 * g.n_rays + ray;
+                o[0] = gc[0] * Kb[0] + gc[1] * Kb[3] + gc[2] * Kb[6];
+                o[g.n_rays] = gc[0] * Kb[1] + gc[1] * Kb[4] + gc[2] * Kb[7];
+            }
         }
         sum_T[0] += g_T[0];
         sum_T[1] += g_T[1];
@@ -435,14 +459,20 @@ __global__ void train_camera_bwd_kernel(N3dtGeom g, const float* __restrict__ xy
         for (int i = 0; i < 9; ++i) cam_red[wave][i] = sum_R[i];
 #pragma unroll
         for (int i = 0; i < 3; ++i) cam_red[wave][9 + i] = sum_T[i];
+        if constexpr (KX) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) cam_red[wave][12 + i] = sum_K[i];
+        }
     }
     __syncthreads();
-    if (threadIdx.x < 12) {
+    if (threadIdx.x < (KX ? 21 : 12)) {
         const float v = (cam_red[0][threadIdx.x] + cam_red[1][threadIdx.x]) + (cam_red[2][threadIdx.x] + cam_red[3][threadIdx.x]);
         if (threadIdx.x < 9) {
             if (d_R) atomicAdd(&d_R[b * 9 + threadIdx.x], v);
-        } else if (d_T) {
-            atomicAdd(&d_T[b * 3 + threadIdx.x - 9], v);
+        } else if (threadIdx.x < 12) {
+            if (d_T) atomicAdd(&d_T[b * 3 + threadIdx.x - 9], v);
+        } else if (d_Kinv) {
+            atomicAdd(&d_Kinv[b * 9 + threadIdx.x - 12], v);
         }
     }
 }
@@ -683,8 +713,8 @@ extern "C" void n3dt_launch_train_bwd(const N3dtGeom* g, const N3dtMlpParams* p,
                                       const float* appea, const float* audio, const float* bg_featmap, const float* d_merge,
                                       const float* d_fg, const float* d_ba, const float* saved, float* d_bg_featmap, float* d_shape,
                                       float* d_appea, float* d_audio, const float* xy, const float* Rm, const float* Tv,
-                                      const float* Kinv, const float* t_rand, float* d_R, float* d_T, float* ws, float* d_ray_bias,
-                                      hipStream_t s) {
+                                      const float* Kinv, const float* t_rand, float* d_R, float* d_T, float* d_Kinv, float* d_xy,
+                                      float* ws, float* d_ray_bias, hipStream_t s) {
     const TrainSaved sv = saved_layout(g);
     const TrainWs wl = ws_layout(g);
     const int P = g->batch * g->n_rays * g->n_samples, ppf = g->n_rays * g->n_samples;
@@ -774,7 +804,7 @@ extern "C" void n3dt_launch_train_bwd(const N3dtGeom* g, const N3dtMlpParams* p,
         } else if (gp) {
             launch_colsum(dcur, 384L, P, 1, 384, gp->bias[l], 0L, s);
         }
-        const bool want_cam = d_R || d_T;
+        const bool want_cam = d_R || d_T || d_Kinv || d_xy;
         // DIAGNOSTIC (N3DT_DIAG_PE_BF16, bit 0: round dZ, bit 1: round the weights): the two d-PE products of THIS exact path with
         // operands rounded to bf16 -- what the fused bf16 path's last product does to the camera gradients, in isolation from
         // the rounding its dZ has already collected upstream (tools/cam_error_probe.py)
@@ -809,8 +839,9 @@ extern "C" void n3dt_launch_train_bwd(const N3dtGeom* g, const N3dtMlpParams* p,
             if (d_R) (void)hipMemsetAsync(d_R, 0, sizeof(float) * 9 * B, s);
             if (d_T) (void)hipMemsetAsync(d_T, 0, sizeof(float) * 3 * B, s);
             const int cr = n3dt_cam_rays_per_block(g->n_rays, B);
-            hipLaunchKernelGGL(train_camera_bwd_kernel, dim3((g->n_rays + cr - 1) / cr, B), dim3(256), 0, s, *g, xy, Rm, Tv, Kinv, t_rand, cat5,
-                               ws + wl.dpe, dxr, d_R, d_T, cr);
+            auto kern = (d_Kinv || d_xy) ? train_camera_bwd_kernel<true> : train_camera_bwd_kernel<false>;
+            hipLaunchKernelGGL(kern, dim3((g->n_rays + cr - 1) / cr, B), dim3(256), 0, s, *g, xy, Rm, Tv, Kinv, t_rand, cat5,
+                               ws + wl.dpe, dxr, d_R, d_T, d_Kinv, d_xy, cr);
         }
         if (l == 0) break;
         // input gradient: dH_{l-1} = (dH_l W_l) * relu'(H_{l-1})

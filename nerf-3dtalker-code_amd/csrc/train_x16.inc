@@ -402,17 +402,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void nerf_bwd_x16_kernel(N3dtGeom g,
 
 // Camera backward of the fused path: the algebra of train_camera_bwd_kernel (above), with the encoder's sin / cos
 // recomputed from the sample position (accurate sinf / cosf) and d PE = dpe5 + dpe0 in block-padded point order.
+template <bool KX>
 __global__ void train16_camera_bwd_kernel(N3dtGeom g, int bpr, const float* __restrict__ xy, const float* __restrict__ R,
                                           const float* __restrict__ T, const float* __restrict__ Kinv,
                                           const float* __restrict__ t_rand, const float* __restrict__ dpe5,
                                           const float* __restrict__ dpe0, const float* __restrict__ ddist, float* __restrict__ d_R,
-                                          float* __restrict__ d_T, const int cam_rays) {
+                                          float* __restrict__ d_T, float* __restrict__ d_Kinv, float* __restrict__ d_xy,
+                                          const int cam_rays) {
     // block = cam_rays (<= CAM_RAYS, n3dt_cam_rays_per_block) consecutive rays of ONE frame (blockIdx.y), 4 waves taking rays in turn;
-    // the 12 results are summed in registers and LDS and leave as 12 atomics per block
-    __shared__ float cam_red[4][12];
+    // the 12 results are summed in registers and LDS and leave as 12 atomics per block (KX: 21, and d_xy per ray, as in the fp32 kernel)
+    __shared__ float cam_red[4][21];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y, Ns = g.n_samples;
     float sum_R[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sum_T[3] = {0.f, 0.f, 0.f};
+    float sum_K[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int ray_end = min(g.n_rays, (int)(blockIdx.x + 1) * cam_rays);
     for (int ray = blockIdx.x * cam_rays + wave; ray < ray_end; ray += 4) {
     const long rayg = (long)b * g.n_rays + ray;
@@ -478,11 +481,31 @@ __global__ void train16_camera_bwd_kernel(N3dtGeom g, int bpr, const float* __re
         const float gl = g_l + g_dl[0] * dh[0] + g_dl[1] * dh[1] + g_dl[2] * dh[2];
         float g_dh[3] = {g_dl[0] * l, g_dl[1] * l, g_dl[2] * l + gl * l * l};
         const float dot = g_dh[0] * dh[0] + g_dh[1] * dh[1] + g_dh[2] * dh[2];
+        [[maybe_unused]] float gwv[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const float gw = (g_dh[i] - dh[i] * dot) / n;
 #pragma unroll
             for (int j = 0; j < 3; ++j) sum_R[i * 3 + j] += gw * cc[j];
+            if constexpr (KX) gwv[i] = gw;
+        }
+        if constexpr (KX) {
+            // gradient at c = Kinv [x, y, 1]: gc = R^T gw (gw carries |w|, l and the sample distances already), then
+            // d Kinv[i][j] = gc[i] h[j] with h = [x, y, 1] and d (x, y) = the first two columns of Kinv against gc
+            float gc[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gc[j] = Rb[j] * gwv[0] + Rb[3 + j] * gwv[1] + Rb[6 + j] * gwv[2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                sum_K[i * 3 + 0] += gc[i] * x;
+                sum_K[i * 3 + 1] += gc[i] * y;
+                sum_K[i * 3 + 2] += gc[i];
+            }
+            if (d_xy && lane == 0) {
+                float* o = d_xy + (size_t)b * 2 * g.n_rays + ray;
+                o[0] = gc[0] * Kb[0] + gc[1] * Kb[3] + gc[2] * Kb[6];
+                o[g.n_rays] = gc[0] * Kb[1] + gc[1] * Kb[4] + gc[2] * Kb[7];
+            }
         }
         sum_T[0] += g_T[0];
         sum_T[1] += g_T[1];
@@ -494,14 +517,20 @@ __global__ void train16_camera_bwd_kernel(N3dtGeom g, int bpr, const float* __re
         for (int i = 0; i < 9; ++i) cam_red[wave][i] = sum_R[i];
 #pragma unroll
         for (int i = 0; i < 3; ++i) cam_red[wave][9 + i] = sum_T[i];
+        if constexpr (KX) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) cam_red[wave][12 + i] = sum_K[i];
+        }
     }
     __syncthreads();
-    if (threadIdx.x < 12) {
+    if (threadIdx.x < (KX ? 21 : 12)) {
         const float v = (cam_red[0][threadIdx.x] + cam_red[1][threadIdx.x]) + (cam_red[2][threadIdx.x] + cam_red[3][threadIdx.x]);
         if (threadIdx.x < 9) {
             if (d_R) atomicAdd(&d_R[b * 9 + threadIdx.x], v);
-        } else if (d_T) {
-            atomicAdd(&d_T[b * 3 + threadIdx.x - 9], v);
+        } else if (threadIdx.x < 12) {
+            if (d_T) atomicAdd(&d_T[b * 3 + threadIdx.x - 9], v);
+        } else if (d_Kinv) {
+            atomicAdd(&d_Kinv[b * 9 + threadIdx.x - 12], v);
         }
     }
 }
@@ -1126,8 +1155,8 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
                                         const float* appea, const float* audio, const float* bg_featmap, const float* d_merge,
                                         const float* d_fg, const float* d_ba, const void* saved, float* d_bg_featmap, float* d_shape,
                                         float* d_appea, float* d_audio, const float* xy, const float* Rm, const float* Tv,
-                                        const float* Kinv, const float* t_rand, float* d_R, float* d_T, void* wsv, float* d_ray_bias,
-                                        hipStream_t s) {
+                                        const float* Kinv, const float* t_rand, float* d_R, float* d_T, float* d_Kinv, float* d_xy,
+                                        void* wsv, float* d_ray_bias, hipStream_t s) {
     const Train16Saved sv = saved16_layout(g);
     const Train16Ws wl = ws16_layout(g);
     const unsigned char* sb = reinterpret_cast<const unsigned char*>(saved);
@@ -1144,7 +1173,7 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
     unsigned char* packT = ws + wl.packT;
     unsigned char* dzT = ws + wl.dzT;
     float* dsig = reinterpret_cast<float*>(ws + wl.dsig);
-    const bool cam = d_R || d_T;
+    const bool cam = d_R || d_T || d_Kinv || d_xy;
     float* ddist = cam ? reinterpret_cast<float*>(ws + wl.ddist) : nullptr;
     float* dpe5 = reinterpret_cast<float*>(ws + wl.dpe5);
     float* dpe0 = reinterpret_cast<float*>(ws + wl.dpe0);
@@ -1199,8 +1228,9 @@ extern "C" void n3dt_launch_train16_bwd(const N3dtGeom* g, const N3dtMlpParams* 
         if (d_R) (void)hipMemsetAsync(d_R, 0, sizeof(float) * 9 * B, s);
         if (d_T) (void)hipMemsetAsync(d_T, 0, sizeof(float) * 3 * B, s);
         const int cr = n3dt_cam_rays_per_block(g->n_rays, B);
-        hipLaunchKernelGGL(train16_camera_bwd_kernel, dim3((g->n_rays + cr - 1) / cr, B), dim3(256), 0, s, *g, bpr, xy, Rm, Tv, Kinv, t_rand, dpe5,
-                           dpe0, ddist, d_R, d_T, cr);
+        auto ckern = (d_Kinv || d_xy) ? train16_camera_bwd_kernel<true> : train16_camera_bwd_kernel<false>;
+        hipLaunchKernelGGL(ckern, dim3((g->n_rays + cr - 1) / cr, B), dim3(256), 0, s, *g, bpr, xy, Rm, Tv, Kinv, t_rand, dpe5,
+                           dpe0, ddist, d_R, d_T, d_Kinv, d_xy, cr);
     }
     if (!gp) {
         // Frozen network (single-image fitting, FittingSingleImage_new.py:826-859: only codes and cameras are optimised): no weight

@@ -63,6 +63,7 @@ EXPORTS = [
     "n3dt_render_workspace_bytes", "n3dt_render_fwd", "n3dt_neural_render_workspace_bytes",
     "n3dt_neural_render_fwd", "n3dt_chw_to_hwc", "n3dt_prof_enable", "n3dt_prof_collect",
     "n3dt_render_train_saved_bytes", "n3dt_render_train_workspace_bytes", "n3dt_render_train_fwd", "n3dt_render_bwd",
+    "n3dt_render_bwd_cam",
     "n3dt_neural_render_train_saved_bytes", "n3dt_neural_render_train_workspace_bytes",
     "n3dt_neural_render_train_fwd", "n3dt_neural_render_bwd", "n3dt_loss_fwd", "n3dt_loss_bwd", "n3dt_fine_sample",
     "n3dt_img_to_uint8", "n3dt_sample_points", "n3dt_embed", "n3dt_mlp_points_workspace_bytes", "n3dt_mlp_points", "n3dt_composite",
@@ -125,6 +126,8 @@ def lib():
     L.n3dt_render_train_fwd.argtypes = [gp, ci, vp, mp] + [vp] * 14 + [vp, sz, vp, sz, vp]
     L.n3dt_render_bwd.restype = ci
     L.n3dt_render_bwd.argtypes = [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 12 + [vp, sz, vp]
+    L.n3dt_render_bwd_cam.restype = ci  # n3dt_render_bwd + d_Kinv, d_xy behind d_T
+    L.n3dt_render_bwd_cam.argtypes = [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 14 + [vp, sz, vp]
     L.n3dt_neural_render_train_saved_bytes.restype = sz
     L.n3dt_neural_render_train_saved_bytes.argtypes = [gp, ci]
     L.n3dt_neural_render_train_workspace_bytes.restype = sz

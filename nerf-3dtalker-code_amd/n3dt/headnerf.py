@@ -233,9 +233,10 @@ def _zeros_like_many(tensors):
 
 
 class _RenderFn(torch.autograd.Function):
-    """a1..a7 with saved activations (n3dt_render_train_fwd) and its backward (n3dt_render_bwd).
-    Inputs after `net`/`geom`: xy, Kinv, t_rand (no grad), then R, T, shape, appea, audio, bg_featmap, ray_bias and the
-    24 MLP parameter tensors (all differentiable; R/T gradients are computed only when they require grad).
+    """a1..a7 with saved activations (n3dt_render_train_fwd) and its backward (n3dt_render_bwd_cam).
+    Inputs after `net`/`geom`: xy, Kinv, then t_rand (no grad), then R, T, shape, appea, audio, bg_featmap, ray_bias and the
+    24 MLP parameter tensors (all differentiable; each of the four camera gradients -- xy, Kinv, R, T -- is computed only when
+    its input requires grad).  xy may be a strided view (an expand()ed grid): its gradient comes back as a dense [B, 2, N_r].
     ray_bias [B, N_r, 192] (include_vd, else None): the per-ray addend of RGB_layer_1's pre-activation; the caller forms it from
     the ray directions with autograd, so its gradient carries on to the 27 view-direction columns and to the cameras."""
 
@@ -244,10 +245,11 @@ class _RenderFn(torch.autograd.Function):
         """merge_out: None, or a _Slot whose `.t` [B, N_r, C] (a slice of the renderer's input batch) receives the merged
         map and becomes the output.  (Handed over inside a plain object, not as a tensor argument: autograd then sees a fresh
         output, not a modified input.)"""
-        ctx.want_cam = R.requires_grad or T.requires_grad
-        ctx.T_shape = T.shape
+        ctx.want_cam = R.requires_grad or T.requires_grad or Kinv.requires_grad or xy.requires_grad
+        ctx.T_shape, ctx.K_shape = T.shape, Kinv.shape
         R = ops._f32c(R)
         T = ops._f32c(T).view(-1, 3)
+        Kinv = ops._f32c(Kinv)
         ws = [t.detach().view(t.shape[0], -1).contiguous() for t in mlp[:12]]
         bs = [t.detach().contiguous() for t in mlp[12:]]
         params = ops.mlp_params(ws, bs)
@@ -274,6 +276,8 @@ class _RenderFn(torch.autograd.Function):
     def backward(ctx, d_merge):
         ws, bs, shape_c, appea_c, audio_c, bg = ctx.keep
         geom = ctx.geom
+        # inputs 3, 4, 6, 7 = xy, Kinv, R, T: ask the library for the gradients autograd will use, no others
+        cam_grads = [n for n, i in (("xy", 3), ("Kinv", 4), ("R", 6), ("T", 7)) if ctx.needs_input_grad[i]] if ctx.cam is not None else None
         # gradient buffers: slices of the module's persistent arena (zeroed by one fill per backward pass, and what a
         # multi-GPU step all-reduces in place) -- or fresh zeroed buffers when the arena cannot be used (see FlatGrads.hand_out)
         vd = geom.vd_dim > 0
@@ -281,12 +285,15 @@ class _RenderFn(torch.autograd.Function):
             # FROZEN network (single-image fitting optimises codes and cameras only, FittingSingleImage_new.py:826-859): no
             # parameter gradient is wanted, so none is computed -- the weight-gradient stage is a quarter of a fitting iteration
             res = ops.render_bwd(geom, ops.mlp_params(ws, bs), None, shape_c, appea_c, audio_c, bg,
-                                 d_merge.contiguous(), ctx.saved, ctx.cam, ctx.prec, frozen=True)
+                                 d_merge.contiguous(), ctx.saved, ctx.cam, ctx.prec, frozen=True, cam_grads=cam_grads)
             _, d_shape, d_appea, d_audio, d_R, d_T = res[:6]
+            d_Kinv, d_xy = res[-2:] if cam_grads is not None else (None, None)
             ctx.saved = None
             if d_T is not None:
                 d_T = d_T.view(ctx.T_shape)
-            return (None, None, None, None, None, None, d_R, d_T, d_shape, d_appea, d_audio, None, res[6] if vd else None,
+            if d_Kinv is not None:
+                d_Kinv = d_Kinv.view(ctx.K_shape)
+            return (None, None, None, d_xy, d_Kinv, None, d_R, d_T, d_shape, d_appea, d_audio, None, res[6] if vd else None,
                     *([None] * len(ctx.mlp_shapes)))
         views = ctx.net._hand_out_grads(ctx.param_objs)
         if views is None:
@@ -295,8 +302,9 @@ class _RenderFn(torch.autograd.Function):
             gws = [v.view(w.shape) for v, w in zip(views[:12], ws)]
             gbs, d_bg_out = views[12:24], views[24].view(geom.feat_nc, geom.n_rays)
         res = ops.render_bwd(geom, ops.mlp_params(ws, bs), ops.mlp_params(gws, gbs), shape_c, appea_c, audio_c, bg, d_merge.contiguous(),
-                             ctx.saved, ctx.cam, ctx.prec, d_bg=d_bg_out)
+                             ctx.saved, ctx.cam, ctx.prec, d_bg=d_bg_out, cam_grads=cam_grads)
         d_bg, d_shape, d_appea, d_audio, d_R, d_T = res[:6]
+        d_Kinv, d_xy = res[-2:] if cam_grads is not None else (None, None)
         d_ray = res[6] if vd else None
         ctx.saved = None
         grads = [g.view(s) for g, s in zip(gws + gbs, ctx.mlp_shapes)]
@@ -307,7 +315,9 @@ class _RenderFn(torch.autograd.Function):
             ctx.net.invalidate_packed()
         if d_T is not None:
             d_T = d_T.view(ctx.T_shape)
-        return (None, None, None, None, None, None, d_R, d_T, d_shape, d_appea, d_audio, d_bg.view(ctx.bg_shape), d_ray, *grads)
+        if d_Kinv is not None:
+            d_Kinv = d_Kinv.view(ctx.K_shape)
+        return (None, None, None, d_xy, d_Kinv, None, d_R, d_T, d_shape, d_appea, d_audio, d_bg.view(ctx.bg_shape), d_ray, *grads)
 
 
 class _Slot:
@@ -665,7 +675,7 @@ class HeadNeRFNet(nn.Module):
 
     def _vd_ray_bias(self, xy, batch_Rmats, batch_inv_inmats, fine=False):
         """include_vd, differentiable: ray_bias [B, N_r, 192] = Embedder_4(ray direction) . RGB_layer_1.weight[:, 384:411]^T with
-        autograd (gradients reach the 27 weight columns and batch_Rmats).  The direction as GenSamplePoints builds it
+        autograd (gradients reach the 27 weight columns, batch_Rmats, batch_inv_inmats and xy).  The direction as GenSamplePoints builds it
         (NetWorks/utils.py:149-153), the encoder's channel order as Embedder (:20-51).  A [B*N_r, 27] x [27, 192] product: plumbing
         next to the sample-point work the kernels do; the inference path uses the HIP kernel (ops.ray_vd_bias)."""
         B, _, n_r = xy.shape
@@ -747,7 +757,8 @@ class HeadNeRFNet(nn.Module):
         fs, C = self.featmap_size, self.featmap_nc
         needs_grad = torch.is_grad_enabled() and (
             any(p.requires_grad for p in self.parameters()) or
-            any(torch.is_tensor(t) and t.requires_grad for t in (audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs)))
+            any(torch.is_tensor(t) and t.requires_grad for t in (audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs,
+                                                                     batch_inv_inmats, batch_xy)))
         if needs_grad:
             return self._forward_train(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand,
                                        for_train=for_train, fine_u=fine_u)
@@ -924,8 +935,10 @@ class HeadNeRFNet(nn.Module):
     def _forward_train(self, batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand,
                        for_train=False, fine_u=None):
         """Differentiable forward: gradients reach every parameter, audiostyle, shape_code, appea_code and (when they require
-        grad) batch_Rmats / batch_Tvecs.  With hier_sampling the fine pass is differentiated too; its sample planes come
-        from the DETACHED coarse weights, as in the reference (NetWorks/utils.py:219), so they are constants of the backward."""
+        grad) batch_Rmats / batch_Tvecs / batch_inv_inmats / batch_xy (the latter also as a broadcast view, xy.expand(B, -1, -1):
+        autograd sums the per-frame result onto the base tensor); batch_uv is not used.  With hier_sampling the fine pass is
+        differentiated too; its sample planes come from the DETACHED coarse weights, as in the reference (NetWorks/utils.py:219),
+        so they are constants of the backward (they depend on neither the intrinsics nor xy)."""
         B, _, n_r = batch_xy.size()
         fs, C = self.featmap_size, self.featmap_nc
         xy = batch_xy if batch_xy.dtype == torch.float32 else batch_xy.float()
@@ -941,15 +954,15 @@ class HeadNeRFNet(nn.Module):
             h, vd = self.mlp_h_channel, self._vd_dim()
             w10 = layers[10].weight
             mlp[10] = torch.cat([w10[:, :h], w10[:, h + vd:]], dim=1)
-            ray_bias = self._vd_ray_bias(xy.detach(), batch_Rmats, batch_inv_inmats)
+            ray_bias = self._vd_ray_bias(xy, batch_Rmats, batch_inv_inmats)
         audio = audiostyle if self.audio_dim > 0 else torch.zeros(B, 0, device=xy.device)
         n_pass = 2 if self.hier_sampling else 1
         nb = B * n_pass
         # the renderer's input batch, allocated per call (it is saved for the backward): the volumetric passes write their merged
         # maps straight into it, the renderer's forward fills the last slot from bg_featmap
         maps = torch.empty(nb + 1, fs, fs, C, dtype=torch.float32, device=xy.device)
-        Kinv = ops._f32c(batch_inv_inmats)
-        merge = _RenderFn.apply(self, geom, _Slot(maps[:B].view(B, n_r, C)), xy.detach(), Kinv, None if t_rand is None else ops._f32c(t_rand),
+        Kinv = batch_inv_inmats  # (handed over as it is: _RenderFn returns its gradient)
+        merge = _RenderFn.apply(self, geom, _Slot(maps[:B].view(B, n_r, C)), xy, Kinv, None if t_rand is None else ops._f32c(t_rand),
                                 batch_Rmats, batch_Tvecs, shape_code, appea_code, audio, self.neural_render.bg_featmap, ray_bias, *mlp)
         merged = [merge]
         if self.hier_sampling:
@@ -965,8 +978,8 @@ class HeadNeRFNet(nn.Module):
             if self.include_vd:
                 fw10 = flayers[10].weight
                 fmlp[10] = torch.cat([fw10[:, :h], fw10[:, h + vd:]], dim=1)
-                fine_ray_bias = self._vd_ray_bias(xy.detach(), batch_Rmats, batch_inv_inmats, fine=True)
-            merged.append(_RenderFn.apply(self, gfine, _Slot(maps[B:nb].view(B, n_r, C)), xy.detach(), Kinv, planes, batch_Rmats, batch_Tvecs,
+                fine_ray_bias = self._vd_ray_bias(xy, batch_Rmats, batch_inv_inmats, fine=True)
+            merged.append(_RenderFn.apply(self, gfine, _Slot(maps[B:nb].view(B, n_r, C)), xy, Kinv, planes, batch_Rmats, batch_Tvecs,
                                           shape_code, appea_code, audio, self.neural_render.bg_featmap, fine_ray_bias, *fmlp))
         flat = []
         for m in self.neural_render._flat_modules():

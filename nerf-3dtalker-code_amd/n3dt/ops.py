@@ -332,11 +332,15 @@ def render_train_fwd(geom, packed, params, xy, R, T, Kinv, shape, appea, audio, 
     return out, saved
 
 
-def render_bwd(geom, params, grads, shape, appea, audio, bg_featmap, d_merge, saved, cam=None, precision=0, d_bg=None, frozen=False):
+def render_bwd(geom, params, grads, shape, appea, audio, bg_featmap, d_merge, saved, cam=None, precision=0, d_bg=None, frozen=False,
+               cam_grads=None):
     """Backward of render_train_fwd.  `grads` (MlpParams struct of zeroed tensors) is accumulated into.
     cam = (xy, R, T, Kinv, t_rand) requests camera gradients.
     Returns (d_bg_featmap [C,Nr], d_shape, d_appea, d_audio, d_R, d_T) -- and, with geom.vd_dim > 0 (include_vd), a seventh
-    entry d_ray_bias [B, N_r, 192]."""
+    entry d_ray_bias [B, N_r, 192].
+    cam_grads: None -- d_R and d_T, through n3dt_render_bwd (the call as it always was).  Else the names among "R", "T", "Kinv",
+    "xy" whose gradient is wanted, through n3dt_render_bwd_cam: the others come back as None, and the tuple ends in two more
+    entries, d_Kinv [B,3,3] and d_xy [B,2,N_r] (contiguous whatever the strides of xy)."""
     dev = d_merge.device
     B, Nr, C = geom.batch, geom.n_rays, geom.feat_nc
     if frozen:  # grads is None: no parameter gradient, no d_bg_featmap
@@ -350,23 +354,33 @@ def render_bwd(geom, params, grads, shape, appea, audio, bg_featmap, d_merge, sa
     d_shape = codes[:B * S_].view(B, S_)
     d_appea = codes[B * S_:B * (S_ + A_)].view(B, A_)
     d_audio = codes[B * (S_ + A_):].view(B, U_) if U_ > 0 else None
-    d_R = d_T = None
+    d_R = d_T = d_Kinv = d_xy = None
     cam_ptrs = [None] * 5
     if cam is not None:
-        d_R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
-        d_T = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        want = ("R", "T") if cam_grads is None else tuple(cam_grads)
+        assert set(want) <= {"R", "T", "Kinv", "xy"}
+        if "R" in want:
+            d_R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+        if "T" in want:
+            d_T = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        if "Kinv" in want:  # the library accumulates into this one
+            d_Kinv = torch.zeros(B, 3, 3, dtype=torch.float32, device=dev)
+        if "xy" in want:
+            d_xy = torch.empty(B, 2, Nr, dtype=torch.float32, device=dev)
         cam_ptrs = [_ptr(t) for t in cam]
     d_ray = torch.empty(B, Nr, 192, dtype=torch.float32, device=dev) if geom.vd_dim > 0 else None
     wbytes = lib().n3dt_render_train_workspace_bytes(ctypes.byref(geom))
     ws = WORKSPACE.get("train", wbytes, dev)
-    check(lib().n3dt_render_bwd(
-        ctypes.byref(geom), precision, ctypes.byref(params), None if grads is None else ctypes.byref(grads), _ptr(shape), _ptr(appea), _ptr(audio),
-        _ptr(bg_featmap),
-        _ptr(d_merge), None, None, _ptr(saved), saved.numel(), _ptr(d_bg), _ptr(d_shape), _ptr(d_appea), _ptr(d_audio), _ptr(d_ray),
-        *cam_ptrs, _ptr(d_R), _ptr(d_T), _ptr(ws), wbytes, _stream()), "n3dt_render_bwd")
-    if d_ray is not None:
-        return d_bg, d_shape, d_appea, d_audio, d_R, d_T, d_ray
-    return d_bg, d_shape, d_appea, d_audio, d_R, d_T
+    head = (ctypes.byref(geom), precision, ctypes.byref(params), None if grads is None else ctypes.byref(grads), _ptr(shape), _ptr(appea),
+            _ptr(audio), _ptr(bg_featmap),
+            _ptr(d_merge), None, None, _ptr(saved), saved.numel(), _ptr(d_bg), _ptr(d_shape), _ptr(d_appea), _ptr(d_audio), _ptr(d_ray),
+            *cam_ptrs, _ptr(d_R), _ptr(d_T))
+    if cam_grads is None:
+        check(lib().n3dt_render_bwd(*head, _ptr(ws), wbytes, _stream()), "n3dt_render_bwd")
+    else:
+        check(lib().n3dt_render_bwd_cam(*head, _ptr(d_Kinv), _ptr(d_xy), _ptr(ws), wbytes, _stream()), "n3dt_render_bwd_cam")
+    res = (d_bg, d_shape, d_appea, d_audio, d_R, d_T) + ((d_ray,) if d_ray is not None else ())
+    return res if cam_grads is None else res + (d_Kinv, d_xy)
 
 
 def neural_render_train_fwd(geom, nb, rparams, featmap, precision=0):
