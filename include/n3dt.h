@@ -369,6 +369,44 @@ int n3dt_a2s_fwd(int T, const N3dtA2sParams* p, const float* mel, const float* m
 int n3dt_a2s_bwd(int T, const N3dtA2sParams* p, const float* g_out, const void* saved, size_t saved_bytes, float* grad_arena,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* ---- FlatAdam: torch.optim.Adam's step (amsgrad = False) for any number of tensors in ONE launch ------------------
+ * The reference ends its step with two torch.optim.Adam steps (talker_trainer.py:722-727, 1063-1067).  The caller lays the
+ * work out once per layout in device memory:
+ *   tensor table  N3dtAdamTensor[n]: the four fp32 pointers of a tensor (any 4-byte alignment), numel, its group and an
+ *                 "active" flag (0: the parameter has no gradient this step -- value and state stay as they are);
+ *   chunk table   N3dtAdamChunk[n_chunks]: (tensor, start element, length); the chunks tile every tensor exactly once and
+ *                 none crosses a tensor;
+ *   group table   N3dtAdamGroup[n_groups <= N3DT_ADAM_MAX_GROUPS]: hyper-parameters as doubles, read from device memory at
+ *                 every launch (a replayed graph follows a copy into it);
+ *   step counter  int32[N3DT_ADAM_COUNTER_INTS], zeroed once by the caller: [0] = steps taken (the kernel uses t = [0] + 1
+ *                 and adds 1 once per launch, after every read), [1] = the kernel's own completion counter.
+ * n3dt_flat_adam_record_bytes(which): sizeof of the tensor (0), chunk (1) and group (2) record, 0 for anything else. */
+#define N3DT_ADAM_MAX_GROUPS 64
+#define N3DT_ADAM_MAX_GRID 1024
+#define N3DT_ADAM_COUNTER_INTS 4
+typedef struct N3dtAdamTensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    int32_t group;
+    int32_t active;
+} N3dtAdamTensor;
+typedef struct N3dtAdamChunk {
+    int64_t start;
+    int32_t tensor;
+    int32_t length;
+} N3dtAdamChunk;
+typedef struct N3dtAdamGroup {
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t maximize;
+    int32_t reserved;
+} N3dtAdamGroup;
+size_t n3dt_flat_adam_record_bytes(int which);
+int n3dt_flat_adam_step(const void* tensor_table, const void* chunk_table, int n_chunks, const void* group_table, int n_groups,
+                        void* step_counter, void* stream);
+
 /* [C, N_r] (NCHW parameter) -> [N_r, C]; used to feed bg_featmap to the renderer */
 int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream);
 

@@ -80,6 +80,7 @@ size_t n3dt_a2s_saved_floats(int);
 size_t n3dt_a2s_ws_floats(int);
 void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* const[3], float*, void*, void*, hipStream_t);
 void n3dt_launch_a2s_bwd(int, const N3dtA2sParams*, const float*, const void*, float*, void*, hipStream_t);
+void n3dt_launch_flat_adam(const void*, const void*, int, const void*, int, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -564,6 +565,21 @@ extern "C" int n3dt_a2s_bwd(int T, const N3dtA2sParams* p, const float* g_out, c
     if ((rc = check_a2s_buf(who, "ws", ws, ws_bytes, n3dt_a2s_ws_floats(T) * sizeof(float)))) return rc;
     n3dt_launch_a2s_bwd(T, p, g_out, saved, grad_arena, ws, (hipStream_t)stream);
     return check_hip(who);
+}
+
+extern "C" size_t n3dt_flat_adam_record_bytes(int which) {
+    return which == 0 ? sizeof(N3dtAdamTensor) : which == 1 ? sizeof(N3dtAdamChunk) : which == 2 ? sizeof(N3dtAdamGroup) : 0;
+}
+
+extern "C" int n3dt_flat_adam_step(const void* tensor_table, const void* chunk_table, int n_chunks, const void* group_table,
+                                   int n_groups, void* step_counter, void* stream) {
+    if (!tensor_table || !chunk_table || !group_table || !step_counter) return fail(N3DT_EINVAL, "n3dt_flat_adam_step: NULL table");
+    if (n_chunks <= 0) return fail(N3DT_EINVAL, "n3dt_flat_adam_step: n_chunks must be >= 1");
+    if (n_groups < 1 || n_groups > N3DT_ADAM_MAX_GROUPS) return fail(N3DT_EINVAL, "n3dt_flat_adam_step: n_groups outside 1..64");
+    if ((((size_t)tensor_table) | ((size_t)chunk_table) | ((size_t)group_table)) & 7 || ((size_t)step_counter) & 3)
+        return fail(N3DT_EINVAL, "n3dt_flat_adam_step: tables must be 8-byte aligned, the step counter 4-byte aligned");
+    n3dt_launch_flat_adam(tensor_table, chunk_table, n_chunks, group_table, n_groups, step_counter, (hipStream_t)stream);
+    return check_hip("n3dt_flat_adam_step");
 }
 
 extern "C" int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream) {

@@ -2,4 +2,5 @@
 from .options import BaseOptions  # noqa: F401
 from .headnerf import HeadNeRFNet, NeuralRenderer, MLPforNeRF  # noqa: F401
 from .audio import Audio2style  # noqa: F401
-from . import checkpoint, render_utils, parallel, train, fitting, audio  # noqa: F401,E402
+from .optim import FlatAdam  # noqa: F401
+from . import checkpoint, render_utils, parallel, train, fitting, audio, optim  # noqa: F401,E402

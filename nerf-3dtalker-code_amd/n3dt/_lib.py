@@ -41,6 +41,23 @@ class A2sParams(ctypes.Structure):
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
 
 
+class AdamTensor(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("group", ctypes.c_int32), ("active", ctypes.c_int32)]
+
+
+class AdamChunk(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_int64), ("tensor", ctypes.c_int32), ("length", ctypes.c_int32)]
+
+
+class AdamGroup(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("maximize", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+ADAM_MAX_GROUPS = 64
+ADAM_COUNTER_INTS = 4
+
 A2S_MAX_T = 256
 A2S_GRAD_FLOATS = 20726784
 
@@ -71,6 +88,7 @@ EXPORTS = [
     "n3dt_neural_render_pack", "n3dt_neural_render_fwd_reuse", "n3dt_stage_inputs", "n3dt_graph_begin", "n3dt_graph_end", "n3dt_graph_launch", "n3dt_graph_destroy",
     "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd",
     "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
+    "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
 ]
 
 STAGE_MAX = 12
@@ -192,8 +210,15 @@ def lib():
     L.n3dt_a2s_fwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
     L.n3dt_a2s_bwd.restype = ci
     L.n3dt_a2s_bwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, sz, vp, vp, sz, vp]
+    L.n3dt_flat_adam_record_bytes.restype = sz
+    L.n3dt_flat_adam_record_bytes.argtypes = [ci]
+    L.n3dt_flat_adam_step.restype = ci
+    L.n3dt_flat_adam_step.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     if L.n3dt_abi_version() != 5:
         raise N3dtError("libn3dt.so ABI version mismatch")
+    for which, rec in enumerate((AdamTensor, AdamChunk, AdamGroup)):
+        if L.n3dt_flat_adam_record_bytes(which) != ctypes.sizeof(rec):
+            raise N3dtError("libn3dt.so: FlatAdam table record %d differs from its ctypes mirror" % which)
     _LIB = L
     return L
 

@@ -1,8 +1,8 @@
 """Train-step harness around HeadNeRFNet (the caller side of SURVEY 8a row a12).
 
 The reference's loop is `pred = model("train", ...)` -> data losses -> `backward()` -> two Adam steps
-(talker_trainer.py:1008-1067).  The renderer's forward/backward run in libn3dt; the loss terms and the
-optimizer are plain PyTorch, exactly as in the reference (they are outside the accelerated path).
+(talker_trainer.py:1008-1067).  The renderer's forward/backward and the fused loss tail run in libn3dt; the optimizer is
+torch.optim.Adam as in the reference (make_optimizer) or the same step as one libn3dt launch (make_flat_optimizer).
 """
 import torch
 import torch.nn.functional as F
@@ -151,6 +151,15 @@ class HeadNeRFLossUtils(object):
 def make_optimizer(net, lr=1e-4):
     """Adam + StepLR as the reference builds them (talker_trainer.py:722-727)."""
     opt = torch.optim.Adam(net.parameters(), lr=lr)
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.1)
+    return opt, sched
+
+
+def make_flat_optimizer(net, lr=1e-4):
+    """The same Adam + StepLR with the optimizer step on libn3dt (n3dt.FlatAdam: one launch over the net's gradient arena,
+    version counters and packed-weight caches kept right after every step)."""
+    from .optim import FlatAdam
+    opt = FlatAdam(net.parameters(), lr=lr, modules=[net])
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.1)
     return opt, sched
 
