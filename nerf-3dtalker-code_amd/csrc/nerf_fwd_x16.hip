@@ -26,8 +26,7 @@
 // One stage: out[N x 32*NB] = W'[N x K] . in[K x 32*NB] + bias (+ activation), NT = N/32 out tiles.
 // The KPE leading k-steps take their B operand from the wave's PE fragments: registers (pe_reg,
 // stage L0) or the wave's LDS copy (pe_lds, skip stage L5); the rest come from hin.
-// `bias` is wave-uniform, so the 32 values of a tile arrive by scalar loads; lane half h picks
-// rows (r&3)+8(r>>2)+4h of the tile.
+// The bias is the C operand of a tile's first weight MFMA (X16TileInit below).
 // SAVE (training forward, NB == 1): every finished output tile is also written to HBM for the backward -- hidden
 // tiles as [sample][channel] images (x16_core.h: x16_image_store) at sv.tile0 + 2 KiB * tile, the RGB_layer_1 activations
 // lane-linear (lane = sample fragments) at sv.tile0 + 1 KiB * k-step.
@@ -37,58 +36,111 @@ struct X16SaveStage {
     unsigned* gate0;       // per-lane pointer to this layer's 6 gate words (64 words apart)
 };
 
-// Biases of the training forward come from LDS.  vmcnt retires in order, so hipcc's wait for a bias LOAD also waits for every
-// store issued before it: with the inference form (a global load one tile ahead) each tile began by waiting for the previous
-// tile's 2-3 KiB of saved-tile stores to be acknowledged, while the write path runs near the HBM write bandwidth -- 0.2 ms of
-// the 1.65 ms kernel (diagnostic build without the loads).  Here every wave copies the next stage's bias table (<= 1.5 KiB) into
-// its own LDS slot by LDS-DMA a stage ahead (X16BiasLds::stage_in; complete by the next rendezvous wait, which leaves only
-// the stores issued since outstanding), and a tile's value is read with an asm ds_read_b32 issued a tile ahead: LDS returns in
-// order, so it has landed once any later weight fragment has been awaited -- no wait of its own, nothing on vmcnt.
+// Biases come from LDS (the 4-wave x 64-sample tiling excepted, below).  Every wave copies the next stage's fp32 bias table (<= 1.5 KiB) into its own
+// LDS slot by LDS-DMA a stage ahead (X16BiasLds::stage_in; complete two rendezvous waits later at the latest -- the first may
+// still leave as many operations outstanding as stores were reported before the copy was issued -- and read no earlier than the
+// stage's last tile).  Nothing of it is on vmcnt inside the stream: vmcnt retires in order, so a wait for a bias LOAD would also
+// wait for every saved-tile store of the training forward issued before it (0.2 ms of its 1.65 ms, diagnostic build).
+//
+// A tile's accumulator starts as the bias itself, exact in fp32, with no instruction of the matrix pipe spent on it (an
+// earlier form broadcast a hi/lo-split 16-bit copy of it with one extra MFMA per tile: 95 of 2 375 per block).  Accumulator
+// register r of lane half h is row (r & 3) + 8 (r >> 2) + 4 h of the tile, so the 16 values of a lane are four groups of four
+// consecutive floats, at float 32 ot + 8 j + 4 h of the table, j = 0 .. 3: four ds_read_b128, each a broadcast within a lane
+// half.  They are issued from inline asm a TILE AHEAD into the register set the running tile parity picks, and not
+// awaited: LDS returns in order, so they have landed once a fragment read issued after them has been awaited, which
+// WeightStream::next does DEPTH - 1 pieces later (its EXTRA argument keeps the counted waits in between exact).
+// The FIRST tile of a stage is the exception.  Its reads are issued behind the k-loop of the last tile of the stage before,
+// under that tile's pack / store epilogue, and the stage begins with the one full LDS wait it has (settle): a last tile
+// holds the whole input and 11/12 of the output of its layer, and a second register set across its k-loop does not fit the
+// 256 registers of two waves per SIMD (28 - 132 bytes of scratch in every instantiation when it was tried).
+// Two kinds of instantiation keep the earlier form, in which one float per lane (row c of the tile), fetched a tile ahead,
+// is split hi/lo and broadcast by one extra MFMA (template argument BIAS of x16_stage):
+//   * the training forward (SAVE), from LDS with x16_bias_read (X16_BIAS_LDS_MFMA): 84 bytes of scratch with the second
+//     register set next to its save pointers, 16 without.  Its density stage loads from global memory, as it always did;
+//   * the 4-wave x 64-sample tiling (NB = 2, diagnostic only), by global loads (X16_BIAS_GLOBAL_MFMA), exactly as before: its
+//     256 ARCHITECTURAL registers hold both blocks' activations; either LDS form costs it 16 - 44 bytes of scratch and brings
+//     back the misplaced register copy that tools/check_smem_hazard.py scans for (scan_join_copies).
+enum { X16_BIAS_GLOBAL_MFMA = 0, X16_BIAS_LDS_MFMA = 1, X16_BIAS_LDS_C = 2 };
 #define X16_BIAS_SLOT 1536  // bytes: 384 floats
-#ifndef X16_SAVE_LDS_BIAS
-#define X16_SAVE_LDS_BIAS 1
-#endif
 struct X16BiasLds {
     unsigned char* slots;  // this wave's two slots (generic pointer, wave-uniform)
-    unsigned addr;         // LDS byte address of slot 0 + 4 * (lane & 31)
-    // table -> slot by LDS-DMA: n floats (a multiple of 64), 256 B per instruction, lane-linear
-    __device__ __forceinline__ void stage_in(const float* table, const int n, const int slot, const int lane) const {
+    unsigned addr;         // LDS byte address of slot 0 + 16 * (lane >> 5)   (X16_BIAS_LDS_MFMA: + 4 * (lane & 31))
+    // table -> slot (+ at, in floats) by LDS-DMA: n floats (a multiple of 64), 256 B per instruction, lane-linear
+    __device__ __forceinline__ void stage_in(const float* table, const int n, const int slot, const int lane, const int at = 0) const {
 #pragma unroll
         for (int i = 0; i < 6; ++i)
             if (64 * i < n)
-                __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(table + 64 * i + lane), (LDS_AS void*)(slots + slot * X16_BIAS_SLOT + 256 * i), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(table + 64 * i + lane),
+                                                 (LDS_AS void*)(slots + slot * X16_BIAS_SLOT + 4 * at + 256 * i), 4, 0, 0);
+    }
+    // LDS address (lane half included) of the table staged into `slot` at float `at`
+    __device__ __forceinline__ unsigned at(const int slot, const int at = 0) const { return addr + slot * X16_BIAS_SLOT + 4 * at; }
+};
+// the bias of one output tile as the lane's 16 accumulator values; two sets, tile n of the kernel's running count uses set n & 1
+struct X16TileInit {
+    f32x4 q[2][4];
+    // OFF: byte offset of the tile in the table (128 per tile); table: X16BiasLds::at()
+    template <int SET, int OFF>
+    __device__ __forceinline__ void issue(const unsigned table) {
+        asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\t"
+                     "ds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
+                     : "=&v"(q[SET][0]), "=&v"(q[SET][1]), "=&v"(q[SET][2]), "=&v"(q[SET][3])
+                     : "v"(table), "i"(OFF), "i"(OFF + 32), "i"(OFF + 64), "i"(OFF + 96)
+                     : "memory");
+    }
+    // the set stays reserved up to here (volatile asm statements keep their order: this one stays behind the stream's waits)
+    template <int SET>
+    __device__ __forceinline__ void landed() {
+        asm volatile("" : "+v"(q[SET][0]), "+v"(q[SET][1]), "+v"(q[SET][2]), "+v"(q[SET][3]));
+    }
+    // first tile of a stage: one full wait (the two weight prefetches in flight are older and had to land first anyway)
+    template <int SET>
+    __device__ __forceinline__ void settle() {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(q[SET][0]), "+v"(q[SET][1]), "+v"(q[SET][2]), "+v"(q[SET][3]));
+    }
+    template <int SET>
+    __device__ __forceinline__ f32x16 get() const {
+        f32x16 v;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = q[SET][r >> 2][r & 3];
+        return v;
     }
 };
+constexpr int X16_TILE_INIT_READS = 4;
 
-template <int PREC, int NB, int WAVES, int KS, int KPE, int NT, int MODE, bool SAVE = false, class WS>
-__device__ __forceinline__ void x16_stage(WS& ws, const float* __restrict__ bias,
+// PAR: parity of the stage's first tile in the kernel's running tile count.  The caller has issued that tile's bias reads;
+// NEXT: a stage follows, and this one issues the reads of ITS first tile (table next_lds) behind its last k-loop.
+// bias: the stage's table in global memory (read by X16_BIAS_GLOBAL_MFMA only); bias_lds: X16BiasLds::at() of its LDS copy
+template <int PREC, int NB, int WAVES, int KS, int KPE, int NT, int MODE, bool SAVE, int BIAS, int PAR, bool NEXT, class WS>
+__device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* __restrict__ bias, const unsigned bias_lds, const unsigned next_lds,
                                           const typename X16<PREC>::frag (&pe_reg)[NB][4], const unsigned char* pe_lds,
                                           const typename X16<PREC>::frag (&hin)[NB][24], typename X16<PREC>::frag (&hout)[NB][24],
                                           float (&aux)[NB], float* const (&po)[NB], const bool (&live)[NB], const int lane,
-                                          const X16SaveStage<PREC>* sv = nullptr, const short relu_lo = 0,
-                                          const unsigned bias_lds = 0 /* SAVE: LDS address of this stage's bias slot + 4 c */) {
+                                          const X16SaveStage<PREC>* sv = nullptr, const short relu_lo = 0) {
     typedef typename X16<PREC>::frag frag;
     static_assert(!SAVE || NB == 1, "the training forward runs one block per wave");
+    static_assert(KS >= WS::depth, "a tile's bias reads are covered by the wait of its own k-step DEPTH - 1");
     const int h = lane >> 5, c = lane & 31;
     float red[NB][32];
     unsigned gate_word = 0;
-    const frag ones = X16<PREC>::ones_frag();
-    float bias_cur = 0.0f, bias_nxt = 0.0f;
-    constexpr bool LB = SAVE && X16_SAVE_LDS_BIAS;
+    constexpr bool PACKS = (MODE == MODE_HIDDEN || MODE == MODE_LINEAR);
+    f32x16 acc[NB];
+    constexpr bool CINIT = BIAS == X16_BIAS_LDS_C, LB = BIAS == X16_BIAS_LDS_MFMA;
+    // the two MFMA forms
+    [[maybe_unused]] const frag ones = X16<PREC>::ones_frag();
+    [[maybe_unused]] float bias_cur = 0.0f, bias_nxt = 0.0f;
     if constexpr (LB) {
         x16_bias_read<0>(bias_cur, bias_lds);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bias_cur));  // once per stage; the tiles' values travel a tile ahead
-    } else {
+    } else if constexpr (!CINIT) {
         bias_cur = bias[c];
     }
-    constexpr bool PACKS = (MODE == MODE_HIDDEN || MODE == MODE_LINEAR);
-    f32x16 acc[1][NB];
     auto finish_half = [&](const int t, const int half) {  // registers 8*half .. 8*half+7 of tile t -> k-step 2t+half
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             float v[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = acc[0][nb][8 * half + r];
+            for (int r = 0; r < 8; ++r) v[r] = acc[nb][8 * half + r];
             frag f = X16<PREC>::pack(v);
             if (MODE == MODE_HIDDEN) f = X16<PREC>::relu(f, relu_lo);
             hout[nb][2 * t + half] = f;
@@ -96,9 +148,16 @@ __device__ __forceinline__ void x16_stage(WS& ws, const float* __restrict__ bias
     };
     static_for<0, NT>([&](auto ot_c) {
         constexpr int ot = decltype(ot_c)::value;
-        constexpr int cur = 0;
+        constexpr int cs = (PAR + ot) & 1, ns = cs ^ 1;    // this tile's register set of ti, the next tile's
+        constexpr bool FETCH = CINIT && ot + 1 < NT;       // the next tile's bias is read under this tile's MFMAs
         X16_T(const unsigned long long s0 = x16_now();)
-        {
+        if constexpr (CINIT) {
+            if constexpr (ot == 0) ti.template settle<cs>();
+            if constexpr (FETCH) ti.template issue<ns, (ot + 1) * 128>(bias_lds);
+            const f32x16 binit = ti.template get<cs>();  // landed and pinned a tile ago: C of the first weight MFMA
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) acc[nb] = binit;
+        } else {
             // acc = bias, broadcast over the samples, by ONE extra MFMA (hi/lo split keeps ~16 mantissa bits):
             // lane r of the lower half holds bias[ot*32 + r], fetched one tile ahead
             const frag bf = X16<PREC>::bias_frag(bias_cur, h == 0);
@@ -112,12 +171,15 @@ __device__ __forceinline__ void x16_stage(WS& ws, const float* __restrict__ bias
             for (int r = 0; r < 16; ++r) zero[r] = 0.0f;
             const f32x16 binit = X16<PREC>::mfma(bf, ones, zero);
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[cur][nb] = binit;
+            for (int nb = 0; nb < NB; ++nb) acc[nb] = binit;
         }
         X16_T(const unsigned long long s1 = x16_now(); const unsigned long long rv0 = ws.t_rv;)
         static_for<0, KS>([&](auto ks_c) {
             constexpr int ks = decltype(ks_c)::value;
-            const frag a_cur = ws.template next<MODE == MODE_COMPOSITE, NT * KS, ot * KS + ks>();
+            // the four reads just issued are younger than the pieces of k-steps 0 .. DEPTH - 2, whose waits therefore allow
+            // four more operations in flight; the wait of k-step DEPTH - 1 is the one that covers them
+            const frag a_cur = ws.template next<MODE == MODE_COMPOSITE, NT * KS, ot * KS + ks,
+                                                (FETCH && ks < WS::depth - 1) ? X16_TILE_INIT_READS : 0>();
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 frag b;
@@ -127,13 +189,15 @@ __device__ __forceinline__ void x16_stage(WS& ws, const float* __restrict__ bias
                 } else {
                     b = hin[nb][ks >= KPE ? ks - KPE : 0];
                 }
-                acc[cur][nb] = X16<PREC>::mfma(a_cur, b, acc[cur][nb]);
+                acc[nb] = X16<PREC>::mfma(a_cur, b, acc[nb]);
             }
         });
+        // landed: the reads are older than the fragment awaited at k-step DEPTH - 1 of the loop above
+        if constexpr (FETCH) ti.template landed<ns>();
+        else if constexpr (CINIT && NEXT && ot + 1 == NT) ti.template issue<ns, 0>(next_lds);  // awaited by the next stage's settle
         if constexpr (LB && ot + 1 < NT) {
-            // landed: it is older than every fragment read awaited in the k-loop above (the accumulator rides along: the
-            // statement then cannot move ahead of the loop's last MFMA)
-            asm volatile("" : "+v"(bias_nxt), "+v"(acc[cur][0]));
+            // landed likewise (the accumulator rides along: the statement then cannot move ahead of the loop's last MFMA)
+            asm volatile("" : "+v"(bias_nxt), "+v"(acc[0]));
             bias_cur = bias_nxt;
         }
         X16_T(const unsigned long long s2 = x16_now();)
@@ -170,17 +234,17 @@ __device__ __forceinline__ void x16_stage(WS& ws, const float* __restrict__ bias
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             if (MODE == MODE_DENSITY) {
-                aux[nb] = acc[cur][nb][0];  // row 0 of the tile, valid on lanes with h == 0
+                aux[nb] = acc[nb][0];  // row 0 of the tile, valid on lanes with h == 0
             } else if (MODE == MODE_COMPOSITE) {
                 // weighted RGB_layer_1 activations; two tiles (32 values) feed one butterfly over the samples
 #pragma unroll
-                for (int r = 0; r < 16; ++r) red[nb][(ot & 1) * 16 + r] = fmaxf(acc[cur][nb][r], 0.0f) * aux[nb];
+                for (int r = 0; r < 16; ++r) red[nb][(ot & 1) * 16 + r] = fmaxf(acc[nb][r], 0.0f) * aux[nb];
                 if constexpr (SAVE) {
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
                         float v[8];
 #pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = fmaxf(acc[cur][nb][8 * half + r], 0.0f);
+                        for (int r = 0; r < 8; ++r) v[r] = fmaxf(acc[nb][8 * half + r], 0.0f);
                         __builtin_nontemporal_store(X16<PREC>::pack(v), reinterpret_cast<frag*>(sv->tile0 + (2 * ot + half) * X16_PIECE));
                     }
                     ws.note_stores(2);
@@ -315,41 +379,53 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
             return nullptr;
         }
     };
-    // SAVE: per-wave bias slots in LDS, filled a stage ahead (X16BiasLds above); stage k reads slot k & 1
-    X16BiasLds bl;
-    if constexpr (SAVE && X16_SAVE_LDS_BIAS) {
+    // how a tile's bias reaches its accumulator (X16TileInit above)
+    constexpr int BIAS = SAVE ? X16_BIAS_LDS_MFMA : (NB == 1 ? X16_BIAS_LDS_C : X16_BIAS_GLOBAL_MFMA);
+    constexpr int BIAS_DEN = BIAS == X16_BIAS_LDS_C ? X16_BIAS_LDS_C : X16_BIAS_GLOBAL_MFMA;
+    // per-wave bias slots in LDS, filled a stage ahead (X16BiasLds above).  Hidden stage k reads slot k & 1; the density tile
+    // (64 floats staged, 32 used) and the merged RGB stage's table share slot 0, filled while stage 7 runs: the density
+    // stage is a single chunk, too short to stage anything under it.
+    X16BiasLds bl{nullptr, 0u};
+    constexpr int DEN_AT = 192;  // float offset of the density tile in slot 0, behind the 192 RGB biases
+    if constexpr (BIAS != X16_BIAS_GLOBAL_MFMA) {
         bl.slots = lds + X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * NB * 4 * X16_PIECE + (size_t)wave * 2 * X16_BIAS_SLOT;
-        bl.addr = (unsigned)(size_t)(LDS_AS unsigned char*)bl.slots + 4 * c;
+        bl.addr = (unsigned)(size_t)(LDS_AS unsigned char*)bl.slots + (BIAS == X16_BIAS_LDS_C ? 16 * h : 4 * c);
         bl.stage_in(fb + n3dt_bias_offset(0), 384, 0, lane);
     }
-    // the bias slot of SAVE stage number k (0 .. 8), after staging the table of the stage that follows it
-    auto bias_slot = [&](const int k, const int next_table, const int next_n) -> unsigned {
-        if constexpr (SAVE && X16_SAVE_LDS_BIAS) {
-            if (next_table >= 0) bl.stage_in(next_table == 10 ? b10 : fb + n3dt_bias_offset(next_table), next_n, (k + 1) & 1, lane);
-            return bl.addr + (k & 1) * X16_BIAS_SLOT;
-        } else {
-            return 0u;
+    // the bias slot of hidden stage k, after staging the table(s) of the stage that follows it
+    auto bias_slot = [&](const int k) -> unsigned {
+        if constexpr (BIAS != X16_BIAS_GLOBAL_MFMA) {
+            if (k < 7) {
+                bl.stage_in(fb + n3dt_bias_offset(k + 1), 384, (k + 1) & 1, lane);
+            } else {
+                bl.stage_in(b10, 192, 0, lane);
+                if constexpr (BIAS_DEN == X16_BIAS_LDS_C) bl.stage_in(fb + n3dt_bias_offset(8), 64, 0, lane, DEN_AT);
+            }
         }
+        return bl.at(k & 1);
     };
-    ws.prologue_wait();
+    ws.prologue_wait();  // (vmcnt(0): table 0 is in its slot)
     X16_T(if (wlocal && live[0]) ws.tl = wlocal + (size_t)blk[0] * X16_BS;)
+    X16TileInit ti;
+    if constexpr (BIAS == X16_BIAS_LDS_C) ti.template issue<0, 0>(bl.at(0));
 
     frag ha[NB][24], hb[NB][24];
     float aux[NB];
     // FeaExt_module_0 (reference: NetWorks/models.py:69-71)
-    x16_stage<PREC, NB, WAVES, 4, 4, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(0), pe, nullptr, ha, ha, aux, po, live, lane, sv_hidden(0), 0, bias_slot(0, 1, 384));
+    x16_stage<PREC, NB, WAVES, 4, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(0), bias_slot(0), bl.at(1), pe, nullptr, ha, ha, aux, po, live, lane, sv_hidden(0));
     // FeaExt_module_1..7 with the skip concat after layer 4 (models.py:72-76).  Fully unrolled on purpose: rolling the
     // identical 384->384 layers into a loop (tried: one-layer body + register copy, two-layer ping-pong body) makes the
     // register allocator spill 120-270 VGPRs across the back edge and runs 1.7x slower.
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(1), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(1), 0, bias_slot(1, 2, 384));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(2), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(2), 0, bias_slot(2, 3, 384));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(3), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(3), 0, bias_slot(3, 4, 384));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(4), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(4), 0, bias_slot(4, 5, 384));
-    x16_stage<PREC, NB, WAVES, 28, 4, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(5), pe, pe_lds, ha, hb, aux, po, live, lane, sv_hidden(5), 0, bias_slot(5, 6, 384));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(6), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(6), 0, bias_slot(6, 7, 384));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE>(ws, fb + n3dt_bias_offset(7), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(7), 0, bias_slot(7, 10, 192));
-    // density head on h7 (models.py:78,84); the bias rides in the accumulator
-    x16_stage<PREC, NB, WAVES, 24, 0, 1, MODE_DENSITY, false>(ws, fb + n3dt_bias_offset(8), pe, nullptr, hb, ha, aux, po, live, lane);
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(1), bias_slot(1), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(1));
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(2), bias_slot(2), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(2));
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(3), bias_slot(3), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(3));
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(4), bias_slot(4), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(4));
+    x16_stage<PREC, NB, WAVES, 28, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(5), bias_slot(5), bl.at(0), pe, pe_lds, ha, hb, aux, po, live, lane, sv_hidden(5));
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(6), bias_slot(6), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(6));
+    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(7), bias_slot(7), bl.at(0, DEN_AT), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(7));
+    // density head on h7 (models.py:78,84); the bias rides in the accumulator.  Its one tile is tile 96 of the running count
+    // and fetches the first RGB tile's bias, which therefore starts on parity 1.
+    x16_stage<PREC, NB, WAVES, 24, 0, 1, MODE_DENSITY, false, BIAS_DEN, 0, true>(ws, ti, fb + n3dt_bias_offset(8), bl.at(0, DEN_AT), bl.at(0), pe, nullptr, hb, ha, aux, po, live, lane);
     // alpha, in-block transmittance and weights (reference: NetWorks/utils.py:273-289)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -397,8 +473,8 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         svs.tile0 = tsv.gS + (size_t)rec * 12 * X16_PIECE + lane * 16;
         svs.gate0 = nullptr;
     }
-    x16_stage<PREC, NB, WAVES, 24, 0, 6, MODE_COMPOSITE, SAVE>(ws, b10, pe, nullptr, hb, ha, aux, po, live, lane,
-                                                                     SAVE ? &svs : nullptr, 0, bias_slot(8, -1, 0));
+    x16_stage<PREC, NB, WAVES, 24, 0, 6, MODE_COMPOSITE, SAVE, BIAS, 1, false>(ws, ti, b10, bl.at(0), 0u, pe, nullptr, hb, ha, aux, po, live, lane,
+                                                                               SAVE ? &svs : nullptr);
 #ifdef X16_STAMP
     if (wlocal && lane == 0 && live[0]) {
         float* dbg = wlocal + (size_t)blk[0] * X16_BS;
@@ -457,7 +533,8 @@ static void launch_x16(const N3dtGeom* g, const void* packed, const float* fold,
     const long total = (long)g->batch * g->n_rays * bpr;
     const long per_wg = (long)WAVES * NB;
     const int grid = (int)((total + per_wg - 1) / per_wg);
-    const size_t lds_bytes = X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * NB * 4 * X16_PIECE;
+    // weight ring + the waves' PE copies + their two bias slots: 72 + 32 + 24 KiB with 8 waves, one workgroup per CU
+    const size_t lds_bytes = X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * NB * 4 * X16_PIECE + (size_t)WAVES * 2 * X16_BIAS_SLOT;
     auto kern = nerf_fwd_x16_kernel<PREC, NB, WAVES>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds_bytes, stream, *g, reinterpret_cast<const unsigned char*>(packed),

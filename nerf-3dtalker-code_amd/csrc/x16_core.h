@@ -311,7 +311,14 @@ struct WeightStream {
     }
     // Fragment of stage-local piece P (stages are whole chunks, so P % X16_CH and P % DEPTH equal their
     // stream-global values).  LAST/NP: the final stage must not prefetch past the end of the stream.
-    template <bool LAST, int NP, int P>
+    // EXTRA: LDS reads of the caller's own (inline asm, not awaited by it) that are YOUNGER than piece P's read and may still
+    // be in flight here.  LDS returns in order, so they sit between piece P and the prefetches in the queue and the counted
+    // wait has to allow for them, or it would wait for them and for the prefetch behind them as well.  Reads the caller issues
+    // just before next<P0>() are younger than the pieces P0 .. P0 + DEPTH - 2 (read before them) and older than piece
+    // P0 + DEPTH - 1, which next<P0>() itself reads: the caller passes EXTRA to exactly those DEPTH - 1 calls, and its reads
+    // have landed once next<P0 + DEPTH - 1>() returns.
+    static constexpr int depth = DEPTH;
+    template <bool LAST, int NP, int P, int EXTRA = 0>
     __device__ __forceinline__ frag next() {
         constexpr int rv = X16_CH - DEPTH;
         if (P % X16_CH == rv) {
@@ -330,7 +337,8 @@ struct WeightStream {
         }
         // at the stream's tail fewer reads are in flight behind this one: the count shrinks with them
         constexpr int younger = (LAST && NP - 1 - P < DEPTH - 1) ? NP - 1 - P : DEPTH - 1;
-        await_frag<younger>(a[P % DEPTH]);
+        static_assert(younger + EXTRA <= 15, "lgkmcnt is a 4-bit counter");
+        await_frag<younger + EXTRA>(a[P % DEPTH]);
         const frag r = a[P % DEPTH];
         if ((P + 1) % X16_CH == 0) {
             ++chunk;
