@@ -153,6 +153,22 @@ int n3dt_render_fwd(const N3dtGeom* g, int precision, const void* packed_mlp, co
                     float* fg_feat, float* bg_alpha, float* depth, float* weight, float* merge_feat,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* n3dt_render_fwd for a caller that hands the merged map straight to the 2-D renderer's 16-bit path (precision BF16 / F16 /
+ * BF16X3 only).  Two more optional outputs, both written by the ray head from the fp32 values it holds in registers:
+ *   merge_feat16 [B,N_r,C] 16-bit: merge_feat rounded (nearest-even) to the renderer's map type -- bf16 for N3DT_BF16, f16
+ *                for N3DT_F16 and N3DT_BF16X3 -- exactly what the renderer's first block forms from an fp32 map while staging
+ *   rgb0         [B,3,N_r] fp32 planar: feat_2_rgb[0] of the FP32 merged values, rgb0_w [3,C], rgb0_b [3]
+ *                (the projection n3dt_neural_render_fwd runs as a pass of its own over an fp32 map)
+ * One of fg_feat / merge_feat / merge_feat16 must be given; rgb0 needs rgb0_w and rgb0_b; merge_feat, when NULL, is not
+ * written.  Feed both to n3dt_neural_render_fwd16_reuse.  An addition to ABI 5: no existing entry changed. */
+int n3dt_render_fwd16(const N3dtGeom* g, int precision, const void* packed_mlp, const N3dtMlpParams* p,
+                      const float* xy, const float* R, const float* T, const float* Kinv,
+                      const float* shape, const float* appea, const float* audio, const float* t_rand,
+                      const float* bg_featmap, const float* ray_bias,
+                      float* fg_feat, float* bg_alpha, float* depth, float* weight, float* merge_feat,
+                      void* merge_feat16, float* rgb0, const float* rgb0_w, const float* rgb0_b,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- include_vd: the view-direction columns of RGB_layer_1 as a per-ray bias (ABI 5) -------------------------------
  * Replaces, for `include_vd=True`: GenSamplePoints' ray direction (NetWorks/utils.py:149-153), `vd_encoder(fg_dirs)`
  * (HeadNeRFNet.py:141-142: Embedder, 4 frequencies + input = 27 channels, utils.py:20-51), its expand over the samples and the
@@ -229,6 +245,14 @@ int n3dt_neural_render_pack(const N3dtGeom* g, int nb, int precision, const N3dt
                             size_t workspace_bytes, void* stream);
 int n3dt_neural_render_fwd_reuse(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const float* featmap,
                                  float* img, void* workspace, size_t workspace_bytes, void* stream);
+/* n3dt_neural_render_fwd_reuse on the outputs of n3dt_render_fwd16 (16-bit precisions only): featmap16 [nb, fs, fs, C] in the
+ * map type of `precision`, rgb0 [nb, 3, fs, fs] the level-0 projection (read only).  The first block then reads 16-bit rows
+ * and no projection pass runs; everything behind the first block's staging is the fp32-input form's arithmetic, bit for bit. */
+/* The level-0 projection on its own, as n3dt_neural_render_fwd's 16-bit path runs it on an fp32 map: featmap [nb, n_pix, 256]
+ * -> rgb0 [nb, 3, n_pix] = feat_2_rgb[0] (w [3,256], b [3]).  A seam for comparing the two producers of rgb0. */
+int n3dt_feat_to_rgb0(int nb, int n_pix, const float* featmap, const float* w, const float* b, float* rgb0, void* stream);
+int n3dt_neural_render_fwd16_reuse(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const void* featmap16,
+                                   const float* rgb0, float* img, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training path (fwd -> loss -> backward) -----------------------------------
  * `precision` = N3DT_F32: exact fp32 (the mode the gradient-parity tests pin); N3DT_BF16: every matrix product

@@ -19,6 +19,8 @@ void n3dt_launch_ray_head(const N3dtGeom*, int, int, const float*, const float*,
                           float*, float*, float*, hipStream_t);
 void n3dt_launch_ray_head_mfma(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*, float*,
                                float*, float*, float*, float*, hipStream_t);
+void n3dt_launch_ray_head_mfma16(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*, float*,
+                                 float*, float*, float*, void*, int, float*, const float*, const float*, hipStream_t);
 void n3dt_launch_chw_to_hwc(int, int, const float*, float*, hipStream_t);
 void n3dt_launch_rayfold(const N3dtGeom*, const float*, const float*, hipStream_t);
 void n3dt_launch_ray_vd_bias(const N3dtGeom*, const float*, long, const float*, const float*, const float*, float*, hipStream_t);
@@ -69,6 +71,8 @@ void n3dt_launch_nr_train_fwd(const N3dtGeom*, int, const N3dtRenderParams*, con
 void n3dt_launch_nr_bwd(const N3dtGeom*, int, const N3dtRenderParams*, const N3dtRenderGrads*, const float*, const float*, const float*,
                         float*, float*, int, hipStream_t);
 void n3dt_launch_neural_render(const N3dtGeom*, int, int, const N3dtRenderParams*, const float*, float*, float*, int, hipStream_t);
+void n3dt_launch_feat_to_rgb0(int, int, const float*, const float*, const float*, float*, hipStream_t);
+void n3dt_launch_neural_render16(const N3dtGeom*, int, int, const N3dtRenderParams*, const void*, const float*, float*, float*, hipStream_t);
 void n3dt_launch_stage(const N3dtStageCopy*, hipStream_t);
 size_t n3dt_vgg_packed_layout_bytes(int);
 size_t n3dt_vgg_saved_floats(int);
@@ -235,19 +239,23 @@ extern "C" size_t n3dt_render_workspace_bytes(const N3dtGeom* g, int precision) 
     return render_carve(g, precision).total;
 }
 
-extern "C" int n3dt_render_fwd(const N3dtGeom* g, int precision, const void* packed_mlp, const N3dtMlpParams* p, const float* xy,
-                               const float* R, const float* T, const float* Kinv, const float* shape, const float* appea,
-                               const float* audio, const float* t_rand, const float* bg_featmap, const float* ray_bias, float* fg_feat,
-                               float* bg_alpha, float* depth, float* weight, float* merge_feat, void* workspace,
-                               size_t workspace_bytes, void* stream) {
+// n3dt_render_fwd and n3dt_render_fwd16 (the latter with the ray head's 16-bit map / level-0 RGB outputs)
+static int render_fwd_common(const N3dtGeom* g, int precision, const void* packed_mlp, const N3dtMlpParams* p, const float* xy,
+                             const float* R, const float* T, const float* Kinv, const float* shape, const float* appea,
+                             const float* audio, const float* t_rand, const float* bg_featmap, const float* ray_bias, float* fg_feat,
+                             float* bg_alpha, float* depth, float* weight, float* merge_feat, void* merge_feat16, float* rgb0,
+                             const float* rgb0_w, const float* rgb0_b, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = check_geom(g, precision);
     if (rc) return rc;
     if ((rc = check_ray_bias(g, ray_bias, "n3dt_render_fwd")) != N3DT_OK) return rc;
     if (!packed_mlp || !p || !xy || !R || !T || !Kinv || !shape || !appea || !workspace)
         return fail(N3DT_EINVAL, "n3dt_render_fwd: NULL argument");
-    if (!fg_feat && !merge_feat) return fail(N3DT_EINVAL, "n3dt_render_fwd: neither fg_feat nor merge_feat requested");
+    if (!fg_feat && !merge_feat && !merge_feat16) return fail(N3DT_EINVAL, "n3dt_render_fwd: neither fg_feat nor merge_feat requested");
     if (g->audio_dim > 0 && !audio) return fail(N3DT_EINVAL, "n3dt_render_fwd: audio is NULL but audio_dim > 0");
-    if (merge_feat && !bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_fwd: merge_feat needs bg_featmap");
+    if ((merge_feat || merge_feat16 || rgb0) && !bg_featmap) return fail(N3DT_EINVAL, "n3dt_render_fwd: merge_feat needs bg_featmap");
+    if ((merge_feat16 || rgb0) && precision == N3DT_F32)
+        return fail(N3DT_EINVAL, "n3dt_render_fwd16: the 16-bit map and rgb0 are outputs of the 16-bit precisions");
+    if (rgb0 && (!rgb0_w || !rgb0_b)) return fail(N3DT_EINVAL, "n3dt_render_fwd16: rgb0 needs rgb0_w and rgb0_b");
     if (g->z_planes_given && !t_rand) return fail(N3DT_EINVAL, "n3dt_render_fwd: z_planes_given but no planes passed as t_rand");
     const RenderCarve c = render_carve(g, precision);
     if (workspace_bytes < c.total) return fail(N3DT_EWORKSPACE, "n3dt_render_fwd: workspace too small");
@@ -271,15 +279,37 @@ extern "C" int n3dt_render_fwd(const N3dtGeom* g, int precision, const void* pac
     n3dt_prof_span_end(span, s);
     const float* tail = (const float*)((const unsigned char*)packed_mlp + n3dt_packed_tail_offset(precision));
     const float* bghwc = bg_featmap;
-    if (merge_feat && !g->bg_is_hwc) {  // [C][N_r] parameter -> [N_r][C]
+    const bool merged = merge_feat || merge_feat16 || rgb0;
+    if (merged && !g->bg_is_hwc) {  // [C][N_r] parameter -> [N_r][C]
         n3dt_launch_chw_to_hwc(g->feat_nc, g->n_rays, bg_featmap, (float*)(ws + c.bghwc), s);
         bghwc = (const float*)(ws + c.bghwc);
     }
     if (precision == N3DT_F32)
         n3dt_launch_ray_head(g, c.bpr, c.bs, part, wlocal, tail, bghwc, 1, fg_feat, bg_alpha, depth, weight, merge_feat, s);
+    else if (merge_feat16 || rgb0)  // (the renderer runs the split-precision mode on its f16 path)
+        n3dt_launch_ray_head_mfma16(g, c.bpr, c.bs, part, wlocal, tail, bghwc, 1, fg_feat, bg_alpha, depth, weight, merge_feat, merge_feat16,
+                                    precision == N3DT_BF16 ? N3DT_BF16 : N3DT_F16, rgb0, rgb0_w, rgb0_b, s);
     else
         n3dt_launch_ray_head_mfma(g, c.bpr, c.bs, part, wlocal, tail, bghwc, 1, fg_feat, bg_alpha, depth, weight, merge_feat, nullptr, s);
     return check_hip("n3dt_render_fwd");
+}
+
+extern "C" int n3dt_render_fwd(const N3dtGeom* g, int precision, const void* packed_mlp, const N3dtMlpParams* p, const float* xy,
+                               const float* R, const float* T, const float* Kinv, const float* shape, const float* appea,
+                               const float* audio, const float* t_rand, const float* bg_featmap, const float* ray_bias, float* fg_feat,
+                               float* bg_alpha, float* depth, float* weight, float* merge_feat, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return render_fwd_common(g, precision, packed_mlp, p, xy, R, T, Kinv, shape, appea, audio, t_rand, bg_featmap, ray_bias, fg_feat, bg_alpha,
+                             depth, weight, merge_feat, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int n3dt_render_fwd16(const N3dtGeom* g, int precision, const void* packed_mlp, const N3dtMlpParams* p, const float* xy,
+                                 const float* R, const float* T, const float* Kinv, const float* shape, const float* appea,
+                                 const float* audio, const float* t_rand, const float* bg_featmap, const float* ray_bias, float* fg_feat,
+                                 float* bg_alpha, float* depth, float* weight, float* merge_feat, void* merge_feat16, float* rgb0,
+                                 const float* rgb0_w, const float* rgb0_b, void* workspace, size_t workspace_bytes, void* stream) {
+    return render_fwd_common(g, precision, packed_mlp, p, xy, R, T, Kinv, shape, appea, audio, t_rand, bg_featmap, ray_bias, fg_feat, bg_alpha,
+                             depth, weight, merge_feat, merge_feat16, rgb0, rgb0_w, rgb0_b, workspace, workspace_bytes, stream);
 }
 
 // ---- stand-alone seams (csrc/seams.hip) ------------------------------------------------------------
@@ -362,9 +392,12 @@ extern "C" size_t n3dt_neural_render_workspace_bytes(const N3dtGeom* g, int nb) 
     return n3dt_nr_workspace_floats(g, nb) * sizeof(float);
 }
 
+// featmap16 / rgb0 (n3dt_neural_render_fwd16_reuse): the 16-bit input map and its level-0 projection instead of `featmap`
 static int neural_render_common(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const float* featmap, float* img,
-                                void* workspace, size_t workspace_bytes, int pack_mode, void* stream, const char* who) {
-    if (!g || !p || !workspace || (pack_mode != 2 && (!featmap || !img))) return fail(N3DT_EINVAL, "neural render: NULL argument");
+                                void* workspace, size_t workspace_bytes, int pack_mode, void* stream, const char* who,
+                                const void* featmap16 = nullptr, const float* rgb0 = nullptr) {
+    if (!g || !p || !workspace || (pack_mode != 2 && ((!featmap && !featmap16) || !img))) return fail(N3DT_EINVAL, "neural render: NULL argument");
+    if (featmap16 && (!rgb0 || precision == N3DT_F32)) return fail(N3DT_EINVAL, "neural render: a 16-bit map needs rgb0 and a 16-bit precision");
     // the split-precision mode renders the 2-D stage on its fp16 path: 2.3e-4 on RGB where bf16 maps reach 1.6e-3 (fixture
     // `contrast`, features O(10)), inside the mode's 1e-3 budget without splitting the renderer's products as well
     if (precision == N3DT_BF16X3) precision = N3DT_F16;
@@ -384,7 +417,10 @@ static int neural_render_common(const N3dtGeom* g, int nb, int precision, const 
     for (int i = 0; i < g->n_blocks; ++i)
         if (!p->psu1_w[i] || !p->psu1_b[i] || !p->psu2_w[i] || !p->psu2_b[i] || !p->feat_w[i] || !p->feat_b[i])
             return fail(N3DT_EINVAL, "NULL neural-render block parameter");
-    n3dt_launch_neural_render(g, nb, precision, p, featmap, img, (float*)workspace, pack_mode, (hipStream_t)stream);
+    if (featmap16)
+        n3dt_launch_neural_render16(g, nb, precision, p, featmap16, rgb0, img, (float*)workspace, (hipStream_t)stream);
+    else
+        n3dt_launch_neural_render(g, nb, precision, p, featmap, img, (float*)workspace, pack_mode, (hipStream_t)stream);
     return check_hip(who);
 }
 
@@ -401,6 +437,20 @@ extern "C" int n3dt_neural_render_pack(const N3dtGeom* g, int nb, int precision,
 extern "C" int n3dt_neural_render_fwd_reuse(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const float* featmap,
                                             float* img, void* workspace, size_t workspace_bytes, void* stream) {
     return neural_render_common(g, nb, precision, p, featmap, img, workspace, workspace_bytes, 1, stream, "n3dt_neural_render_fwd_reuse");
+}
+
+extern "C" int n3dt_feat_to_rgb0(int nb, int n_pix, const float* featmap, const float* w, const float* b, float* rgb0, void* stream) {
+    if (nb < 1 || n_pix < 1 || !featmap || !w || !b || !rgb0) return fail(N3DT_EINVAL, "n3dt_feat_to_rgb0: bad argument");
+    if ((size_t)nb * n_pix >= ((size_t)1 << 27)) return fail(N3DT_EINVAL, "n3dt_feat_to_rgb0: more than 2^27 pixels");
+    n3dt_launch_feat_to_rgb0(nb, n_pix, featmap, w, b, rgb0, (hipStream_t)stream);
+    return check_hip("n3dt_feat_to_rgb0");
+}
+
+extern "C" int n3dt_neural_render_fwd16_reuse(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const void* featmap16,
+                                              const float* rgb0, float* img, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!featmap16) return fail(N3DT_EINVAL, "n3dt_neural_render_fwd16_reuse: NULL argument");
+    return neural_render_common(g, nb, precision, p, nullptr, img, workspace, workspace_bytes, 1, stream, "n3dt_neural_render_fwd16_reuse",
+                                featmap16, rgb0);
 }
 
 // ---- VGG16 perceptual term (csrc/vgg_loss.hip) ----

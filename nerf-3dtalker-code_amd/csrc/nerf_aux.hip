@@ -444,18 +444,27 @@ typedef __bf16 rh_bf16x8 __attribute__((ext_vector_type(8)));
 #define RH_RAYS 32
 // __launch_bounds__(256, 4): four waves per SIMD = four workgroups per CU (128 registers, no spill; hipcc took 160 unasked, three
 // workgroups per CU: 2 048 workgroups at 16 frames then ran in 2.7 rounds instead of 2): 64 -> 55 us per 65 536 rays.
+// MAP16 (the inference forward of the 16-bit modes): the merged map also -- or only -- as the 16-bit rounding the 2-D renderer's
+// first block would form from it (`merge16`, bf16 or f16 by `prec16`), and the renderer's level-0 RGB projection
+// feat_2_rgb[0] of the fp32 merged values (`rgb0`, planar [B][3][N_r]): the renderer then neither reads an fp32 map nor runs
+// a projection pass of its own over it.
+template <bool MAP16, int PREC16 = N3DT_BF16>
 __global__ __launch_bounds__(256, 4) void ray_head_mfma_kernel(N3dtGeom g, int bpr, int bs, const float* __restrict__ part,
                                                             const float* __restrict__ wlocal, const float* __restrict__ tail,
                                                             const float* __restrict__ bg_featmap, int bg_hwc,
                                                             float* __restrict__ fg_feat, float* __restrict__ bg_alpha,
                                                             float* __restrict__ depth, float* __restrict__ weight,
-                                                            float* __restrict__ merge_feat, float* __restrict__ rayrec) {
+                                                            float* __restrict__ merge_feat, float* __restrict__ rayrec,
+                                                            unsigned short* __restrict__ merge16, float* __restrict__ rgb0, const float* __restrict__ rgb_w,
+                                                            const float* __restrict__ rgb_b) {
     __shared__ __attribute__((aligned(16))) float G[RH_RAYS][N3DT_G + 4];  // +4: 16-byte aligned rows off the bank stride
     __shared__ float pref[RH_RAYS][HEAD_MAX_BPR];
     __shared__ float wsum_s[RH_RAYS], dsum_s[RH_RAYS];
+    __shared__ float rgb_s[4][RH_RAYS][3];  // rgb0: every wave's share (its 64 channels) of a ray's level-0 projection
     const long nrays_total = (long)g.batch * g.n_rays;
     const long ray0 = (long)blockIdx.x * RH_RAYS;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (MAP16) rayrec = nullptr;  // (the inference forward keeps no per-ray record)
     if (t < RH_RAYS) {
         const long rg = ray0 + t;
         float Trun = 1.0f, ws = 0.0f, ds = 0.0f;
@@ -553,27 +562,104 @@ __global__ __launch_bounds__(256, 4) void ray_head_mfma_kernel(N3dtGeom g, int b
         }
     }
     // accumulator tile: column (output channel) on the lane, rays in the registers
+    float pr[MAP16 ? 16 : 1][3];  // MAP16: this lane's two channels' share of the level-0 RGB projection, per ray register
+    if constexpr (!MAP16) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int c = 64 * wave + 32 * i + r31;
-        const float b2 = tail[N3DT_G * N3DT_C + c];
-        // (the sixteen background values first, from clamped ray indices, then the stores: no load waits behind a store)
-        float bgv[16];
+        for (int i = 0; i < 2; ++i) {
+            const int c = 64 * wave + 32 * i + r31;
+            const float b2 = tail[N3DT_G * N3DT_C + c];
+            // (the sixteen background values first, from clamped ray indices, then the stores: no load waits behind a store)
+            float bgv[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const long rg = min(ray0 + rr, nrays_total - 1);
-            const int ray = (int)(rg % g.n_rays);
-            bgv[r] = merge_feat ? (bg_hwc ? bg_featmap[(size_t)ray * N3DT_C + c] : bg_featmap[(size_t)c * g.n_rays + ray]) : 0.0f;
+            for (int r = 0; r < 16; ++r) {
+                const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const long rg = min(ray0 + rr, nrays_total - 1);
+                const int ray = (int)(rg % g.n_rays);
+                bgv[r] = merge_feat ? (bg_hwc ? bg_featmap[(size_t)ray * N3DT_C + c] : bg_featmap[(size_t)c * g.n_rays + ray]) : 0.0f;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const long rg = ray0 + rr;
+                if (rg >= nrays_total) continue;
+                const float fg = acc[i][r] + b2 * wsum_s[rr];
+                if (fg_feat) fg_feat[(size_t)rg * N3DT_C + c] = fg;
+                if (merge_feat) merge_feat[(size_t)rg * N3DT_C + c] = fg + (1.0f - wsum_s[rr]) * bgv[r];
+            }
+        }
+    } else {
+        // (this form writes the renderer's inputs only: fg_feat / merge_feat stay with the form above)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = 64 * wave + 32 * i + r31;
+            const float b2 = tail[N3DT_G * N3DT_C + c];
+            float w3[3] = {0.0f, 0.0f, 0.0f};
+            if (rgb0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) w3[k] = rgb_w[k * N3DT_C + c];
+            }
+            // (eight background values at a time: with all sixteen in flight next to the 48 projection sums the form spills)
+#pragma unroll
+            for (int r0 = 0; r0 < 16; r0 += 8) {
+                float bgv[8];
+#pragma unroll
+                for (int r = r0; r < r0 + 8; ++r) {
+                    const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const long rg = min(ray0 + rr, nrays_total - 1);
+                    const int ray = (int)(rg % g.n_rays);
+                    bgv[r - r0] = bg_featmap[(size_t)ray * N3DT_C + c];  // (ray-major: the only layout this form is launched with)
+                }
+#pragma unroll
+                for (int r = r0; r < r0 + 8; ++r) {
+                    const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const long rg = ray0 + rr;
+                    const float mg = (acc[i][r] + b2 * wsum_s[rr]) + (1.0f - wsum_s[rr]) * bgv[r - r0];  // the fp32 merged value, as above
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) pr[MAP16 ? r : 0][k] = i == 0 ? w3[k] * mg : fmaf(w3[k], mg, pr[MAP16 ? r : 0][k]);
+                    // the renderer's first block rounds its fp32 input exactly like this while staging (nr_level_x16_kernel, IN32)
+                    if (merge16 && rg < nrays_total)
+                        merge16[(size_t)rg * N3DT_C + c] = PREC16 == N3DT_BF16 ? __builtin_bit_cast(unsigned short, (__bf16)mg)
+                                                                               : __builtin_bit_cast(unsigned short, (_Float16)mg);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // (keeps the second tile's sixteen loads behind the first tile's stores: hoisted, they cost 38 spilled registers)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (MAP16) if (rgb0) {
+        // 16 rays x 3 sums per lane, 32 lanes (channels) to add up: a halving butterfly -- each step hands half of the rays to
+        // the partner lane -- leaves one ray's three sums per lane pair after four steps (24 + 12 + 6 + 3 exchanges), one more
+        // step closes the pair.  Lane bits 4..1 of r31 then name the ray register the lane ended up with.
+#pragma unroll
+        for (int step = 0; step < 4; ++step) {
+            const int n = 8 >> step, off = 16 >> step;  // rays kept, partner distance
+            const bool up = (r31 & off) != 0;
+#pragma unroll
+            for (int r = 0; r < n; ++r)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float keep = up ? pr[r + n][k] : pr[r][k], send = up ? pr[r][k] : pr[r + n][k];
+                    pr[r][k] = keep + __shfl_xor(send, off, 64);
+                }
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+        for (int k = 0; k < 3; ++k) pr[0][k] += __shfl_xor(pr[0][k], 1, 64);
+        if ((r31 & 1) == 0) {
+            const int rsel = (r31 >> 1) & 15;  // bit 4 of r31 chose the upper 8 registers, bit 3 the upper 4 of those, ...
+            const int rr = (rsel & 3) + 8 * (rsel >> 2) + 4 * h;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) rgb_s[wave][rr][k] = pr[0][k];
+        }
+        __syncthreads();
+        if (t < 3 * RH_RAYS) {
+            const int rr = t % RH_RAYS, k = t / RH_RAYS;
             const long rg = ray0 + rr;
-            if (rg >= nrays_total) continue;
-            const float fg = acc[i][r] + b2 * wsum_s[rr];
-            if (fg_feat) fg_feat[(size_t)rg * N3DT_C + c] = fg;
-            if (merge_feat) merge_feat[(size_t)rg * N3DT_C + c] = fg + (1.0f - wsum_s[rr]) * bgv[r];
+            if (rg < nrays_total) {
+                const float v = (rgb_s[0][rr][k] + rgb_s[1][rr][k]) + (rgb_s[2][rr][k] + rgb_s[3][rr][k]) + rgb_b[k];
+                const long img = rg / g.n_rays, p = rg % g.n_rays;
+                rgb0[(size_t)(img * 3 + k) * g.n_rays + p] = v;
+            }
         }
     }
     if (t < RH_RAYS && ray0 + t < nrays_total) {
@@ -597,8 +683,31 @@ extern "C" void n3dt_launch_ray_head_mfma(const N3dtGeom* g, int bpr, int bs, co
                                           float* depth, float* weight, float* merge_feat, float* rayrec, hipStream_t stream) {
     const long nrays_total = (long)g->batch * g->n_rays;
     const int grid = (int)((nrays_total + RH_RAYS - 1) / RH_RAYS);
-    hipLaunchKernelGGL(ray_head_mfma_kernel, dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail,
-                       merge_feat ? bg_featmap : nullptr, bg_hwc, fg_feat, bg_alpha, depth, weight, merge_feat, rayrec);
+    hipLaunchKernelGGL(ray_head_mfma_kernel<false>, dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail,
+                       merge_feat ? bg_featmap : nullptr, bg_hwc, fg_feat, bg_alpha, depth, weight, merge_feat, rayrec,
+                       (unsigned short*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+}
+
+// the same head with the renderer's 16-bit input map and / or its level-0 RGB planes as outputs (see the kernel)
+extern "C" void n3dt_launch_ray_head_mfma16(const N3dtGeom* g, int bpr, int bs, const float* part, const float* wlocal,
+                                            const float* tail, const float* bg_featmap, int bg_hwc, float* fg_feat, float* bg_alpha,
+                                            float* depth, float* weight, float* merge_feat, void* merge16, int prec16, float* rgb0,
+                                            const float* rgb_w, const float* rgb_b, hipStream_t stream) {
+    const long nrays_total = (long)g->batch * g->n_rays;
+    const int grid = (int)((nrays_total + RH_RAYS - 1) / RH_RAYS);
+    if (fg_feat || merge_feat) {  // the fp32 maps as well (not the inference forward's call): they come from the plain form
+        hipLaunchKernelGGL(ray_head_mfma_kernel<false>, dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail,
+                           merge_feat ? bg_featmap : nullptr, bg_hwc, fg_feat, (float*)nullptr, (float*)nullptr, (float*)nullptr, merge_feat,
+                           (float*)nullptr, (unsigned short*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+    }
+    if (prec16 == N3DT_BF16)
+        hipLaunchKernelGGL((ray_head_mfma_kernel<true, N3DT_BF16>), dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail, bg_featmap,
+                           bg_hwc, (float*)nullptr, bg_alpha, depth, weight, (float*)nullptr, (float*)nullptr,
+                           reinterpret_cast<unsigned short*>(merge16), rgb0, rgb_w, rgb_b);
+    else
+        hipLaunchKernelGGL((ray_head_mfma_kernel<true, N3DT_F16>), dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail, bg_featmap,
+                           bg_hwc, (float*)nullptr, bg_alpha, depth, weight, (float*)nullptr, (float*)nullptr,
+                           reinterpret_cast<unsigned short*>(merge16), rgb0, rgb_w, rgb_b);
 }
 
 extern "C" void n3dt_launch_ray_head(const N3dtGeom* g, int bpr, int bs, const float* part, const float* wlocal,
@@ -618,8 +727,9 @@ extern "C" void n3dt_launch_ray_head_rec(const N3dtGeom* g, int bpr, int bs, con
     //  render modes -- the FMA form took 41 us for 8 192 rays, 1 536 FMAs per thread)
     const long nrays_total = (long)g->batch * g->n_rays;
     const int grid = (int)((nrays_total + RH_RAYS - 1) / RH_RAYS);
-    hipLaunchKernelGGL(ray_head_mfma_kernel, dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail,
-                       merge_feat ? bg_featmap : nullptr, 0, fg_feat, bg_alpha, depth, weight, merge_feat, rayrec);
+    hipLaunchKernelGGL(ray_head_mfma_kernel<false>, dim3(grid), dim3(256), 0, stream, *g, bpr, bs, part, wlocal, tail,
+                       merge_feat ? bg_featmap : nullptr, 0, fg_feat, bg_alpha, depth, weight, merge_feat, rayrec,
+                       (unsigned short*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
 }
 
 // [C][n] -> [n][C]

@@ -252,6 +252,17 @@ static NrCarve nr_carve(const N3dtGeom* g, int nb) {
 
 extern "C" size_t n3dt_nr_workspace_floats(const N3dtGeom* g, int nb) { return nr_carve(g, nb).total; }
 
+extern "C" void n3dt_launch_feat_to_rgb0(int nb, int n_pix, const float* featmap, const float* w, const float* b, float* rgb0, hipStream_t s) {
+    const size_t npix = (size_t)nb * n_pix;
+    hipLaunchKernelGGL(to_rgb16_kernel, dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 3 * 256 * sizeof(float), s, nb, n_pix, 256, featmap, w, b,
+                       rgb0);
+}
+
+extern "C" void n3dt_launch_neural_render16(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const void* featmap16,
+                                            const float* rgb0, float* img, float* ws, hipStream_t s) {
+    n3dt_launch_neural_render_x16_in16(g, nb, precision, p, featmap16, rgb0, img, ws, nr_carve(g, nb).total, s);
+}
+
 // pack_mode: 0 = pack the fused blocks' weights into the workspace tail and render; 1 = render with the stream a previous call
 // left there; 2 = pack only.  The fp32 path reads the raw parameters (nothing to pack).
 extern "C" void n3dt_launch_neural_render(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p,

@@ -559,8 +559,10 @@ static inline bool nrf_enabled() {
 }
 
 template <int PREC>
-static void run_x16(const N3dtGeom* g, int nb, const N3dtRenderParams* p, const float* featmap, float* img, float* ws, size_t ws_floats,
-                    const int pack_mode, hipStream_t s) {
+static void run_x16(const N3dtGeom* g, int nb, const N3dtRenderParams* p, const void* featmap, float* img, float* ws, size_t ws_floats,
+                    const int pack_mode, hipStream_t s, const float* rgb0 = nullptr) {
+    // rgb0 != nullptr: `featmap` is already the 16-bit map and rgb0 [nb][3][fs*fs] its level-0 projection (both from the ray
+    // head, n3dt_render_fwd16): no projection pass, and the first block reads 16-bit rows
     const int C = g->feat_nc, fs = g->featmap_size, nblk = g->n_blocks;
     // carve (in 16-bit elements for the maps): t1 | ps | hid | netA | netB, then planar fp32 rgbA | rgbB
     size_t e_t1 = 0, e_ps = 0, e_hid = 0, e_net = 0;
@@ -593,21 +595,23 @@ static void run_x16(const N3dtGeom* g, int nb, const N3dtRenderParams* p, const 
         }
         return;
     }
-    {
+    if (!rgb0) {
         const size_t npix = (size_t)nb * h * h;
+        const float* f32map = reinterpret_cast<const float*>(featmap);
         if (C % 64 == 0)
-            hipLaunchKernelGGL(to_rgb16_kernel, dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 3 * C * sizeof(float), s, nb, h * h, C, featmap,
+            hipLaunchKernelGGL(to_rgb16_kernel, dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 3 * C * sizeof(float), s, nb, h * h, C, f32map,
                                p->to_rgb_w[0], p->to_rgb_b[0], rgbB);
         else
-            hipLaunchKernelGGL(to_rgb_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 3 * C * sizeof(float), s, nb, h * h, C, featmap,
+            hipLaunchKernelGGL(to_rgb_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 3 * C * sizeof(float), s, nb, h * h, C, f32map,
                                p->to_rgb_w[0], p->to_rgb_b[0], (const float*)nullptr, rgbB, 0);
     }
     // the RGB pyramid: `lo` holds it at the current block's INPUT resolution; a fused block upsamples it on the fly, the
-    // layered fallback needs the stand-alone rgb_up pass first
-    float* lo = rgbB;
+    // layered fallback needs the stand-alone rgb_up pass first.  (A caller's rgb0 is only ever read: the first level writes
+    // into the workspace, and from then on the two workspace planes alternate as before.)
+    const float* lo = rgb0 ? rgb0 : rgbB;
     float* spare = rgbA;
     const void* x = featmap;
-    bool x16 = false;
+    bool x16 = rgb0 != nullptr;
     unsigned short* cur = netA;
     unsigned short* oth = netB;
     for (int i = 0; i < nblk; ++i) {
@@ -644,16 +648,18 @@ static void run_x16(const N3dtGeom* g, int nb, const N3dtRenderParams* p, const 
         const size_t nthr = (size_t)M4 * (co / 8);
         if (fused) {
             launch_blur_q<PREC>(nb, h / 2, h / 2, co, hid, p->feat_b[i], last ? (unsigned short*)nullptr : cur, p->to_rgb_w[i + 1],
-                                p->to_rgb_b[i + 1], (const float*)lo, last ? img : spare, last ? 1 : 0, (float*)nullptr, s);
-            float* t2 = lo;
+                                p->to_rgb_b[i + 1], lo, last ? img : spare, last ? 1 : 0, (float*)nullptr, s);
+            float* t2 = lo == rgb0 ? rgbB : const_cast<float*>(lo);
             lo = spare;
             spare = t2;
         } else {
+            float* low = lo == rgb0 ? rgbB : const_cast<float*>(lo);  // this level's pyramid output, in the workspace
             const size_t nout = (size_t)nb * 3 * h * h;  // h is the OUTPUT resolution here
             hipLaunchKernelGGL(rgb_up_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, nb * 3, h / 2, h / 2, lo, spare);
             hipLaunchKernelGGL(blur_act_rgb_kernel<PREC>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 4 * co * sizeof(float), s, nb, h, h, co,
                                hid, p->feat_b[i], last ? (unsigned short*)nullptr : cur, p->to_rgb_w[i + 1], p->to_rgb_b[i + 1], (const float*)spare,
-                               last ? img : lo, last ? 1 : 0, (h == w_of(h)) ? hg_log2(h) : -1);
+                               last ? img : low, last ? 1 : 0, (h == w_of(h)) ? hg_log2(h) : -1);
+            lo = low;
         }
         x = cur;
         x16 = true;
@@ -748,6 +754,12 @@ static void n3dt_launch_neural_render_x16(const N3dtGeom* g, int nb, int precisi
                                               float* img, float* ws, size_t ws_floats, const int pack_mode, hipStream_t s) {
     if (precision == N3DT_BF16) run_x16<N3DT_BF16>(g, nb, p, featmap, img, ws, ws_floats, pack_mode, s);
     else run_x16<N3DT_F16>(g, nb, p, featmap, img, ws, ws_floats, pack_mode, s);
+}
+// the 16-bit input form (packed block weights already in the workspace tail)
+static void n3dt_launch_neural_render_x16_in16(const N3dtGeom* g, int nb, int precision, const N3dtRenderParams* p, const void* featmap16,
+                                               const float* rgb0, float* img, float* ws, size_t ws_floats, hipStream_t s) {
+    if (precision == N3DT_BF16) run_x16<N3DT_BF16>(g, nb, p, featmap16, img, ws, ws_floats, 1, s, rgb0);
+    else run_x16<N3DT_F16>(g, nb, p, featmap16, img, ws, ws_floats, 1, s, rgb0);
 }
 
 // The pixel-major 1x1-conv GEMM of this file for the training path's forward (bf16 maps):

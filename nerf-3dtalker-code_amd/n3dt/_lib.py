@@ -89,6 +89,7 @@ EXPORTS = [
     "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd",
     "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
     "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
+    "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
 ]
 
 STAGE_MAX = 12
@@ -125,12 +126,18 @@ def lib():
     L.n3dt_render_workspace_bytes.argtypes = [ctypes.POINTER(Geom), ci]
     L.n3dt_render_fwd.restype = ci
     L.n3dt_render_fwd.argtypes = [ctypes.POINTER(Geom), ci, vp, ctypes.POINTER(MlpParams)] + [vp] * 15 + [vp, sz, vp]
+    L.n3dt_render_fwd16.restype = ci
+    L.n3dt_render_fwd16.argtypes = [ctypes.POINTER(Geom), ci, vp, ctypes.POINTER(MlpParams)] + [vp] * 19 + [vp, sz, vp]
     L.n3dt_neural_render_workspace_bytes.restype = sz
     L.n3dt_neural_render_workspace_bytes.argtypes = [ctypes.POINTER(Geom), ci]
     L.n3dt_neural_render_fwd.restype = ci
     L.n3dt_neural_render_fwd.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, sz, vp]
     L.n3dt_neural_render_fwd_reuse.restype = ci
     L.n3dt_neural_render_fwd_reuse.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, sz, vp]
+    L.n3dt_neural_render_fwd16_reuse.restype = ci
+    L.n3dt_neural_render_fwd16_reuse.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, vp, sz, vp]
+    L.n3dt_feat_to_rgb0.restype = ci
+    L.n3dt_feat_to_rgb0.argtypes = [ci, ci, vp, vp, vp, vp, vp]
     L.n3dt_neural_render_pack.restype = ci
     L.n3dt_neural_render_pack.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, sz, vp]
     L.n3dt_chw_to_hwc.restype = ci

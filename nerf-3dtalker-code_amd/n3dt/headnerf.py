@@ -196,20 +196,42 @@ class NeuralRenderer(nn.Module):
             return out
         geom = self._geom(nb)
         if ws is None:
-            # ONE grow-only workspace per (device, stream), sized for the largest batch seen (a caller whose batch varies -- a
-            # last partial batch, validation at 1 next to sweeps at 16 -- must not keep a workspace per size alive).  The
-            # packed block weights sit at an offset that depends on nb; the pack signature carries nb, so a different nb re-packs.
-            dev = featmap_hwc.device
-            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-            need = ops.neural_render_workspace_bytes(geom, nb)
-            ws = self._own_ws.get(key)
-            if ws is None or ws.numel() < need:
-                if ws is not None:
-                    self._packed_sig.pop(ws.data_ptr(), None)
-                ws = self._own_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-                self._packed_sig.pop(ws.data_ptr(), None)  # (a fresh allocation may sit where a released one sat)
+            ws = self._own_workspace(geom, nb, featmap_hwc.device)
         rp = self.ensure_packed(nb, precision, ws)
         return ops.neural_render_fwd(geom, nb, rp, featmap_hwc, _lib.PRECISIONS[precision], img=img, ws=ws, reuse_packed=True)
+
+    def _own_workspace(self, geom, nb, dev):
+        # ONE grow-only workspace per (device, stream), sized for the largest batch seen (a caller whose batch varies -- a
+        # last partial batch, validation at 1 next to sweeps at 16 -- must not keep a workspace per size alive).  The
+        # packed block weights sit at an offset that depends on nb; the pack signature carries nb, so a different nb re-packs.
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        need = ops.neural_render_workspace_bytes(geom, nb)
+        ws = self._own_ws.get(key)
+        if ws is None or ws.numel() < need:
+            if ws is not None:
+                self._packed_sig.pop(ws.data_ptr(), None)
+            ws = self._own_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._packed_sig.pop(ws.data_ptr(), None)  # (a fresh allocation may sit where a released one sat)
+        return ws
+
+    def render_maps16(self, maps16, rgb0, precision, img=None, ws=None):
+        """The 16-bit modes' renderer on what the ray head leaves behind (ops.render_fwd's merge16_out / rgb0_out): maps16
+        [nb, fs, fs, C] in the mode's map type, rgb0 [nb, 3, fs*fs] their level-0 RGB projection -> [nb, 3, P, P].  The first
+        block reads 16-bit rows and no projection pass runs; the rest is render_hwc's arithmetic."""
+        nb = maps16.shape[0]
+        side = self.featmap_size << self.n_blocks
+        cap = getattr(self, "_max_maps_per_call", None) or max(1, ((1 << 31) - 1) // (side * side * 32))
+        if nb > cap:
+            assert ws is None, "a caller-owned workspace is sized for one call"
+            out = img if img is not None else torch.empty(nb, 3, side, side, dtype=torch.float32, device=maps16.device)
+            for i in range(0, nb, cap):
+                self.render_maps16(maps16[i:i + cap], rgb0[i:i + cap], precision, img=out[i:i + cap])
+            return out
+        geom = self._geom(nb)
+        if ws is None:
+            ws = self._own_workspace(geom, nb, maps16.device)
+        rp = self.ensure_packed(nb, precision, ws)
+        return ops.neural_render_fwd16(geom, nb, rp, maps16, rgb0, _lib.PRECISIONS[precision], img=img, ws=ws)
 
     def forward(self, x):
         """x: [nb, C, fs, fs] like the reference module."""
@@ -547,6 +569,8 @@ class HeadNeRFNet(nn.Module):
         self._graphs = {}
         self._bg_cache = None
         self._maps_cache = {}
+        self._bg_img_cache = {}  # (device, precision, geometry) -> (parameter versions, bg_img [1, 3, P, P]): see _bg_image
+        self.bg_renders = 0      # background renders run so far (cache misses of _bg_image)
         self._w10c_cache = {}
         # a (strict or not) load_state_dict replaces every weight: drop the packed copies
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.invalidate_packed())
@@ -579,8 +603,25 @@ class HeadNeRFNet(nn.Module):
             dst = c[1] if c is not None and c[1].device == bg.device else torch.empty(fs * fs, C, dtype=torch.float32, device=bg.device)
             ops.chw_to_hwc(bg.detach().view(C, fs * fs), C, fs * fs, dst)
             self._bg_cache = c = (ver, dst)
-            self._bg_serial = getattr(self, "_bg_serial", 0) + 1  # moves with every re-transpose (what the batch buffers compare)
         return c[1]
+
+    def _bg_image(self, dev):
+        """bg_img [1, 3, P, P]: the 2-D renderer's image of neural_render.bg_featmap alone.  With frozen weights -- inference --
+        it has the same bits in every forward, so it is rendered once per parameter version (the renderer's parameters' and
+        bg_featmap's version counters, voided by invalidate_packed() and by every training-mode or gradient-carrying forward,
+        like the packed weights) into a buffer whose address does not change (recorded graphs copy from it)."""
+        nr = self.neural_render
+        bg = nr.bg_featmap
+        key = (dev.index, self.precision, self.featmap_size, self.pred_img_size, self.featmap_nc)
+        ver = (nr._param_sig(), bg.data_ptr(), bg._version)
+        hit = self._bg_img_cache.get(key)
+        if hit is None or hit[0] != ver:
+            fs, C, P = self.featmap_size, self.featmap_nc, self.pred_img_size
+            buf = hit[1] if hit is not None else torch.empty(1, 3, P, P, dtype=torch.float32, device=dev)
+            nr.render_hwc(self._bg_hwc().view(1, fs, fs, C), self.precision, img=buf)  # the fp32-input form, nb = 1
+            self.bg_renders += 1
+            hit = self._bg_img_cache[key] = (ver, buf)
+        return hit[1]
 
     def invalidate_packed(self):
         """Forget the packed (MFMA-ordered, 16-bit) copies of the MLP weights.  They are rebuilt on the next call.
@@ -596,11 +637,9 @@ class HeadNeRFNet(nn.Module):
             self._bg_cache = (None, self._bg_cache[1])
         for k, (ver, buf) in list(self._w10c_cache.items()):
             self._w10c_cache[k] = (None, buf)
-        for k, ent in list(self._maps_cache.items()):
-            self._maps_cache[k] = (None,) + tuple(ent[1:])
+        for k, (ver, buf) in list(self._bg_img_cache.items()):
+            self._bg_img_cache[k] = (None, buf)
         self.neural_render.invalidate_packed()
-        for e in self._graphs.values():
-            e["bg_ver"] = None
 
     def _build_info(self, opt):
         self.num_sample_coarse = opt.num_sample_coarse
@@ -707,7 +746,7 @@ class HeadNeRFNet(nn.Module):
 
     def render_features(self, batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats,
                         t_rand=None, want_depth=False, want_weight=False, want_merge=True, precision=None, merge_out=None,
-                        z_planes=None, want_fg=True, weight_out=None, workspace=None):
+                        z_planes=None, want_fg=True, weight_out=None, workspace=None, merge16_out=None, rgb0_out=None, rgb0_wb=None):
         """Rays -> composited feature map (seams a1..a7).  Outputs are ray-major [B, N_r, C].
         z_planes [B, N_r, N+1] (from fine_planes()): the hierarchical pass -- those planes, the fine network."""
         prec = _lib.PRECISIONS[precision or self.precision]
@@ -732,7 +771,8 @@ class HeadNeRFNet(nn.Module):
                              None if t_rand is None else ops._f32c(t_rand),
                              self._bg_hwc() if want_merge else None,  # ray-major, cached per parameter version
                              want_depth=want_depth, want_weight=want_weight, want_merge=want_merge, merge_out=merge_out,
-                             want_fg=want_fg, weight_out=weight_out, ws=workspace, ray_bias=ray_bias)
+                             want_fg=want_fg, weight_out=weight_out, ws=workspace, ray_bias=ray_bias,
+                             merge16_out=merge16_out, rgb0_out=rgb0_out, rgb0_wb=rgb0_wb)
         return out
 
     def fine_planes(self, batch_xy, coarse_weight, batch_Tvecs, t_rand=None, fine_u=None, out=None):
@@ -759,6 +799,11 @@ class HeadNeRFNet(nn.Module):
             any(p.requires_grad for p in self.parameters()) or
             any(torch.is_tensor(t) and t.requires_grad for t in (audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs,
                                                                      batch_inv_inmats, batch_xy)))
+        if needs_grad or for_train:
+            # training: the weights are about to move, possibly without their version counters (fused Adam) -- the cached
+            # background image does not outlive such a call
+            for k, (ver, buf) in list(self._bg_img_cache.items()):
+                self._bg_img_cache[k] = (None, buf)
         if needs_grad:
             return self._forward_train(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand,
                                        for_train=for_train, fine_u=fine_u)
@@ -766,29 +811,31 @@ class HeadNeRFNet(nn.Module):
             return self._forward_graph(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats)
         n_pass = 2 if self.hier_sampling else 1
         nb = n_pass * batch_size
-        maps = self._maps_with_background(nb, batch_xy.device)
+        scratch = self._infer_scratch(nb, batch_xy.device)
         if self.hier_sampling and for_train and fine_u is None:  # the reference's torch.rand(num_temp, NFsample) (NetWorks/utils.py:227)
             fine_u = torch.rand(batch_size * n_r, self.num_sample_fine + 1, device=batch_xy.device, dtype=torch.float32)
-        imgs = self._infer_launch(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand, fine_u, maps,
-                                  bufs={"bg_in_maps": True})
+        imgs = self._infer_launch(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand, fine_u, scratch,
+                                  bufs={"bg_img": self._bg_image(batch_xy.device)})
         return self._result(imgs, batch_size, nb)
 
-    def _maps_with_background(self, nb, dev):
-        """The renderer's input batch [nb + 1, fs, fs, C] (merged maps, then the background map) as scratch kept per (device,
-        stream), grow-only: the background slot is filled once per parameter version and batch size instead of by a copy
-        kernel in every forward (it is 4 us of a 0.64 ms one-head step).  The merged slots are overwritten by every call; the
-        images returned to the caller are separate."""
-        bg = self._bg_hwc()
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        ent = self._maps_cache.get(key)
+    def _alloc_scratch(self, nb, dev):
+        """What crosses from the ray head to the 2-D renderer for nb merged maps.  16-bit modes: the maps in the renderer's
+        map type (bf16; f16 for fp16 and bf16x3) and their level-0 RGB planes; fp32: the fp32 maps."""
         fs, C = self.featmap_size, self.featmap_nc
-        if ent is None or ent[1].shape[0] < nb + 1:
-            ent = (None, torch.empty(nb + 1, fs, fs, C, dtype=torch.float32, device=dev))
-        tag = (self._bg_serial, nb)
-        if ent[0] != tag:
-            ent[1][nb].view(fs * fs, C).copy_(bg)
-            self._maps_cache[key] = ent = (tag, ent[1])
-        return ent[1][:nb + 1]
+        prec = _lib.PRECISIONS[self.precision]
+        if prec == _lib.F32:
+            return {"maps": torch.empty(nb, fs, fs, C, dtype=torch.float32, device=dev)}
+        return {"maps16": torch.empty(nb, fs, fs, C, dtype=torch.bfloat16 if prec == _lib.BF16 else torch.float16, device=dev),
+                "rgb0": torch.empty(nb, 3, fs * fs, dtype=torch.float32, device=dev)}
+
+    def _infer_scratch(self, nb, dev):
+        """_alloc_scratch kept per (device, stream, precision), grow-only.  Overwritten by every call; the images returned to
+        the caller are separate."""
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, self.precision)
+        ent = self._maps_cache.get(key)
+        if ent is None or next(iter(ent.values())).shape[0] < nb:
+            ent = self._maps_cache[key] = self._alloc_scratch(nb, dev)
+        return {k: v[:nb] for k, v in ent.items()}
 
     def _result(self, imgs, batch_size, nb):
         res = {"coarse_dict": {"merge_img": imgs[:batch_size], "bg_img": imgs[nb:]}}
@@ -797,26 +844,40 @@ class HeadNeRFNet(nn.Module):
         return res
 
     def _infer_launch(self, batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats, t_rand, fine_u,
-                      maps, imgs=None, bufs=None):
-        """Enqueue one inference forward.  The merged maps (coarse, then fine) and the background map go through the 2-D
-        renderer in one call; the render kernel writes its merged maps straight into that batch.  With `imgs` and `bufs`
-        (caller-owned workspaces / intermediates) nothing is allocated, so the sequence can be recorded into a hipGraph."""
+                      scratch, imgs=None, bufs=None):
+        """Enqueue one inference forward.  The merged maps (coarse, then fine) go through the 2-D renderer in one call; in the
+        16-bit modes the ray head leaves them behind as the renderer's 16-bit rows together with their level-0 RGB planes
+        (no fp32 map is written), in fp32 as fp32 maps.  The background image is not rendered here: bufs["bg_img"] (see
+        _bg_image) is copied into the last slot of the call's own output.  With `imgs` and the workspaces in `bufs` (caller-owned)
+        nothing is allocated, so the sequence can be recorded into a hipGraph."""
         batch_size, _, n_r = batch_xy.size()
-        fs, C = self.featmap_size, self.featmap_nc
+        fs, C, P = self.featmap_size, self.featmap_nc, self.pred_img_size
         nb = (2 if self.hier_sampling else 1) * batch_size
         bufs = bufs or {}
+        nr = self.neural_render
+        x16 = "maps16" in scratch
+        if x16:
+            rgb0_wb = (nr.feat_2_rgb_list[0].w2d().detach().contiguous(), nr.feat_2_rgb_list[0].bias.detach().contiguous())
+
+        def outs(lo, hi):
+            if x16:
+                return {"merge16_out": scratch["maps16"][lo:hi].view(hi - lo, fs * fs, C), "rgb0_out": scratch["rgb0"][lo:hi], "rgb0_wb": rgb0_wb}
+            return {"merge_out": scratch["maps"][lo:hi].view(hi - lo, fs * fs, C)}
         coarse = self.render_features(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats,
                                       t_rand=t_rand, want_weight=self.hier_sampling, want_merge=True, want_fg=False,
-                                      merge_out=maps[:batch_size].view(batch_size, fs * fs, C), weight_out=bufs.get("weight"),
-                                      workspace=bufs.get("render_ws"))
+                                      weight_out=bufs.get("weight"), workspace=bufs.get("render_ws"), **outs(0, batch_size))
         if self.hier_sampling:
             planes = self.fine_planes(batch_xy, coarse["weight"], batch_Tvecs, t_rand=t_rand, fine_u=fine_u, out=bufs.get("planes"))
             self.render_features(batch_xy, audiostyle, shape_code, appea_code, batch_Rmats, batch_Tvecs, batch_inv_inmats,
-                                 z_planes=planes, want_merge=True, want_fg=False,
-                                 merge_out=maps[batch_size:nb].view(batch_size, fs * fs, C), workspace=bufs.get("fine_ws"))
-        if "nr_ws" not in bufs and not bufs.get("bg_in_maps"):  # (a recorded graph keeps the background map in its static batch: see _forward_graph)
-            maps[nb].view(fs * fs, C).copy_(self._bg_hwc())
-        return self.neural_render.render_hwc(maps, self.precision, img=imgs, ws=bufs.get("nr_ws"))
+                                 z_planes=planes, want_merge=True, want_fg=False, workspace=bufs.get("fine_ws"), **outs(batch_size, nb))
+        if imgs is None:
+            imgs = torch.empty(nb + 1, 3, P, P, dtype=torch.float32, device=batch_xy.device)
+        if x16:
+            nr.render_maps16(scratch["maps16"][:nb], scratch["rgb0"][:nb], self.precision, img=imgs[:nb], ws=bufs.get("nr_ws"))
+        else:
+            nr.render_hwc(scratch["maps"][:nb], self.precision, img=imgs[:nb], ws=bufs.get("nr_ws"))
+        imgs[nb:].copy_(bufs["bg_img"])  # one device copy on the caller's stream: bg_img stays a slice of the call's own output
+        return imgs
 
     # ---- hipGraph replay of the inference forward ---------------------------------------------------------------
     def _graph_usable(self, for_train, t_rand, batch_xy):
@@ -852,7 +913,7 @@ class HeadNeRFNet(nn.Module):
         for fine in ((False, True) if self.hier_sampling else (False,)):
             params, ws, bs = self._mlp_params(fine=fine)
             if self._packed(e["geom"], _lib.PRECISIONS[self.precision], params, ws, bs).data_ptr() != e["packed"][fine] or \
-                    self._bg_hwc().data_ptr() != e["bg_ptr"]:
+                    self._bg_hwc().data_ptr() != e["bg_ptr"] or self._bg_image(dev).data_ptr() != e["bufs"]["bg_img"].data_ptr():
                 self._drop_graph(self._graphs.pop(key))
                 e = self._graphs[key] = self._record_graph(B, n_r, dev, sig, xy, small)
                 break
@@ -863,15 +924,10 @@ class HeadNeRFNet(nn.Module):
         return self._result(imgs, B, e["nb"])
 
     def _refresh_graph_constants(self, e):
-        """What a replay reads but does not compute: the background map's slot of the renderer batch and the renderer's packed
-        block weights, refreshed (on the caller's stream, ahead of the replay) when their parameters' versions moved."""
-        bg = self.neural_render.bg_featmap
-        ver = (bg.data_ptr(), bg._version)
-        if e.get("bg_ver") != ver:
-            fs, C = self.featmap_size, self.featmap_nc
-            e["maps"][e["nb"]].view(fs * fs, C).copy_(self._bg_hwc())
-            e["bg_ver"] = ver
-        self.neural_render.ensure_packed(e["nb"] + 1, self.precision, e["bufs"]["nr_ws"])
+        """What a replay reads but does not compute: the cached background image and the renderer's packed block weights,
+        refreshed in place (on the caller's stream, ahead of the replay) when their parameters' versions moved."""
+        self._bg_image(e["imgs"].device)
+        self.neural_render.ensure_packed(e["nb"], self.precision, e["bufs"]["nr_ws"])
 
     def _record_graph(self, B, n_r, dev, sig, xy, small):
         fs, C, P = self.featmap_size, self.featmap_nc, self.pred_img_size
@@ -879,10 +935,10 @@ class HeadNeRFNet(nn.Module):
         nb = (2 if self.hier_sampling else 1) * B
         f32 = dict(dtype=torch.float32, device=dev)
         e = {"sig": sig, "nb": nb, "xy": torch.empty(B, 2, n_r, **f32), "small": [torch.empty_like(t) for t in small],
-             "maps": torch.empty(nb + 1, fs, fs, C, **f32), "imgs": torch.empty(nb + 1, 3, P, P, **f32)}
+             "scratch": self._alloc_scratch(nb, dev), "imgs": torch.empty(nb + 1, 3, P, P, **f32)}
         geom = e["geom"] = self._geom(B, n_r, e["xy"])
         bufs = {"render_ws": torch.empty(ops.render_workspace_bytes(geom, prec), dtype=torch.uint8, device=dev),
-                "nr_ws": torch.empty(ops.neural_render_workspace_bytes(self.neural_render._geom(nb + 1), nb + 1), dtype=torch.uint8, device=dev)}
+                "nr_ws": torch.empty(ops.neural_render_workspace_bytes(self.neural_render._geom(nb), nb), dtype=torch.uint8, device=dev)}
         # a freshly allocated workspace may sit where a released one sat: whatever was recorded for that address is void
         self.neural_render._packed_sig.pop(bufs["nr_ws"].data_ptr(), None)
         packed = {}
@@ -897,6 +953,7 @@ class HeadNeRFNet(nn.Module):
             packed[fine] = self._packed(geom, prec, params, ws, bs).data_ptr()  # packs now, on the caller's stream
         e["packed"], e["bufs"] = packed, bufs
         e["bg_ptr"] = self._bg_hwc().data_ptr()
+        bufs["bg_img"] = self._bg_image(dev)  # (rendered now if need be, on the caller's stream; the graph only copies it)
         self._refresh_graph_constants(e)
         R, T, Kinv, shape, appea = e["small"][:5]
         audio = e["small"][5] if self.audio_dim > 0 else None
@@ -906,7 +963,7 @@ class HeadNeRFNet(nn.Module):
         with torch.cuda.stream(side):
             ops.graph_begin(side)
             try:
-                self._infer_launch(e["xy"], audio, shape, appea, R, T, Kinv, None, None, e["maps"], imgs=e["imgs"], bufs=bufs)
+                self._infer_launch(e["xy"], audio, shape, appea, R, T, Kinv, None, None, e["scratch"], imgs=e["imgs"], bufs=bufs)
             except BaseException:
                 try:  # end the capture so the stream is usable again, and let the ORIGINAL error through
                     ops.graph_destroy(ops.graph_end(side))

@@ -104,25 +104,43 @@ def render_workspace_bytes(geom, precision):
 
 
 def render_fwd(geom, precision, packed, params, xy, R, T, Kinv, shape, appea, audio, t_rand, bg_featmap,
-               want_depth=False, want_weight=False, want_merge=True, merge_out=None, want_fg=True, weight_out=None, ws=None, ray_bias=None):
+               want_depth=False, want_weight=False, want_merge=True, merge_out=None, want_fg=True, weight_out=None, ws=None, ray_bias=None,
+               merge16_out=None, rgb0_out=None, rgb0_wb=None):
     """a1..a7 fused.  Returns dict(fg_feat [B,Nr,C]?, bg_alpha [B,Nr]?, depth?, weight?, merge_feat?).
-    With merge_out / weight_out / ws given (and want_fg, want_depth off) the call allocates nothing: hipGraph-capturable."""
+    With merge_out / weight_out / ws given (and want_fg, want_depth off) the call allocates nothing: hipGraph-capturable.
+    merge16_out [B,Nr,C] (torch.bfloat16 / float16, the 2-D renderer's map type) and rgb0_out [B,3,Nr] with rgb0_wb =
+    (feat_2_rgb[0] weight [3,C], bias [3]): the ray head's 16-bit map and level-0 RGB outputs (n3dt_render_fwd16); the fp32
+    merged map is then written only when merge_out is given."""
     dev = xy.device
     B, Nr, Ns, C = geom.batch, geom.n_rays, geom.n_samples, geom.feat_nc
     assert want_fg or want_merge
+    map16 = merge16_out is not None or rgb0_out is not None
+    if map16:
+        assert want_merge and (merge16_out is None or (merge16_out.is_contiguous() and merge16_out.element_size() == 2))
+        assert rgb0_out is None or (rgb0_wb is not None and rgb0_out.is_contiguous() and rgb0_out.dtype == torch.float32)
     out = {
         "fg_feat": torch.empty(B, Nr, C, dtype=torch.float32, device=dev) if want_fg else None,
         "bg_alpha": torch.empty(B, Nr, dtype=torch.float32, device=dev) if want_fg else None,
         "depth": torch.empty(B, Nr, dtype=torch.float32, device=dev) if want_depth else None,
         "weight": (weight_out if weight_out is not None else torch.empty(B, Nr, Ns, dtype=torch.float32, device=dev))
         if want_weight else None,
-        "merge_feat": (merge_out if merge_out is not None else torch.empty(B, Nr, C, dtype=torch.float32, device=dev))
+        "merge_feat": (merge_out if merge_out is not None else None if map16 else torch.empty(B, Nr, C, dtype=torch.float32, device=dev))
         if want_merge else None,
     }
     ws_bytes = render_workspace_bytes(geom, precision)
     if ws is None:
         ws = WORKSPACE.get("render", ws_bytes, dev)
     assert ws.numel() >= ws_bytes
+    if map16:
+        out["merge_feat16"], out["rgb0"] = merge16_out, rgb0_out
+        rc = lib().n3dt_render_fwd16(
+            ctypes.byref(geom), precision, _ptr(packed), ctypes.byref(params), _ptr(xy), _ptr(R), _ptr(T), _ptr(Kinv),
+            _ptr(shape), _ptr(appea), _ptr(audio), _ptr(t_rand), _ptr(bg_featmap), _ptr(ray_bias),
+            _ptr(out["fg_feat"]), _ptr(out["bg_alpha"]), _ptr(out["depth"]), _ptr(out["weight"]), _ptr(out["merge_feat"]),
+            _ptr(merge16_out), _ptr(rgb0_out), _ptr(rgb0_wb[0]) if rgb0_wb else None, _ptr(rgb0_wb[1]) if rgb0_wb else None,
+            _ptr(ws), ws_bytes, _stream())
+        check(rc, "n3dt_render_fwd16")
+        return out
     rc = lib().n3dt_render_fwd(
         ctypes.byref(geom), precision, _ptr(packed), ctypes.byref(params), _ptr(xy), _ptr(R), _ptr(T), _ptr(Kinv),
         _ptr(shape), _ptr(appea), _ptr(audio), _ptr(t_rand), _ptr(bg_featmap) if want_merge else None, _ptr(ray_bias),
@@ -254,6 +272,28 @@ def neural_render_fwd(geom, nb, rparams, featmap, precision=0, img=None, ws=None
     fn = lib().n3dt_neural_render_fwd_reuse if reuse_packed else lib().n3dt_neural_render_fwd
     check(fn(ctypes.byref(geom), nb, precision, ctypes.byref(rparams), _ptr(featmap), _ptr(img), _ptr(ws), ws_bytes, _stream()),
           "n3dt_neural_render_fwd")
+    return img
+
+
+def feat_to_rgb0(featmap, w, b):
+    """featmap [nb, n_pix, 256] fp32 -> [nb, 3, n_pix]: the renderer's stand-alone level-0 RGB projection (n3dt_feat_to_rgb0)."""
+    nb, n_pix, C = featmap.shape
+    assert C == 256 and featmap.is_contiguous() and featmap.dtype == torch.float32
+    out = torch.empty(nb, 3, n_pix, dtype=torch.float32, device=featmap.device)
+    check(lib().n3dt_feat_to_rgb0(nb, n_pix, _ptr(featmap), _ptr(w), _ptr(b), _ptr(out), _stream()), "n3dt_feat_to_rgb0")
+    return out
+
+
+def neural_render_fwd16(geom, nb, rparams, featmap16, rgb0, precision, img=None, ws=None):
+    """The same renderer on the ray head's outputs (render_fwd's merge16_out / rgb0_out): featmap16 [nb, fs, fs, C] 16-bit,
+    rgb0 [nb, 3, fs*fs].  `ws` must hold the packed block weights (neural_render_pack)."""
+    P = geom.featmap_size << geom.n_blocks
+    if img is None:
+        img = torch.empty(nb, 3, P, P, dtype=torch.float32, device=featmap16.device)
+    ws_bytes = neural_render_workspace_bytes(geom, nb)
+    assert ws is not None and ws.numel() >= ws_bytes and featmap16.element_size() == 2 and featmap16.is_contiguous()
+    check(lib().n3dt_neural_render_fwd16_reuse(ctypes.byref(geom), nb, precision, ctypes.byref(rparams), _ptr(featmap16), _ptr(rgb0), _ptr(img),
+                                               _ptr(ws), ws_bytes, _stream()), "n3dt_neural_render_fwd16_reuse")
     return img
 
 
