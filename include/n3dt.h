@@ -430,6 +430,9 @@ typedef struct N3dtAdamGroup {
 size_t n3dt_flat_adam_record_bytes(int which);
 int n3dt_flat_adam_step(const void* tensor_table, const void* chunk_table, int n_chunks, const void* group_table, int n_groups,
                         void* step_counter, void* stream);
+/* the guarded step (global-norm clipping, non-finite step skipping, both decided on the device): N3dtAdamGuard and its two
+ * entry points, on the same tables */
+#include "n3dt_flat_adam_guard.h"
 
 /* [C, N_r] (NCHW parameter) -> [N_r, C]; used to feed bg_featmap to the renderer */
 int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream);

@@ -6,7 +6,7 @@
 //   m  = b1 m + (1 - b1) g
 //   v  = b2 v + (1 - b2) g g
 //   p += -(lr / (1 - b1^t)) * (m / (sqrt(v) / sqrt(1 - b2^t) + eps))
-// Non-finite gradients propagate; nothing is skipped.
+// Non-finite gradients propagate; nothing is skipped -- unless the step is GUARDED (below).
 //
 // Work list: a chunk table in device memory (tensor index, start element, length), one chunk at a time per workgroup,
 // grid-stride; no chunk crosses a tensor.  A tensor record holds the four pointers, the group index and an "active" flag
@@ -28,6 +28,23 @@
 // part in the vector body only when they are congruent to the gradient modulo 16 bytes (they are: three arenas of one
 // layout), else the chunk is walked element by element; the PARAMETER (never re-homed: its storage offset is any multiple
 // of 4 bytes) falls back on its own to four 4-byte accesses per vector when it is not congruent.
+//
+// The guarded step (include/n3dt_flat_adam_guard.h, n3dt_flat_adam_guarded_step): global-norm clipping and non-finite step
+// skipping decided on the device, two launches, nothing for the host to do.
+//   flat_grad_norm_kernel  walks the same chunk table with the same head / 16-byte body / tail split, over the GRADIENT only
+//       (4 more bytes read per element).  Every thread squares and adds in double (an fp32 square is exact in double, and
+//       |g| ~ 1e30 stays finite), the workgroup adds its 256 values in a fixed order and ONE double per chunk goes to
+//       partials[chunk] with a plain vector store (0 for a chunk of an inactive tensor).  No floating-point atomics: the
+//       last workgroup to finish -- found with the same completion-counter idiom as below, on guard->norm_done -- adds
+//       partials[0..n_chunks) in INDEX order (one thread, the LDS reads running a batch ahead of the add chain), so the norm
+//       depends neither on the grid nor on scheduling.  It covers exactly the chunks the step kernel updates.  It writes
+//       grad_norm, clip_coef and the skip flag into the guard record and re-arms its counter.  No workgroup waits for
+//       another one.
+//   flat_adam_kernel<true>  reads clip_coef and the skip flag in its prologue.  On skip every workgroup goes straight to the
+//       completion counter and the last one adds 1 to guard->skipped_steps instead of counter[0]: parameters, state and the
+//       step count stay bit for bit as they were.  Otherwise the gradient of every element is multiplied by clip_coef (fp32)
+//       before adam_elem; a coefficient of 1 leaves the arithmetic bit-identical to flat_adam_kernel<false>, which is the
+//       unguarded step as it always was.
 #include "n3dt_device.h"
 
 #define ADAM_THREADS 256
@@ -70,9 +87,9 @@ __device__ __forceinline__ void adam_st4(float* q, f32x4 x) {
 }
 
 // nvec whole vectors starting at element 0 of the four (already offset) pointers; g, m, v 16-byte aligned
-template <bool PVEC>
+template <bool PVEC, bool GUARDED>
 __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, int nvec, const AdamScalars& s, bool maximize) {
+                                          float* __restrict__ v, int nvec, const AdamScalars& s, bool maximize, float clip) {
     for (int base = 0; base < nvec; base += ADAM_THREADS * ADAM_UNROLL) {
         f32x4 P[ADAM_UNROLL], G[ADAM_UNROLL], M[ADAM_UNROLL], V[ADAM_UNROLL];
 #pragma unroll
@@ -92,7 +109,7 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float pj = P[k][j], mj = M[k][j], vj = V[k][j];
-                    adam_elem(pj, G[k][j], mj, vj, s, maximize);
+                    adam_elem(pj, GUARDED ? G[k][j] * clip : G[k][j], mj, vj, s, maximize);
                     P[k][j] = pj; M[k][j] = mj; V[k][j] = vj;
                 }
                 adam_st4<PVEC>(p + 4 * (size_t)i, P[k]);
@@ -103,10 +120,145 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
     }
 }
 
+// one workgroup's sum of a per-thread double, added in a fixed order: xor butterflies inside a wave (every lane ends with
+// the same value), then the waves in index order.  `slot`: 4 doubles of LDS the caller does not touch until its next
+// barrier.  The result is valid in thread 0.
+__device__ __forceinline__ double norm_block_sum(double x, double* slot) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((slot[0] + slot[1]) + slot[2]) + slot[3];
+}
+
+#define NORM_TILE 2048  // partials staged per pass of the final sum (16 KiB of LDS)
+#define NORM_BATCH 16   // partials in registers ahead of the final sum's add chain
+
+__global__ __launch_bounds__(ADAM_THREADS) void flat_grad_norm_kernel(const N3dtAdamTensor* __restrict__ tensors,
+                                                                      const N3dtAdamChunk* __restrict__ chunks, int n_chunks,
+                                                                      int n_groups, double* partials, N3dtAdamGuard* guard) {
+    static_assert(ADAM_THREADS == 256, "norm_block_sum adds four waves");
+    // two sets, toggled once per norm_block_sum (= once per barrier): a wave may be one sum ahead of the slowest reader of the
+    // previous one, and the barrier of that next sum lies between any read of a set and the next write to it
+    __shared__ double s_wave[2][4];
+    __shared__ double s_tile[NORM_TILE];
+    __shared__ int s_last;
+    int set = 0;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const N3dtAdamChunk ck = chunks[c];
+        const N3dtAdamTensor T = tensors[ck.tensor];
+        // exactly the chunks flat_adam_kernel updates (the same for the whole workgroup; no barrier on this path)
+        if (!T.active || ck.length <= 0 || (unsigned)T.group >= (unsigned)n_groups) {
+            if (threadIdx.x == 0) partials[c] = 0.0;
+            continue;
+        }
+        const float* g = T.grad + ck.start;
+        const int n = ck.length;
+        int head = (int)((16 - ((uintptr_t)g & 15)) & 15) >> 2;
+        if (head > n) head = n;
+        const int nvec = (n - head) >> 2, tail = (n - head) & 3;
+        double acc = 0.0;
+        if ((int)threadIdx.x < head + tail) {
+            const int i = (int)threadIdx.x < head ? (int)threadIdx.x : head + 4 * nvec + ((int)threadIdx.x - head);
+            const double x = (double)adam_ld(g + i);
+            acc = x * x;
+        }
+        const float* gv = g + head;
+        for (int base = 0; base < nvec; base += ADAM_THREADS * ADAM_UNROLL) {
+            f32x4 G[ADAM_UNROLL];
+#pragma unroll
+            for (int k = 0; k < ADAM_UNROLL; ++k) {
+                const int i = base + k * ADAM_THREADS + (int)threadIdx.x;
+                if (i < nvec) G[k] = adam_ld4<true>(gv + 4 * (size_t)i);
+            }
+#pragma unroll
+            for (int k = 0; k < ADAM_UNROLL; ++k) {
+                const int i = base + k * ADAM_THREADS + (int)threadIdx.x;
+                if (i < nvec) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const double x = (double)G[k][j];
+                        acc += x * x;
+                    }
+                }
+            }
+        }
+        const double sum = norm_block_sum(acc, s_wave[set]);
+        set ^= 1;
+        if (threadIdx.x == 0) partials[c] = sum;
+    }
+
+    // thread 0 wrote this workgroup's partials: make them visible at agent scope, then count the workgroup as finished
+    if (threadIdx.x == 0) {
+        __threadfence();
+        s_last = atomicAdd(&guard->norm_done, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();  // every partial was stored before its workgroup's count; read them from memory, not from this CU's cache
+    double total = 0.0;
+    for (int base = 0; base < n_chunks; base += NORM_TILE) {
+        const int m = n_chunks - base < NORM_TILE ? n_chunks - base : NORM_TILE;
+        for (int i = threadIdx.x; i < m; i += ADAM_THREADS)
+            s_tile[i] = __hip_atomic_load(partials + base + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            // index order, one dependent add after another; the LDS reads of the next NORM_BATCH values are issued ahead of
+            // the adds of the current ones, so the chain waits for the adder only
+            int i = 0;
+            if (m >= NORM_BATCH) {
+                double cur[NORM_BATCH], nxt[NORM_BATCH];
+#pragma unroll
+                for (int j = 0; j < NORM_BATCH; ++j) cur[j] = s_tile[j];
+                for (; i + 2 * NORM_BATCH <= m; i += NORM_BATCH) {
+#pragma unroll
+                    for (int j = 0; j < NORM_BATCH; ++j) nxt[j] = s_tile[i + NORM_BATCH + j];
+#pragma unroll
+                    for (int j = 0; j < NORM_BATCH; ++j) total += cur[j];
+#pragma unroll
+                    for (int j = 0; j < NORM_BATCH; ++j) cur[j] = nxt[j];
+                }
+#pragma unroll
+                for (int j = 0; j < NORM_BATCH; ++j) total += cur[j];
+                i += NORM_BATCH;
+            }
+            for (; i < m; ++i) total += s_tile[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(total);  // rounded to fp32 once
+        const float max_norm = guard->max_grad_norm;
+        float coef = 1.0f;
+        if (max_norm > 0.0f) {
+            // clip_grad_norm_: max_norm / (total_norm + 1e-6) is reciprocal() * max_norm in fp32, then clamp(max = 1), NaN kept
+            coef = (1.0f / (norm + 1e-6f)) * max_norm;
+            coef = coef != coef ? coef : fminf(coef, 1.0f);
+        }
+        guard->grad_norm = norm;
+        guard->clip_coef = coef;
+        guard->skip = (guard->skip_nonfinite != 0 && !isfinite(norm)) ? 1 : 0;
+        atomicExch(&guard->norm_done, 0);
+    }
+}
+
+template <bool GUARDED>
 __global__ __launch_bounds__(ADAM_THREADS) void flat_adam_kernel(const N3dtAdamTensor* __restrict__ tensors,
                                                                  const N3dtAdamChunk* __restrict__ chunks, int n_chunks,
                                                                  const N3dtAdamGroup* __restrict__ groups, int n_groups,
-                                                                 int* counter) {
+                                                                 int* counter, N3dtAdamGuard* guard) {
+    // the guard record was written by the launch in front of this one and nothing writes it while this one runs
+    const float clip = GUARDED ? guard->clip_coef : 1.0f;
+    if (GUARDED && guard->skip != 0) {  // (the same for every thread of the grid) no tensor, no step count is touched
+        if (threadIdx.x == 0) {
+            const int done = atomicAdd(counter + 1, 1);
+            if (done == (int)gridDim.x - 1) {
+                atomicAdd(&guard->skipped_steps, 1);
+                atomicExch(counter + 1, 0);
+            }
+        }
+        return;
+    }
     __shared__ AdamScalars s_sc[N3DT_ADAM_MAX_GROUPS];
     __shared__ int s_max[N3DT_ADAM_MAX_GROUPS];
     if ((int)threadIdx.x < n_groups) {
@@ -143,7 +295,8 @@ __global__ __launch_bounds__(ADAM_THREADS) void flat_adam_kernel(const N3dtAdamT
         if (!state_vec) {
             for (int i = threadIdx.x; i < n; i += ADAM_THREADS) {
                 float pj = adam_ld(p + i), mj = adam_ld(m + i), vj = adam_ld(v + i);
-                adam_elem(pj, adam_ld(g + i), mj, vj, s, maximize);
+                const float gj = adam_ld(g + i);
+                adam_elem(pj, GUARDED ? gj * clip : gj, mj, vj, s, maximize);
                 adam_st(p + i, pj); adam_st(m + i, mj); adam_st(v + i, vj);
             }
             continue;
@@ -154,13 +307,14 @@ __global__ __launch_bounds__(ADAM_THREADS) void flat_adam_kernel(const N3dtAdamT
         if ((int)threadIdx.x < head + tail) {  // at most 6 scalar elements per chunk
             const int i = (int)threadIdx.x < head ? (int)threadIdx.x : head + 4 * nvec + ((int)threadIdx.x - head);
             float pj = adam_ld(p + i), mj = adam_ld(m + i), vj = adam_ld(v + i);
-            adam_elem(pj, adam_ld(g + i), mj, vj, s, maximize);
+            const float gj = adam_ld(g + i);
+            adam_elem(pj, GUARDED ? gj * clip : gj, mj, vj, s, maximize);
             adam_st(p + i, pj); adam_st(m + i, mj); adam_st(v + i, vj);
         }
         if (((((uintptr_t)p) ^ ga) & 15) == 0)
-            adam_body<true>(p + head, g + head, m + head, v + head, nvec, s, maximize);
+            adam_body<true, GUARDED>(p + head, g + head, m + head, v + head, nvec, s, maximize, clip);
         else
-            adam_body<false>(p + head, g + head, m + head, v + head, nvec, s, maximize);
+            adam_body<false, GUARDED>(p + head, g + head, m + head, v + head, nvec, s, maximize, clip);
     }
 
     // every read of counter[0] in this workgroup happened before the barrier above
@@ -177,6 +331,17 @@ extern "C" void n3dt_launch_flat_adam(const void* tensors, const void* chunks, i
                                       void* counter, hipStream_t stream) {
     // memory-bound: at most 4 workgroups per CU's worth of blocks, the rest of the chunks by grid stride
     const int grid = n_chunks < N3DT_ADAM_MAX_GRID ? n_chunks : N3DT_ADAM_MAX_GRID;
-    hipLaunchKernelGGL(flat_adam_kernel, dim3(grid), dim3(ADAM_THREADS), 0, stream, (const N3dtAdamTensor*)tensors,
-                       (const N3dtAdamChunk*)chunks, n_chunks, (const N3dtAdamGroup*)groups, n_groups, (int*)counter);
+    hipLaunchKernelGGL(flat_adam_kernel<false>, dim3(grid), dim3(ADAM_THREADS), 0, stream, (const N3dtAdamTensor*)tensors,
+                       (const N3dtAdamChunk*)chunks, n_chunks, (const N3dtAdamGroup*)groups, n_groups, (int*)counter,
+                       (N3dtAdamGuard*)nullptr);
+}
+
+extern "C" void n3dt_launch_flat_adam_guarded(const void* tensors, const void* chunks, int n_chunks, const void* groups,
+                                              int n_groups, void* counter, void* partials, void* guard, hipStream_t stream) {
+    const int grid = n_chunks < N3DT_ADAM_MAX_GRID ? n_chunks : N3DT_ADAM_MAX_GRID;
+    hipLaunchKernelGGL(flat_grad_norm_kernel, dim3(grid), dim3(ADAM_THREADS), 0, stream, (const N3dtAdamTensor*)tensors,
+                       (const N3dtAdamChunk*)chunks, n_chunks, n_groups, (double*)partials, (N3dtAdamGuard*)guard);
+    hipLaunchKernelGGL(flat_adam_kernel<true>, dim3(grid), dim3(ADAM_THREADS), 0, stream, (const N3dtAdamTensor*)tensors,
+                       (const N3dtAdamChunk*)chunks, n_chunks, (const N3dtAdamGroup*)groups, n_groups, (int*)counter,
+                       (N3dtAdamGuard*)guard);
 }

@@ -85,6 +85,7 @@ size_t n3dt_a2s_ws_floats(int);
 void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* const[3], float*, void*, void*, hipStream_t);
 void n3dt_launch_a2s_bwd(int, const N3dtA2sParams*, const float*, const void*, float*, void*, hipStream_t);
 void n3dt_launch_flat_adam(const void*, const void*, int, const void*, int, void*, hipStream_t);
+void n3dt_launch_flat_adam_guarded(const void*, const void*, int, const void*, int, void*, void*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -630,6 +631,29 @@ extern "C" int n3dt_flat_adam_step(const void* tensor_table, const void* chunk_t
         return fail(N3DT_EINVAL, "n3dt_flat_adam_step: tables must be 8-byte aligned, the step counter 4-byte aligned");
     n3dt_launch_flat_adam(tensor_table, chunk_table, n_chunks, group_table, n_groups, step_counter, (hipStream_t)stream);
     return check_hip("n3dt_flat_adam_step");
+}
+
+extern "C" size_t n3dt_flat_adam_guard_bytes(void) { return sizeof(N3dtAdamGuard); }
+
+extern "C" int n3dt_flat_adam_guarded_step(const void* tensor_table, const void* chunk_table, int n_chunks, const void* group_table,
+                                           int n_groups, void* step_counter, void* partials, void* guard, void* stream) {
+    static const char* who = "n3dt_flat_adam_guarded_step";
+    char msg[160];
+    const char* what = nullptr;
+    if (!tensor_table || !chunk_table || !group_table || !step_counter) what = "NULL table";
+    else if (!partials || !guard) what = "NULL partials or guard record";
+    else if (n_chunks <= 0) what = "n_chunks must be >= 1";
+    else if (n_groups < 1 || n_groups > N3DT_ADAM_MAX_GROUPS) what = "n_groups outside 1..64";
+    else if ((((size_t)tensor_table) | ((size_t)chunk_table) | ((size_t)group_table)) & 7 || ((size_t)step_counter) & 3)
+        what = "tables must be 8-byte aligned, the step counter 4-byte aligned";
+    else if (((size_t)partials) & 7 || ((size_t)guard) & 3) what = "partials must be 8-byte aligned, the guard record 4-byte aligned";
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_flat_adam_guarded(tensor_table, chunk_table, n_chunks, group_table, n_groups, step_counter, partials, guard,
+                                  (hipStream_t)stream);
+    return check_hip(who);
 }
 
 extern "C" int n3dt_chw_to_hwc(int C, int n, const float* src, float* dst, void* stream) {

@@ -55,6 +55,14 @@ class AdamGroup(ctypes.Structure):
                 ("weight_decay", ctypes.c_double), ("maximize", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class AdamGuard(ctypes.Structure):
+    """N3dtAdamGuard (include/n3dt_flat_adam_guard.h).  The host writes the first GUARD_HOST_BYTES only."""
+    _fields_ = [("max_grad_norm", ctypes.c_float), ("skip_nonfinite", ctypes.c_int32), ("grad_norm", ctypes.c_float),
+                ("clip_coef", ctypes.c_float), ("skip", ctypes.c_int32), ("skipped_steps", ctypes.c_int32),
+                ("norm_done", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+GUARD_HOST_BYTES = 8
 ADAM_MAX_GROUPS = 64
 ADAM_COUNTER_INTS = 4
 
@@ -91,6 +99,9 @@ EXPORTS = [
     "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
     "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
 ]
+
+# the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
+GUARD_EXPORTS = ["n3dt_flat_adam_guard_bytes", "n3dt_flat_adam_guarded_step"]
 
 STAGE_MAX = 12
 
@@ -221,8 +232,14 @@ def lib():
     L.n3dt_flat_adam_record_bytes.argtypes = [ci]
     L.n3dt_flat_adam_step.restype = ci
     L.n3dt_flat_adam_step.argtypes = [vp, vp, ci, vp, ci, vp, vp]
+    L.n3dt_flat_adam_guard_bytes.restype = sz
+    L.n3dt_flat_adam_guard_bytes.argtypes = []
+    L.n3dt_flat_adam_guarded_step.restype = ci
+    L.n3dt_flat_adam_guarded_step.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp]
     if L.n3dt_abi_version() != 5:
         raise N3dtError("libn3dt.so ABI version mismatch")
+    if L.n3dt_flat_adam_guard_bytes() != ctypes.sizeof(AdamGuard):
+        raise N3dtError("libn3dt.so: N3dtAdamGuard differs from its ctypes mirror")
     for which, rec in enumerate((AdamTensor, AdamChunk, AdamGroup)):
         if L.n3dt_flat_adam_record_bytes(which) != ctypes.sizeof(rec):
             raise N3dtError("libn3dt.so: FlatAdam table record %d differs from its ctypes mirror" % which)

@@ -13,7 +13,28 @@ What differs from torch.optim.Adam, on purpose:
     `invalidate_packed()` on the objects passed as `modules`, so version-keyed caches of the weights are rebuilt;
   * `param_groups[g]["lr"]` stays the Python float schedulers edit; the device copy the kernel reads is refreshed by
     step() -- or by sync_hyperparameters() between replays of a captured graph, where Python does not run.
+
+The guarded step (opt-in: `max_grad_norm=`, `skip_nonfinite=`).  With either option set, step() is two launches
+(n3dt_flat_adam_guarded_step): a norm kernel over the gradients of the active tensors, then the Adam kernel.
+  * total_norm = sqrt(sum g^2) over every element of every parameter whose `.grad` is not None, all groups together, on the raw
+    gradient (before maximize and weight decay): what `clip_grad_norm_(params, max_norm, norm_type=2)` sees.  Squares and sums
+    are formed in double in a fixed order and rounded to fp32 once, so the norm is reproducible and |g| ~ 1e30 stays finite.
+  * clip_coef = min(1, max_grad_norm / (total_norm + 1e-6)) in torch's fp32 arithmetic; the Adam arithmetic sees g * clip_coef.
+    `.grad` itself is NOT rewritten -- unlike clip_grad_norm_ -- which keeps the step at 4 reads + 3 writes per element.
+  * skip_nonfinite=True and a total_norm that is not finite: the launch leaves every parameter, exp_avg, exp_avg_sq AND the step
+    counter bit for bit as they were and adds 1 to a device-side counter.  The host does not know the outcome: version bumps
+    and invalidate_packed() still happen, which costs a re-pack and nothing else.  With skip_nonfinite=False the formulas are
+    evaluated as written, as torch would (a NaN norm makes the coefficient NaN).
+  * `opt.grad_norm`, `opt.clip_coef` (0-dim fp32) and `opt.skipped_steps` (0-dim int32) are views of one persistent device
+    record: reading the attribute synchronises nothing, and the views stay valid inside and across graph replays.  Looking at
+    `skipped_steps` once per epoch replaces the reference's per-step `isnan(loss.item())`.
+  * `opt.max_grad_norm` lives in that record too and is pushed by sync_hyperparameters() like the group table, so a replayed
+    graph follows a change made between replays.  Whether a step is guarded at all is fixed when a graph is captured.
+  * the skipped count is not part of the state dict, which stays torch.optim.Adam's.
+  * data parallel: the norm is taken over what the arena holds at step() time, i.e. after GradReducer's in-place averaging, so
+    every rank sees the same gradients and takes the same decision.  No collective is added.
 """
+import math
 import ctypes
 
 import torch
@@ -81,6 +102,17 @@ def _check_group(g):
         raise ValueError("FlatAdam: differentiable=True is not supported")
 
 
+def _check_max_grad_norm(v):
+    if v is None:
+        return None
+    if torch.is_tensor(v) or isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError("FlatAdam: max_grad_norm must be a Python number > 0 (inf allowed) or None (the device copy is kept by "
+                         "the optimizer), got %r" % (type(v).__name__,))
+    if math.isnan(v) or not v > 0:
+        raise ValueError("FlatAdam: max_grad_norm must be > 0 (inf allowed), got %r" % (v,))
+    return float(v)
+
+
 def _bump_versions(params):
     """Move the version counters of `params` by one without a launch.  False when this PyTorch has no way to do it (then
     `modules=` is what keeps version-keyed caches right)."""
@@ -106,9 +138,14 @@ class FlatAdam(torch.optim.Optimizer):
     """Adam (amsgrad=False, L2 weight decay) whose step() is one n3dt_flat_adam_step launch.  Same constructor arguments as
     torch.optim.Adam where they apply; `modules`: objects whose invalidate_packed() is called after every step
     (HeadNeRFNet), and whose grad_arena() -- when they have one -- is the arena the state is laid out over.
+    `max_grad_norm` (a Python number > 0, inf allowed) / `skip_nonfinite`: the guarded step of the module docstring -- global-norm
+    clipping and non-finite step skipping on the device; both off by default, and then step() is the single launch it always was.
     fp32 CUDA parameters with dense gradients only: anything else raises, nothing falls back to PyTorch."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, modules=()):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, modules=(),
+                 max_grad_norm=None, skip_nonfinite=False):
+        self._max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         if amsgrad:
             raise ValueError("FlatAdam: amsgrad=True is not supported (the kernel keeps no max_exp_avg_sq)")
         if torch.is_tensor(lr):
@@ -178,6 +215,13 @@ class FlatAdam(torch.optim.Optimizer):
         self._tensor_dev = torch.empty(ctypes.sizeof(_lib.AdamTensor) * len(self._rows), dtype=torch.uint8, device=dev)
         self._group_dev = torch.empty(ctypes.sizeof(_lib.AdamGroup) * len(self.param_groups), dtype=torch.uint8, device=dev)
         self._counter = torch.zeros(_lib.ADAM_COUNTER_INTS, dtype=torch.int32, device=dev)
+        # the guarded step's scratch: one double per chunk, and the guard record (zero-filled once; the host writes its first
+        # GUARD_HOST_BYTES from then on, the kernels the rest)
+        self._partials = torch.zeros(self._n_chunks, dtype=torch.float64, device=dev)
+        self._guard = torch.zeros(ctypes.sizeof(_lib.AdamGuard) // 4, dtype=torch.int32, device=dev)
+        self._guard_host = self._guard[:_lib.GUARD_HOST_BYTES // 4].view(torch.uint8)
+        self._guard_f32 = self._guard.view(torch.float32)
+        self._pushed_guard = None
         self._pushed_tensors = None   # (param pointers, active flags) of the table on the device
         self._pushed_groups = None
         self._ready = True
@@ -192,6 +236,39 @@ class FlatAdam(torch.optim.Optimizer):
             self.state[p] = {"step": step, "exp_avg": self._exp_avg[ai][sl].view(p.shape),
                              "exp_avg_sq": self._exp_avg_sq[ai][sl].view(p.shape)}
 
+    # ---- the guard ---------------------------------------------------------------------------------------------------
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self._max_grad_norm = _check_max_grad_norm(v)
+
+    @property
+    def guarded(self):
+        return self._max_grad_norm is not None or self.skip_nonfinite
+
+    def _guard_field(self, name, f32):
+        if not self._ready:
+            self._setup()
+        return (self._guard_f32 if f32 else self._guard)[getattr(_lib.AdamGuard, name).offset // 4]
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 device tensor: the global gradient norm of the last guarded step (a view; no synchronisation)."""
+        return self._guard_field("grad_norm", True)
+
+    @property
+    def clip_coef(self):
+        """0-dim fp32 device tensor: the factor the last guarded step multiplied its gradients by (a view)."""
+        return self._guard_field("clip_coef", True)
+
+    @property
+    def skipped_steps(self):
+        """0-dim int32 device tensor: guarded steps skipped so far for a non-finite norm (a view)."""
+        return self._guard_field("skipped_steps", False)
+
     # ---- hyper-parameters --------------------------------------------------------------------------------------------
     def _group_values(self):
         vals = []
@@ -202,9 +279,9 @@ class FlatAdam(torch.optim.Optimizer):
         return tuple(vals)
 
     def sync_hyperparameters(self):
-        """Push lr / betas / eps / weight_decay / maximize of every group to the device if they differ from what was last
-        pushed (one small stream-ordered copy, no synchronisation).  step() does this itself; a caller replaying a captured
-        graph calls it between replays, after scheduler.step()."""
+        """Push lr / betas / eps / weight_decay / maximize of every group, and max_grad_norm / skip_nonfinite, to the device if
+        they differ from what was last pushed (one small stream-ordered copy each, no synchronisation).  step() does this
+        itself; a caller replaying a captured graph calls it between replays, after scheduler.step()."""
         if not self._ready:
             self._setup()
         vals = self._group_values()
@@ -212,6 +289,10 @@ class FlatAdam(torch.optim.Optimizer):
             arr = (_lib.AdamGroup * len(vals))(*[_lib.AdamGroup(*v, 0) for v in vals])
             _upload(self._group_dev, bytes(arr))
             self._pushed_groups = vals
+        gvals = (0.0 if self._max_grad_norm is None else self._max_grad_norm, int(self.skip_nonfinite))
+        if gvals != self._pushed_guard:
+            _upload(self._guard_host, bytes(_lib.AdamGuard(*gvals))[:_lib.GUARD_HOST_BYTES])
+            self._pushed_guard = gvals
 
     # ---- the step ----------------------------------------------------------------------------------------------------
     def _sync_tables(self):
@@ -254,9 +335,15 @@ class FlatAdam(torch.optim.Optimizer):
         self.sync_hyperparameters()
         if any(active):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
-            _lib.check(_lib.lib().n3dt_flat_adam_step(self._tensor_dev.data_ptr(), self._chunk_dev.data_ptr(), self._n_chunks,
-                                                      self._group_dev.data_ptr(), len(self.param_groups),
-                                                      self._counter.data_ptr(), stream), "n3dt_flat_adam_step")
+            if self.guarded:
+                _lib.check(_lib.lib().n3dt_flat_adam_guarded_step(
+                    self._tensor_dev.data_ptr(), self._chunk_dev.data_ptr(), self._n_chunks, self._group_dev.data_ptr(),
+                    len(self.param_groups), self._counter.data_ptr(), self._partials.data_ptr(), self._guard.data_ptr(), stream),
+                    "n3dt_flat_adam_guarded_step")
+            else:
+                _lib.check(_lib.lib().n3dt_flat_adam_step(self._tensor_dev.data_ptr(), self._chunk_dev.data_ptr(), self._n_chunks,
+                                                          self._group_dev.data_ptr(), len(self.param_groups),
+                                                          self._counter.data_ptr(), stream), "n3dt_flat_adam_step")
             self._has_state = True
             _bump_versions([p for (_, _, p), act in zip(self._rows, active) if act])
             for m in self.modules:

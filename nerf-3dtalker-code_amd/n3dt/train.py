@@ -155,11 +155,12 @@ def make_optimizer(net, lr=1e-4):
     return opt, sched
 
 
-def make_flat_optimizer(net, lr=1e-4):
+def make_flat_optimizer(net, lr=1e-4, max_grad_norm=None, skip_nonfinite=False):
     """The same Adam + StepLR with the optimizer step on libn3dt (n3dt.FlatAdam: one launch over the net's gradient arena,
-    version counters and packed-weight caches kept right after every step)."""
+    version counters and packed-weight caches kept right after every step).  `max_grad_norm` / `skip_nonfinite`: FlatAdam's
+    device-side global-norm clipping and non-finite step skipping (off by default)."""
     from .optim import FlatAdam
-    opt = FlatAdam(net.parameters(), lr=lr, modules=[net])
+    opt = FlatAdam(net.parameters(), lr=lr, modules=[net], max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.1)
     return opt, sched
 

@@ -7,6 +7,12 @@ replay()); the figure is the MEDIAN of `--iters` steps after `--warmup`.  GB/s c
 the update needs.  Then one config-3 training step (B = 2, bf16 renderer, FlatBucket stand-in, two optimizers) with torch's fused
 Adam and with FlatAdam, alternating.  Prints one JSON object.
 
+The guarded step (FlatAdam(max_grad_norm=1.0, skip_nonfinite=True): the norm kernel + the Adam kernel, 32 bytes per element) is a
+row of its own next to the unguarded one, and "guard_pairs" times the two ALTERNATELY in this run -- `--pairs` times eager, then
+`--pairs` times as graph replays -- which is the comparison to quote: guarded / unguarded of the same build, same process.
+--against-lib PATH: also time the UNGUARDED n3dt_flat_adam_step of another build of libn3dt.so (e.g. the parent commit's) against
+this build's on the same tables, alternating pairs, eager and graph ("lib_pairs").
+
 --trace-steps N: nothing is timed; N eager steps of each optimizer on each set and nothing else, for a
 `rocprofv3 --kernel-trace --stats -- python tools/adam_time.py --trace-steps N` run (launches per step = Calls / N).
 
@@ -38,9 +44,14 @@ def make_module(name, dev):
     return parallel.FlatBucket().to(dev)
 
 
+GUARD = dict(max_grad_norm=1.0, skip_nonfinite=True)
+
+
 def make_optimizer(kind, name, mod, capturable=False):
     if kind == "flat":
         return FlatAdam(mod.parameters(), modules=[mod], **SETS[name])
+    if kind == "flat_guarded":
+        return FlatAdam(mod.parameters(), modules=[mod], **GUARD, **SETS[name])
     return torch.optim.Adam(mod.parameters(), fused=True, capturable=capturable, **SETS[name])
 
 
@@ -49,7 +60,7 @@ def fill_grads(mod, kind):
     gen = torch.Generator(device="cuda").manual_seed(1)
     for p in mod.parameters():
         p.grad = torch.randn(p.shape, device=p.device, generator=gen) * 1e-3
-    if kind == "flat":
+    if kind.startswith("flat"):
         arena = mod.grad_arena() if hasattr(mod, "grad_arena") else parallel._arena_for(list(mod.parameters()))
         arena.adopt()
 
@@ -69,7 +80,7 @@ def median_us(fn, warmup, iters):
 
 def time_set(name, dev, warmup, iters):
     out = {}
-    for kind in ("flat", "torch_fused"):
+    for kind in ("flat", "flat_guarded", "torch_fused"):
         mod = make_module(name, dev)
         numel = sum(p.numel() for p in mod.parameters() if p.requires_grad)
         fill_grads(mod, kind)
@@ -89,11 +100,82 @@ def time_set(name, dev, warmup, iters):
         with torch.cuda.graph(graph):
             opt.step()
         graphed = median_us(graph.replay, warmup, iters)
-        nbytes = 28.0 * numel
+        nbytes = (32.0 if kind == "flat_guarded" else 28.0) * numel
         out[kind] = {"eager_us": round(eager, 2), "graph_us": round(graphed, 2), "eager_GBps": round(nbytes / eager / 1e3, 1),
                      "graph_GBps": round(nbytes / graphed / 1e3, 1)}
         out["numel"], out["tensors"] = numel, sum(1 for p in mod.parameters() if p.requires_grad)
     return out
+
+
+def _graph_of(fn):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return graph
+
+
+def _alternate(fns, warmup, iters, pairs):
+    """{label: [median us] * pairs}, the labels taken in turn inside every pair."""
+    out = {k: [] for k in fns}
+    for _ in range(pairs):
+        for k, fn in fns.items():
+            out[k].append(round(median_us(fn, warmup, iters), 2))
+    return out
+
+
+def _ratio(d, num, den):
+    return round(statistics.median(d[num]) / statistics.median(d[den]), 4)
+
+
+def guard_pairs(name, dev, warmup, iters, pairs):
+    """The guarded step against the unguarded one of this build, alternating, eager and as graph replays."""
+    opts = {}
+    for kind in ("flat", "flat_guarded"):
+        mod = make_module(name, dev)
+        fill_grads(mod, kind)
+        opts[kind] = (make_optimizer(kind, name, mod), mod)
+    eager = _alternate({k: o.step for k, (o, _) in opts.items()}, warmup, iters, pairs)
+    graphs = {k: _graph_of(o.step) for k, (o, _) in opts.items()}
+    graph = _alternate({k: g.replay for k, g in graphs.items()}, warmup, iters, pairs)
+    skipped = int(opts["flat_guarded"][0].skipped_steps)
+    assert skipped == 0, "the timed guarded steps must be real steps, %d were skipped" % skipped
+    return {"eager_us": eager, "graph_us": graph, "eager_guarded_over_unguarded": _ratio(eager, "flat_guarded", "flat"),
+            "graph_guarded_over_unguarded": _ratio(graph, "flat_guarded", "flat")}
+
+
+def lib_pairs(name, dev, other_path, warmup, iters, pairs):
+    """n3dt_flat_adam_step (unguarded) of this build and of the libn3dt.so at `other_path`, on one optimizer's tables."""
+    import ctypes
+    from n3dt import _lib
+    mod = make_module(name, dev)
+    fill_grads(mod, "flat")
+    opt = make_optimizer("flat", name, mod)
+    opt.step()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    other = ctypes.CDLL(other_path)
+    other.n3dt_flat_adam_step.restype = ci
+    other.n3dt_flat_adam_step.argtypes = [vp, vp, ci, vp, ci, vp, vp]
+
+    def call(L):
+        def fn():
+            s = vp(torch.cuda.current_stream(dev).cuda_stream)
+            rc = L.n3dt_flat_adam_step(opt._tensor_dev.data_ptr(), opt._chunk_dev.data_ptr(), opt._n_chunks, opt._group_dev.data_ptr(),
+                                       len(opt.param_groups), opt._counter.data_ptr(), s)
+            assert rc == 0
+        return fn
+    fns = {"this": call(_lib.lib()), "other": call(other)}
+    eager = _alternate(fns, warmup, iters, pairs)
+    graphs = {k: _graph_of(f) for k, f in fns.items()}
+    graph = _alternate({k: g.replay for k, g in graphs.items()}, warmup, iters, pairs)
+    return {"eager_us": eager, "graph_us": graph, "eager_this_over_other": _ratio(eager, "this", "other"),
+            "graph_this_over_other": _ratio(graph, "this", "other")}
 
 
 def train_step_ms(dev, kind, warmup, iters):
@@ -140,14 +222,14 @@ def train_step_ms(dev, kind, warmup, iters):
 
 def trace(dev, steps):
     for name in SETS:
-        for kind in ("flat", "torch_fused"):
+        for kind in ("flat", "flat_guarded", "torch_fused"):
             mod = make_module(name, dev)
             fill_grads(mod, kind)
             opt = make_optimizer(kind, name, mod)
             for _ in range(steps):
                 opt.step()
     torch.cuda.synchronize()
-    print(json.dumps({"trace_steps": steps, "sets": list(SETS), "optimizers": ["flat", "torch_fused"]}))
+    print(json.dumps({"trace_steps": steps, "sets": list(SETS), "optimizers": ["flat", "flat_guarded", "torch_fused"]}))
 
 
 def main():
@@ -156,13 +238,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--step-iters", type=int, default=20)
     ap.add_argument("--trace-steps", type=int, default=0)
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--against-lib", default=None)
+    ap.add_argument("--skip-train-step", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.trace_steps:
         return trace(dev, args.trace_steps)
-    out = {"iters": args.iters, "warmup": args.warmup, "bytes_per_element": 28}
+    out = {"iters": args.iters, "warmup": args.warmup, "pairs": args.pairs, "bytes_per_element": 28, "bytes_per_element_guarded": 32}
     for name in SETS:
         out[name] = time_set(name, dev, args.warmup, args.iters)
+        out[name]["guard_pairs"] = guard_pairs(name, dev, args.warmup, args.iters, args.pairs)
+        if args.against_lib:
+            out[name]["lib_pairs"] = lib_pairs(name, dev, args.against_lib, args.warmup, args.iters, args.pairs)
+    if args.skip_train_step:
+        print(json.dumps(out, sort_keys=True))
+        return
     runs = {"torch_fused": [], "flat": []}
     for _ in range(2):
         for kind in ("torch_fused", "flat"):
