@@ -40,8 +40,6 @@ void n3dt_launch_nerf_fwd_x16(const N3dtGeom*, int, const void*, const float*, c
                               const float*, const float*, float*, float*, hipStream_t);
 void n3dt_launch_nerf_fwd_x16s(const N3dtGeom*, const void*, const float*, const float*, const float*, const float*, const float*,
                                const float*, float*, float*, hipStream_t);
-void n3dt_launch_nerf_fwd_x16b(const N3dtGeom*, int, const void*, const float*, const float*, const float*, const float*,
-                               const float*, const float*, float*, float*, hipStream_t);
 size_t n3dt_nr_workspace_floats(const N3dtGeom*, int);
 size_t n3dt_train_saved_floats(const N3dtGeom*);
 size_t n3dt_train_ws_floats(const N3dtGeom*);
@@ -124,19 +122,6 @@ static int check_ray_bias(const N3dtGeom* g, const void* ray_bias, const char* w
         return N3DT_EINVAL;
     }
     return N3DT_OK;
-}
-
-// Tiling of the 16-bit fused render kernel: 1 = 32x32x16 MFMA, 8 waves x 32 samples; 2 = the same, 4 waves x 64 samples;
-// 3 = 16x16x32 MFMA, 8 waves x 32 samples (nerf_fwd_x16b.hip).  N3DT_X16_TILING overrides the default at run time.
-#ifndef N3DT_X16_DEFAULT_TILING
-#define N3DT_X16_DEFAULT_TILING 1
-#endif
-static int x16_tiling() {
-    static const int t = [] {
-        const char* e = getenv("N3DT_X16_TILING");
-        return e ? atoi(e) : N3DT_X16_DEFAULT_TILING;
-    }();
-    return t;
 }
 
 static inline int block_samples(int precision) { return precision == N3DT_F32 ? 16 : 32; }
@@ -272,9 +257,6 @@ static int render_fwd_common(const N3dtGeom* g, int precision, const void* packe
         n3dt_launch_nerf_fwd_f32(g, p, packed_mlp, fold, xy, R, T, Kinv, t_rand, part, weight ? wlocal : nullptr, s);
     else if (precision == N3DT_BF16X3)
         n3dt_launch_nerf_fwd_x16s(g, packed_mlp, fold, xy, R, T, Kinv, t_rand, part, weight ? wlocal : nullptr, s);
-    else if (x16_tiling() == 3 && g->vd_dim == 0)
-        n3dt_launch_nerf_fwd_x16b(g, precision, (const unsigned char*)packed_mlp + n3dt_packed_region_b_offset(precision), fold, xy, R, T,
-                                  Kinv, t_rand, part, weight ? wlocal : nullptr, s);
     else
         n3dt_launch_nerf_fwd_x16(g, precision, packed_mlp, fold, xy, R, T, Kinv, t_rand, part, weight ? wlocal : nullptr, s);
     n3dt_prof_span_end(span, s);

@@ -1,8 +1,8 @@
 // Fused volumetric-render kernel, 16-bit MFMA mode (bf16 or f16 inputs, fp32 accumulate):
 // the roofline path.
 //
-// One wavefront carries NB blocks of 32 consecutive samples of a ray (NB = 2 and N_s = 64: one
-// wavefront per ray) through the whole MLP with v_mfma_f32_32x32x16_{bf16,f16}.  Activations are
+// One wavefront carries one block of 32 consecutive samples of a ray through the whole MLP with
+// v_mfma_f32_32x32x16_{bf16,f16}, eight wavefronts per workgroup (two per SIMD).  Activations are
 // kept TRANSPOSED, H^T [channel][sample]: the sample sits on the MFMA column (lane & 31), the
 // channels in the accumulator registers.  A 32x32 accumulator tile, ReLU'd and packed to 16 bit,
 // is then directly the B operand of the next layer's MFMAs (its k order is a fixed permutation,
@@ -23,11 +23,11 @@
 #ifndef X16_SAVE_DEPTH
 #define X16_SAVE_DEPTH 3  // fragments in flight per wave in the training forward (X16_DEPTH for the others)
 #endif
-// One stage: out[N x 32*NB] = W'[N x K] . in[K x 32*NB] + bias (+ activation), NT = N/32 out tiles.
+// One stage: out[N x 32] = W'[N x K] . in[K x 32] + bias (+ activation), NT = N/32 out tiles.
 // The KPE leading k-steps take their B operand from the wave's PE fragments: registers (pe_reg,
 // stage L0) or the wave's LDS copy (pe_lds, skip stage L5); the rest come from hin.
 // The bias is the C operand of a tile's first weight MFMA (X16TileInit below).
-// SAVE (training forward, NB == 1): every finished output tile is also written to HBM for the backward -- hidden
+// SAVE (training forward): every finished output tile is also written to HBM for the backward -- hidden
 // tiles as [sample][channel] images (x16_core.h: x16_image_store) at sv.tile0 + 2 KiB * tile, the RGB_layer_1 activations
 // lane-linear (lane = sample fragments) at sv.tile0 + 1 KiB * k-step.
 template <int PREC>
@@ -36,7 +36,7 @@ struct X16SaveStage {
     unsigned* gate0;       // per-lane pointer to this layer's 6 gate words (64 words apart)
 };
 
-// Biases come from LDS (the 4-wave x 64-sample tiling excepted, below).  Every wave copies the next stage's fp32 bias table (<= 1.5 KiB) into its own
+// Biases come from LDS.  Every wave copies the next stage's fp32 bias table (<= 1.5 KiB) into its own
 // LDS slot by LDS-DMA a stage ahead (X16BiasLds::stage_in; complete two rendezvous waits later at the latest -- the first may
 // still leave as many operations outstanding as stores were reported before the copy was issued -- and read no earlier than the
 // stage's last tile).  Nothing of it is on vmcnt inside the stream: vmcnt retires in order, so a wait for a bias LOAD would also
@@ -53,13 +53,10 @@ struct X16SaveStage {
 // under that tile's pack / store epilogue, and the stage begins with the one full LDS wait it has (settle): a last tile
 // holds the whole input and 11/12 of the output of its layer, and a second register set across its k-loop does not fit the
 // 256 registers of two waves per SIMD (28 - 132 bytes of scratch in every instantiation when it was tried).
-// Two kinds of instantiation keep the earlier form, in which one float per lane (row c of the tile), fetched a tile ahead,
-// is split hi/lo and broadcast by one extra MFMA (template argument BIAS of x16_stage):
-//   * the training forward (SAVE), from LDS with x16_bias_read (X16_BIAS_LDS_MFMA): 84 bytes of scratch with the second
-//     register set next to its save pointers, 16 without.  Its density stage loads from global memory, as it always did;
-//   * the 4-wave x 64-sample tiling (NB = 2, diagnostic only), by global loads (X16_BIAS_GLOBAL_MFMA), exactly as before: its
-//     256 ARCHITECTURAL registers hold both blocks' activations; either LDS form costs it 16 - 44 bytes of scratch and brings
-//     back the misplaced register copy that tools/check_smem_hazard.py scans for (scan_join_copies).
+// The training forward (SAVE) keeps the earlier form, in which one float per lane (row c of the tile), fetched a tile ahead,
+// is split hi/lo and broadcast by one extra MFMA (template argument BIAS of x16_stage): from LDS with x16_bias_read
+// (X16_BIAS_LDS_MFMA) -- 84 bytes of scratch with the second register set next to its save pointers, 16 without.  Its density
+// stage loads its bias from global memory (X16_BIAS_GLOBAL_MFMA), as it always did.
 enum { X16_BIAS_GLOBAL_MFMA = 0, X16_BIAS_LDS_MFMA = 1, X16_BIAS_LDS_C = 2 };
 #define X16_BIAS_SLOT 1536  // bytes: 384 floats
 struct X16BiasLds {
@@ -111,20 +108,19 @@ constexpr int X16_TILE_INIT_READS = 4;
 // PAR: parity of the stage's first tile in the kernel's running tile count.  The caller has issued that tile's bias reads;
 // NEXT: a stage follows, and this one issues the reads of ITS first tile (table next_lds) behind its last k-loop.
 // bias: the stage's table in global memory (read by X16_BIAS_GLOBAL_MFMA only); bias_lds: X16BiasLds::at() of its LDS copy
-template <int PREC, int NB, int WAVES, int KS, int KPE, int NT, int MODE, bool SAVE, int BIAS, int PAR, bool NEXT, class WS>
+template <int PREC, int WAVES, int KS, int KPE, int NT, int MODE, bool SAVE, int BIAS, int PAR, bool NEXT, class WS>
 __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* __restrict__ bias, const unsigned bias_lds, const unsigned next_lds,
-                                          const typename X16<PREC>::frag (&pe_reg)[NB][4], const unsigned char* pe_lds,
-                                          const typename X16<PREC>::frag (&hin)[NB][24], typename X16<PREC>::frag (&hout)[NB][24],
-                                          float (&aux)[NB], float* const (&po)[NB], const bool (&live)[NB], const int lane,
+                                          const typename X16<PREC>::frag (&pe_reg)[4], const unsigned char* pe_lds,
+                                          const typename X16<PREC>::frag (&hin)[24], typename X16<PREC>::frag (&hout)[24],
+                                          float& aux, float* const po, const bool live, const int lane,
                                           const X16SaveStage<PREC>* sv = nullptr, const short relu_lo = 0) {
     typedef typename X16<PREC>::frag frag;
-    static_assert(!SAVE || NB == 1, "the training forward runs one block per wave");
     static_assert(KS >= WS::depth, "a tile's bias reads are covered by the wait of its own k-step DEPTH - 1");
     const int h = lane >> 5, c = lane & 31;
-    float red[NB][32];
+    float red[32];
     unsigned gate_word = 0;
     constexpr bool PACKS = (MODE == MODE_HIDDEN || MODE == MODE_LINEAR);
-    f32x16 acc[NB];
+    f32x16 acc;
     constexpr bool CINIT = BIAS == X16_BIAS_LDS_C, LB = BIAS == X16_BIAS_LDS_MFMA;
     // the two MFMA forms
     [[maybe_unused]] const frag ones = X16<PREC>::ones_frag();
@@ -136,15 +132,12 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
         bias_cur = bias[c];
     }
     auto finish_half = [&](const int t, const int half) {  // registers 8*half .. 8*half+7 of tile t -> k-step 2t+half
+        float v[8];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            float v[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = acc[nb][8 * half + r];
-            frag f = X16<PREC>::pack(v);
-            if (MODE == MODE_HIDDEN) f = X16<PREC>::relu(f, relu_lo);
-            hout[nb][2 * t + half] = f;
-        }
+        for (int r = 0; r < 8; ++r) v[r] = acc[8 * half + r];
+        frag f = X16<PREC>::pack(v);
+        if (MODE == MODE_HIDDEN) f = X16<PREC>::relu(f, relu_lo);
+        hout[2 * t + half] = f;
     };
     static_for<0, NT>([&](auto ot_c) {
         constexpr int ot = decltype(ot_c)::value;
@@ -154,9 +147,7 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
         if constexpr (CINIT) {
             if constexpr (ot == 0) ti.template settle<cs>();
             if constexpr (FETCH) ti.template issue<ns, (ot + 1) * 128>(bias_lds);
-            const f32x16 binit = ti.template get<cs>();  // landed and pinned a tile ago: C of the first weight MFMA
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = binit;
+            acc = ti.template get<cs>();  // landed and pinned a tile ago: C of the first weight MFMA
         } else {
             // acc = bias, broadcast over the samples, by ONE extra MFMA (hi/lo split keeps ~16 mantissa bits):
             // lane r of the lower half holds bias[ot*32 + r], fetched one tile ahead
@@ -169,9 +160,7 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
             f32x16 zero;
 #pragma unroll
             for (int r = 0; r < 16; ++r) zero[r] = 0.0f;
-            const f32x16 binit = X16<PREC>::mfma(bf, ones, zero);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = binit;
+            acc = X16<PREC>::mfma(bf, ones, zero);
         }
         X16_T(const unsigned long long s1 = x16_now(); const unsigned long long rv0 = ws.t_rv;)
         static_for<0, KS>([&](auto ks_c) {
@@ -180,24 +169,21 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
             // four more operations in flight; the wait of k-step DEPTH - 1 is the one that covers them
             const frag a_cur = ws.template next<MODE == MODE_COMPOSITE, NT * KS, ot * KS + ks,
                                                 (FETCH && ks < WS::depth - 1) ? X16_TILE_INIT_READS : 0>();
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                frag b;
-                if (ks < KPE) {
-                    if (pe_lds) b = *reinterpret_cast<const frag*>(pe_lds + (nb * 4 + ks) * X16_PIECE);
-                    else b = pe_reg[nb][ks < 4 ? ks : 0];
-                } else {
-                    b = hin[nb][ks >= KPE ? ks - KPE : 0];
-                }
-                acc[nb] = X16<PREC>::mfma(a_cur, b, acc[nb]);
+            frag b;
+            if (ks < KPE) {
+                if (pe_lds) b = *reinterpret_cast<const frag*>(pe_lds + ks * X16_PIECE);
+                else b = pe_reg[ks < 4 ? ks : 0];
+            } else {
+                b = hin[ks >= KPE ? ks - KPE : 0];
             }
+            acc = X16<PREC>::mfma(a_cur, b, acc);
         });
         // landed: the reads are older than the fragment awaited at k-step DEPTH - 1 of the loop above
         if constexpr (FETCH) ti.template landed<ns>();
         else if constexpr (CINIT && NEXT && ot + 1 == NT) ti.template issue<ns, 0>(next_lds);  // awaited by the next stage's settle
         if constexpr (LB && ot + 1 < NT) {
             // landed likewise (the accumulator rides along: the statement then cannot move ahead of the loop's last MFMA)
-            asm volatile("" : "+v"(bias_nxt), "+v"(acc[0]));
+            asm volatile("" : "+v"(bias_nxt), "+v"(acc));
             bias_cur = bias_nxt;
         }
         X16_T(const unsigned long long s2 = x16_now();)
@@ -208,7 +194,7 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
         if constexpr (SAVE && PACKS) {
             // (unconditional -- dead waves write a dump record -- and reported: the stream's rendezvous waits are counted)
 #ifndef X16_DIAG_NOIMG
-            x16_image_store<PREC>(hout[0][2 * ot], hout[0][2 * ot + 1], sv->tile0 + ot * 2 * X16_PIECE);
+            x16_image_store<PREC>(hout[2 * ot], hout[2 * ot + 1], sv->tile0 + ot * 2 * X16_PIECE);
             ws.note_stores(2);
 #endif
 #ifndef X16_DIAG_NOGATE
@@ -217,7 +203,7 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
             unsigned m = 0;
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-                const s16x8 hv = __builtin_bit_cast(s16x8, hout[0][2 * ot + half]);
+                const s16x8 hv = __builtin_bit_cast(s16x8, hout[2 * ot + half]);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) m |= (hv[j] != 0 ? 1u : 0u) << (8 * half + j);
             }
@@ -231,31 +217,28 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
             }
 #endif
         }
+        if (MODE == MODE_DENSITY) {
+            aux = acc[0];  // row 0 of the tile, valid on lanes with h == 0
+        } else if (MODE == MODE_COMPOSITE) {
+            // weighted RGB_layer_1 activations; two tiles (32 values) feed one butterfly over the samples
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            if (MODE == MODE_DENSITY) {
-                aux[nb] = acc[nb][0];  // row 0 of the tile, valid on lanes with h == 0
-            } else if (MODE == MODE_COMPOSITE) {
-                // weighted RGB_layer_1 activations; two tiles (32 values) feed one butterfly over the samples
+            for (int r = 0; r < 16; ++r) red[(ot & 1) * 16 + r] = fmaxf(acc[r], 0.0f) * aux;
+            if constexpr (SAVE) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) red[nb][(ot & 1) * 16 + r] = fmaxf(acc[nb][r], 0.0f) * aux[nb];
-                if constexpr (SAVE) {
+                for (int half = 0; half < 2; ++half) {
+                    float v[8];
 #pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        float v[8];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = fmaxf(acc[nb][8 * half + r], 0.0f);
-                        __builtin_nontemporal_store(X16<PREC>::pack(v), reinterpret_cast<frag*>(sv->tile0 + (2 * ot + half) * X16_PIECE));
-                    }
-                    ws.note_stores(2);
+                    for (int r = 0; r < 8; ++r) v[r] = fmaxf(acc[8 * half + r], 0.0f);
+                    __builtin_nontemporal_store(X16<PREC>::pack(v), reinterpret_cast<frag*>(sv->tile0 + (2 * ot + half) * X16_PIECE));
                 }
-                if (ot & 1) {
-                    float s = butterfly32(red[nb], c);
-                    // bit-reversed lane index = which of the 32 reduced values this lane ended up with
-                    const int v = ((c & 1) << 4) | ((c & 2) << 2) | (c & 4) | ((c & 8) >> 2) | ((c & 16) >> 4);
-                    const int reg = v & 15, tile = (ot - 1) + (v >> 4);
-                    if (live[nb]) po[nb][tile * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h] = s;
-                }
+                ws.note_stores(2);
+            }
+            if (ot & 1) {
+                float s = butterfly32(red, c);
+                // bit-reversed lane index = which of the 32 reduced values this lane ended up with
+                const int v = ((c & 1) << 4) | ((c & 2) << 2) | (c & 4) | ((c & 8) >> 2) | ((c & 16) >> 4);
+                const int reg = v & 15, tile = (ot - 1) + (v >> 4);
+                if (live) po[tile * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h] = s;
             }
         }
         X16_T(const unsigned long long s3 = x16_now(); ws.t_bias += s1 - s0; ws.t_mfma += (s2 - s1) - (ws.t_rv - rv0); ws.t_epi += s3 - s2;
@@ -279,7 +262,7 @@ struct X16TrainSave {
     unsigned* gates;
 };
 
-template <int PREC, int NB, int WAVES, bool SAVE = false>
+template <int PREC, int WAVES, bool SAVE = false>
 __device__ __forceinline__ void nerf_fwd_x16_body(
     const N3dtGeom& g, const unsigned char* __restrict__ packed, const float* __restrict__ fold, const float* __restrict__ xy,
     const float* __restrict__ R, const float* __restrict__ T, const float* __restrict__ Kinv, const float* __restrict__ t_rand,
@@ -297,31 +280,25 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
     ws.lds_addr0 = (unsigned)(size_t)(LDS_AS unsigned char*)lds + lane * 16;
     ws.wave = wave;
     ws.prologue_issue();  // the sampler / encoder below runs under these loads
-    // per-wave LDS copy of the PE fragments for the skip stage: NB*4 lane-linear 1 KiB pieces
-    unsigned char* pe_lds = lds + X16_NBUF * X16_CH * X16_PIECE + (size_t)wave * NB * 4 * X16_PIECE + lane * 16;
+    // per-wave LDS copy of the PE fragments for the skip stage: 4 lane-linear 1 KiB pieces
+    unsigned char* pe_lds = lds + X16_NBUF * X16_CH * X16_PIECE + (size_t)wave * 4 * X16_PIECE + lane * 16;
 
-    // block bookkeeping: the wave handles NB consecutive 32-sample blocks (all of one frame, host-checked)
-    bool live[NB];
-    float* po[NB];
-    long blk[NB];
-    float dist[NB], zval[NB];
-    frag pe[NB][4];
-    int frame = 0;
-    long ray0 = 0;  // the global ray of the wave's first block (include_vd: NB = 1, so the wave's only ray)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        long bidx = ((long)blockIdx.x * WAVES + wave) * NB + nb;
-        live[nb] = bidx < total_blocks;
-        if (!live[nb]) bidx = total_blocks - 1;
-        blk[nb] = bidx;
-        po[nb] = part + (size_t)bidx * N3DT_PART_STRIDE;
-        const int sb = (int)(bidx % bpr);
-        const long rayg = bidx / bpr;
-        const int ray = (int)(rayg % g.n_rays);
-        const int b = (int)(rayg / g.n_rays);
-        if (nb == 0) frame = b, ray0 = rayg;
+    // block bookkeeping: the wave handles one 32-sample block
+    long blk = (long)blockIdx.x * WAVES + wave;
+    // (wave-uniform, and held as a scalar on purpose: as a lane mask it may be given VCC for the whole stream, and the training
+    // forward's ReLU-gate compares then queue on one SGPR pair -- 550 s_nop per block when it happened)
+    const bool live = __builtin_amdgcn_readfirstlane((int)(blk < total_blocks)) != 0;
+    if (!live) blk = total_blocks - 1;
+    float* const po = part + (size_t)blk * N3DT_PART_STRIDE;
+    float dist, zval;
+    frag pe[4];
+    const int sb = (int)(blk % bpr);
+    const long ray0 = blk / bpr;  // the wave's global ray
+    const int ray = (int)(ray0 % g.n_rays);
+    const int frame = (int)(ray0 / g.n_rays);
+    {
         float p[3];
-        n3dt_sample_point(g, xy, R, T, Kinv, t_rand, b, ray, sb * X16_BS + c, p, dist[nb], zval[nb]);
+        n3dt_sample_point(g, xy, R, T, Kinv, t_rand, frame, ray, sb * X16_BS + c, p, dist, zval);
         // phase in revolutions as hi + lo, so that the 2^k scaling of the encoder stays exact
         float rh[3], rl[3];
 #pragma unroll
@@ -337,37 +314,24 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
             for (int j = 0; j < 8; ++j)
                 v[j] = pe_fast(p[0], p[1], p[2], rh[0], rh[1], rh[2], rl[0], rl[1], rl[2],
                                32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3));
-            pe[nb][ks] = X16<PREC>::pack(v);
-            *reinterpret_cast<frag*>(pe_lds + (nb * 4 + ks) * X16_PIECE) = pe[nb][ks];
+            pe[ks] = X16<PREC>::pack(v);
+            *reinterpret_cast<frag*>(pe_lds + ks * X16_PIECE) = pe[ks];
         }
     }
     const float* fb = fold + (size_t)__builtin_amdgcn_readfirstlane(frame) * N3DT_FOLD_STRIDE;
     // include_vd: the merged RGB stage's bias is per RAY (frame entry + view-direction term; the table sits behind the fold table,
-    // n3dt_layout.h).  The launcher picks the one-block-per-wave tiling then, so the wave has one ray.
+    // n3dt_layout.h)
     const float* b10 = fb + n3dt_bias_offset(10);
-#if defined(X16_DIAG_VD_SELECT_ALL)  // diagnostic builds only (docs/tuning_log.md, round 4: tiling 2 miscompares with these)
-#if defined(X16_DIAG_VD_TERNARY)
-    b10 = g.vd_dim > 0 ? fold + n3dt_rayfold_offset(g.batch) + (size_t)__builtin_amdgcn_readfirstlane((int)ray0) * N3DT_RAYFOLD_STRIDE
-                       : fb + n3dt_bias_offset(10);
-#elif defined(X16_DIAG_VD_NO_RFL)
-    if (g.vd_dim > 0) b10 = fold + n3dt_rayfold_offset(g.batch) + (size_t)ray0 * N3DT_RAYFOLD_STRIDE;
-#else
     if (g.vd_dim > 0) b10 = fold + n3dt_rayfold_offset(g.batch) + (size_t)__builtin_amdgcn_readfirstlane((int)ray0) * N3DT_RAYFOLD_STRIDE;
-#endif
-#else
-    if constexpr (NB == 1) {
-        if (g.vd_dim > 0) b10 = fold + n3dt_rayfold_offset(g.batch) + (size_t)__builtin_amdgcn_readfirstlane((int)ray0) * N3DT_RAYFOLD_STRIDE;
-    }
-#endif
     X16SaveStage<PREC> svs;
     unsigned char* xT_blk = nullptr;  // this block's xT tiles (+ the lane's image offset)
     // record of this block in the saved buffers; a dead wave writes the dump record behind the last block (every wave must
     // issue the stores the stream's counted waits are told about, x16_core.h)
-    const long rec = live[0] ? blk[0] : total_blocks;
+    const long rec = live ? blk : total_blocks;
     if constexpr (SAVE) {
         xT_blk = tsv.xT + (size_t)rec * X16_XT_TILES * 2 * X16_PIECE + x16_image_lane_offset(lane);
-        x16_image_store<PREC>(pe[0][0], pe[0][1], xT_blk);
-        x16_image_store<PREC>(pe[0][2], pe[0][3], xT_blk + 2 * X16_PIECE);
+        x16_image_store<PREC>(pe[0], pe[1], xT_blk);
+        x16_image_store<PREC>(pe[2], pe[3], xT_blk + 2 * X16_PIECE);
     }
     // output tile 0 of hidden layer l inside the block's xT record
     auto sv_hidden = [&](const int l) -> const X16SaveStage<PREC>* {
@@ -380,92 +344,79 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         }
     };
     // how a tile's bias reaches its accumulator (X16TileInit above)
-    constexpr int BIAS = SAVE ? X16_BIAS_LDS_MFMA : (NB == 1 ? X16_BIAS_LDS_C : X16_BIAS_GLOBAL_MFMA);
+    constexpr int BIAS = SAVE ? X16_BIAS_LDS_MFMA : X16_BIAS_LDS_C;
     constexpr int BIAS_DEN = BIAS == X16_BIAS_LDS_C ? X16_BIAS_LDS_C : X16_BIAS_GLOBAL_MFMA;
     // per-wave bias slots in LDS, filled a stage ahead (X16BiasLds above).  Hidden stage k reads slot k & 1; the density tile
     // (64 floats staged, 32 used) and the merged RGB stage's table share slot 0, filled while stage 7 runs: the density
     // stage is a single chunk, too short to stage anything under it.
     X16BiasLds bl{nullptr, 0u};
     constexpr int DEN_AT = 192;  // float offset of the density tile in slot 0, behind the 192 RGB biases
-    if constexpr (BIAS != X16_BIAS_GLOBAL_MFMA) {
-        bl.slots = lds + X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * NB * 4 * X16_PIECE + (size_t)wave * 2 * X16_BIAS_SLOT;
-        bl.addr = (unsigned)(size_t)(LDS_AS unsigned char*)bl.slots + (BIAS == X16_BIAS_LDS_C ? 16 * h : 4 * c);
-        bl.stage_in(fb + n3dt_bias_offset(0), 384, 0, lane);
-    }
+    bl.slots = lds + X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * 4 * X16_PIECE + (size_t)wave * 2 * X16_BIAS_SLOT;
+    bl.addr = (unsigned)(size_t)(LDS_AS unsigned char*)bl.slots + (BIAS == X16_BIAS_LDS_C ? 16 * h : 4 * c);
+    bl.stage_in(fb + n3dt_bias_offset(0), 384, 0, lane);
     // the bias slot of hidden stage k, after staging the table(s) of the stage that follows it
     auto bias_slot = [&](const int k) -> unsigned {
-        if constexpr (BIAS != X16_BIAS_GLOBAL_MFMA) {
-            if (k < 7) {
-                bl.stage_in(fb + n3dt_bias_offset(k + 1), 384, (k + 1) & 1, lane);
-            } else {
-                bl.stage_in(b10, 192, 0, lane);
-                if constexpr (BIAS_DEN == X16_BIAS_LDS_C) bl.stage_in(fb + n3dt_bias_offset(8), 64, 0, lane, DEN_AT);
-            }
+        if (k < 7) {
+            bl.stage_in(fb + n3dt_bias_offset(k + 1), 384, (k + 1) & 1, lane);
+        } else {
+            bl.stage_in(b10, 192, 0, lane);
+            if constexpr (BIAS_DEN == X16_BIAS_LDS_C) bl.stage_in(fb + n3dt_bias_offset(8), 64, 0, lane, DEN_AT);
         }
         return bl.at(k & 1);
     };
     ws.prologue_wait();  // (vmcnt(0): table 0 is in its slot)
-    X16_T(if (wlocal && live[0]) ws.tl = wlocal + (size_t)blk[0] * X16_BS;)
+    X16_T(if (wlocal && live) ws.tl = wlocal + (size_t)blk * X16_BS;)
     X16TileInit ti;
     if constexpr (BIAS == X16_BIAS_LDS_C) ti.template issue<0, 0>(bl.at(0));
 
-    frag ha[NB][24], hb[NB][24];
-    float aux[NB];
+    frag ha[24], hb[24];
+    float aux;
     // FeaExt_module_0 (reference: NetWorks/models.py:69-71)
-    x16_stage<PREC, NB, WAVES, 4, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(0), bias_slot(0), bl.at(1), pe, nullptr, ha, ha, aux, po, live, lane, sv_hidden(0));
+    x16_stage<PREC, WAVES, 4, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(0), bias_slot(0), bl.at(1), pe, nullptr, ha, ha, aux, po, live, lane, sv_hidden(0));
     // FeaExt_module_1..7 with the skip concat after layer 4 (models.py:72-76).  Fully unrolled on purpose: rolling the
     // identical 384->384 layers into a loop (tried: one-layer body + register copy, two-layer ping-pong body) makes the
     // register allocator spill 120-270 VGPRs across the back edge and runs 1.7x slower.
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(1), bias_slot(1), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(1));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(2), bias_slot(2), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(2));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(3), bias_slot(3), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(3));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(4), bias_slot(4), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(4));
-    x16_stage<PREC, NB, WAVES, 28, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(5), bias_slot(5), bl.at(0), pe, pe_lds, ha, hb, aux, po, live, lane, sv_hidden(5));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(6), bias_slot(6), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(6));
-    x16_stage<PREC, NB, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(7), bias_slot(7), bl.at(0, DEN_AT), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(7));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(1), bias_slot(1), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(1));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(2), bias_slot(2), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(2));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(3), bias_slot(3), bl.at(0), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(3));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(4), bias_slot(4), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(4));
+    x16_stage<PREC, WAVES, 28, 4, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(5), bias_slot(5), bl.at(0), pe, pe_lds, ha, hb, aux, po, live, lane, sv_hidden(5));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(6), bias_slot(6), bl.at(1), pe, nullptr, hb, ha, aux, po, live, lane, sv_hidden(6));
+    x16_stage<PREC, WAVES, 24, 0, 12, MODE_HIDDEN, SAVE, BIAS, 0, true>(ws, ti, fb + n3dt_bias_offset(7), bias_slot(7), bl.at(0, DEN_AT), pe, nullptr, ha, hb, aux, po, live, lane, sv_hidden(7));
     // density head on h7 (models.py:78,84); the bias rides in the accumulator.  Its one tile is tile 96 of the running count
     // and fetches the first RGB tile's bias, which therefore starts on parity 1.
-    x16_stage<PREC, NB, WAVES, 24, 0, 1, MODE_DENSITY, false, BIAS_DEN, 0, true>(ws, ti, fb + n3dt_bias_offset(8), bl.at(0, DEN_AT), bl.at(0), pe, nullptr, hb, ha, aux, po, live, lane);
+    x16_stage<PREC, WAVES, 24, 0, 1, MODE_DENSITY, false, BIAS_DEN, 0, true>(ws, ti, fb + n3dt_bias_offset(8), bl.at(0, DEN_AT), bl.at(0), pe, nullptr, hb, ha, aux, po, live, lane);
     // alpha, in-block transmittance and weights (reference: NetWorks/utils.py:273-289)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        float sp = __shfl(aux[nb], c, 64);  // row 0 lives on the h == 0 half
+    {
+        float sp = __shfl(aux, c, 64);  // row 0 lives on the h == 0 half
         if constexpr (SAVE) {
-            if (live[nb] && h == 0) {
-                tsv.geo[(size_t)blk[nb] * 64 + c] = sp;
-                tsv.geo[(size_t)blk[nb] * 64 + 32 + c] = dist[nb];
+            if (live && h == 0) {
+                tsv.geo[(size_t)blk * 64 + c] = sp;
+                tsv.geo[(size_t)blk * 64 + 32 + c] = dist;
             }
         }
         float sigma = fmaxf(sp, 0.0f);
-#if defined(X16_DIAG_REMASK_DEAD_LANES)
-        // diagnostic builds only (docs/tuning_log.md, round 4: the cause of tiling 2's garbage): the lanes past N_s get their
-        // dist = 0 / zval = 0 again HERE, from the sample index, instead of trusting the registers that carried them from the
-        // prologue -- hipcc parked those in AGPRs with a copy that ran under the sampler's reduced lane mask
-        // (the values are made opaque first: the compiler KNOWS they are 0 in those lanes and folds a plain select away)
-        asm volatile("" : "+v"(dist[nb]), "+v"(zval[nb]));
-        if ((int)(blk[nb] % bpr) * X16_BS + c >= g.n_samples) dist[nb] = 0.0f, zval[nb] = 0.0f;
-#endif
-        float alpha = 1.0f - expf(-sigma * dist[nb]);
+        float alpha = 1.0f - expf(-sigma * dist);
         float x = 1.0f - alpha + 1e-10f;
         float Tl = n3dt_exclusive_prod<32>(x, c);
         float w = alpha * Tl;
-        float s0 = w, s1 = w * zval[nb];
+        float s0 = w, s1 = w * zval;
 #pragma unroll
         for (int off = 16; off > 0; off >>= 1) {
             s0 += __shfl_xor(s0, off, 32);
             s1 += __shfl_xor(s1, off, 32);
         }
         float tprod = __shfl(Tl * x, 31, 32);
-        if (live[nb] && lane == 0) {
-            po[nb][N3DT_G + 0] = s0;
-            po[nb][N3DT_G + 1] = s1;
-            po[nb][N3DT_G + 2] = tprod;
-            po[nb][N3DT_G + 3] = 0.0f;
+        if (live && lane == 0) {
+            po[N3DT_G + 0] = s0;
+            po[N3DT_G + 1] = s1;
+            po[N3DT_G + 2] = tprod;
+            po[N3DT_G + 3] = 0.0f;
         }
 #ifndef X16_STAMP
-        if (live[nb] && wlocal && h == 0) wlocal[(size_t)blk[nb] * X16_BS + c] = w;
+        if (live && wlocal && h == 0) wlocal[(size_t)blk * X16_BS + c] = w;
 #endif
-        aux[nb] = w;
+        aux = w;
     }
     // RGB_layer_0 -> RGB_layer_1 as ONE merged 192 x 384 layer on h7 (no activation sits between them, models.py:79-81;
     // merged matrix and bias built by pack / fold), relu, weighted by the sample weights and reduced over the samples
@@ -473,11 +424,11 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         svs.tile0 = tsv.gS + (size_t)rec * 12 * X16_PIECE + lane * 16;
         svs.gate0 = nullptr;
     }
-    x16_stage<PREC, NB, WAVES, 24, 0, 6, MODE_COMPOSITE, SAVE, BIAS, 1, false>(ws, ti, b10, bl.at(0), 0u, pe, nullptr, hb, ha, aux, po, live, lane,
+    x16_stage<PREC, WAVES, 24, 0, 6, MODE_COMPOSITE, SAVE, BIAS, 1, false>(ws, ti, b10, bl.at(0), 0u, pe, nullptr, hb, ha, aux, po, live, lane,
                                                                                SAVE ? &svs : nullptr);
 #ifdef X16_STAMP
-    if (wlocal && lane == 0 && live[0]) {
-        float* dbg = wlocal + (size_t)blk[0] * X16_BS;
+    if (wlocal && lane == 0 && live) {
+        float* dbg = wlocal + (size_t)blk * X16_BS;
         dbg[0] = (float)ws.t_bias;
         dbg[1] = (float)ws.t_mfma;
         dbg[2] = (float)ws.t_epi;
@@ -486,17 +437,17 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
 #endif
 }
 
-template <int PREC, int NB, int WAVES>
+template <int PREC, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, 1) void nerf_fwd_x16_kernel(
     N3dtGeom g, const unsigned char* __restrict__ packed, const float* __restrict__ fold, const float* __restrict__ xy,
     const float* __restrict__ R, const float* __restrict__ T, const float* __restrict__ Kinv, const float* __restrict__ t_rand,
     float* __restrict__ part, float* __restrict__ wlocal, int bpr, long total_blocks) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    nerf_fwd_x16_body<PREC, NB, WAVES>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, bpr, total_blocks, lds, wave);
+    nerf_fwd_x16_body<PREC, WAVES>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, bpr, total_blocks, lds, wave);
 }
 
-// Training forward (bf16, one block per wave): the same body, leaving the activations behind (X16TrainSave)
+// Training forward (bf16): the same body, leaving the activations behind (X16TrainSave)
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64, 1) void nerf_fwd_x16_train_kernel(
     N3dtGeom g, const unsigned char* __restrict__ packed, const float* __restrict__ fold, const float* __restrict__ xy,
@@ -504,7 +455,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void nerf_fwd_x16_train_kernel(
     float* __restrict__ part, float* __restrict__ wlocal, int bpr, long total_blocks, X16TrainSave tsv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    nerf_fwd_x16_body<N3DT_BF16, 1, WAVES, true>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, bpr, total_blocks, lds, wave,
+    nerf_fwd_x16_body<N3DT_BF16, WAVES, true>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, bpr, total_blocks, lds, wave,
                                                         tsv);
 }
 
@@ -526,16 +477,16 @@ extern "C" void n3dt_launch_nerf_fwd_x16_train(const N3dtGeom* g, const void* pa
                        R, T, Kinv, t_rand, part, wlocal, bpr, total, tsv);
 }
 
-template <int PREC, int NB, int WAVES>
+template <int PREC>
 static void launch_x16(const N3dtGeom* g, const void* packed, const float* fold, const float* xy, const float* R, const float* T,
                        const float* Kinv, const float* t_rand, float* part, float* wlocal, hipStream_t stream) {
+    constexpr int WAVES = 8;  // two waves per SIMD, <= 256 registers each
     const int bpr = (g->n_samples + X16_BS - 1) / X16_BS;
     const long total = (long)g->batch * g->n_rays * bpr;
-    const long per_wg = (long)WAVES * NB;
-    const int grid = (int)((total + per_wg - 1) / per_wg);
-    // weight ring + the waves' PE copies + their two bias slots: 72 + 32 + 24 KiB with 8 waves, one workgroup per CU
-    const size_t lds_bytes = X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * NB * 4 * X16_PIECE + (size_t)WAVES * 2 * X16_BIAS_SLOT;
-    auto kern = nerf_fwd_x16_kernel<PREC, NB, WAVES>;
+    const int grid = (int)((total + WAVES - 1) / WAVES);
+    // weight ring + the waves' PE copies + their two bias slots: 72 + 32 + 24 KiB, one workgroup per CU
+    const size_t lds_bytes = X16_NBUF * X16_CH * X16_PIECE + (size_t)WAVES * 4 * X16_PIECE + (size_t)WAVES * 2 * X16_BIAS_SLOT;
+    auto kern = nerf_fwd_x16_kernel<PREC, WAVES>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds_bytes, stream, *g, reinterpret_cast<const unsigned char*>(packed),
                        fold, xy, R, T, Kinv, t_rand, part, wlocal, bpr, total);
@@ -544,29 +495,6 @@ static void launch_x16(const N3dtGeom* g, const void* packed, const float* fold,
 extern "C" void n3dt_launch_nerf_fwd_x16(const N3dtGeom* g, int precision, const void* packed, const float* fold, const float* xy,
                                          const float* R, const float* T, const float* Kinv, const float* t_rand, float* part,
                                          float* wlocal, hipStream_t stream) {
-    // two tilings of the same kernel: 8 waves x 32 samples (2 waves per SIMD, <= 256 registers) or 4 waves x 64 samples
-    // (one wave per SIMD with the whole 512-register file: each weight fragment read from LDS feeds two MFMAs)
-    // Tiling 2 is WITHDRAWN from the run-time switch (round 4): a diagnostic build whose only difference is how the RGB stage's
-    // bias pointer is selected (-DX16_DIAG_VD_SELECT_ALL -DX16_DIAG_VD_TERNARY) miscompares on `tiny_train` in this tiling, with
-    // results that change from run to run on one binary -- i.e. the 4-wave instantiation has a latent ordering hazard that the
-    // shipped code generation happens not to expose (the hazard scanners find nothing in either build; tools/tiling_probe.py,
-    // docs/tuning_log.md).  It measured equal to the default at best, so it is not worth the risk: N3DT_X16_TILING=2 now needs
-    // N3DT_X16_TILING2_DIAG=1 as well and is meant for that investigation only.  The default tiling (8 waves x 32 samples) is the
-    // one every parity test, sweep and bench of four rounds ran on.
-    static const int wide = [] {
-        const char* e = getenv("N3DT_X16_TILING");
-        const char* d = getenv("N3DT_X16_TILING2_DIAG");
-        const int t = e ? atoi(e) : X16_DEFAULT_TILING;
-        return (t == 2 && !(d && atoi(d) == 1)) ? 1 : t;
-    }();
-    const long blocks = (long)g->batch * g->n_rays * ((g->n_samples + X16_BS - 1) / X16_BS);
-    // (include_vd: the bias of the RGB stage is per ray, so a wave must not span two rays: the one-block-per-wave tiling)
-    const bool use_wide = wide == 2 && g->vd_dim == 0 && (((long)g->n_rays * ((g->n_samples + X16_BS - 1) / X16_BS)) % 2 == 0) && blocks >= 2;
-    if (precision == N3DT_BF16) {
-        if (use_wide) launch_x16<N3DT_BF16, 2, 4>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
-        else launch_x16<N3DT_BF16, 1, 8>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
-    } else {
-        if (use_wide) launch_x16<N3DT_F16, 2, 4>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
-        else launch_x16<N3DT_F16, 1, 8>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
-    }
+    if (precision == N3DT_BF16) launch_x16<N3DT_BF16>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
+    else launch_x16<N3DT_F16>(g, packed, fold, xy, R, T, Kinv, t_rand, part, wlocal, stream);
 }

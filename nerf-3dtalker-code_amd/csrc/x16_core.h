@@ -26,9 +26,6 @@ struct X16<N3DT_BF16> {
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
-    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
     static __device__ __forceinline__ frag pack(const float* v) {
         frag f;
 #pragma unroll
@@ -69,9 +66,6 @@ struct X16<N3DT_F16> {
     typedef f16x8 frag;
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     }
     static __device__ __forceinline__ frag pack(const float* v) {
         frag f;
@@ -117,9 +111,6 @@ struct X16<N3DT_F16> {
 //   measured perf-neutral or worse in round 1 -- DESIGN 3.1 log items 3, 8, 11 -- and are gone from the source.)
 #ifndef X16_DEPTH
 #define X16_DEPTH 3  // fragments in flight per wave: 3 measured 0.6 % faster than 2 for the render kernel (same box), 4 spills it
-#endif
-#ifndef X16_DEFAULT_TILING
-#define X16_DEFAULT_TILING 1  // 1: 8 waves x 32 samples, 2: 4 waves x 64 samples (N3DT_X16_TILING overrides at run time)
 #endif
 #ifndef X16_NBUF
 #define X16_NBUF 3  // chunk buffers of the ring (4 measured no faster for the render kernel and the renderer blocks)

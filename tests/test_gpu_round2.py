@@ -195,27 +195,6 @@ def test_fused_loss_tail_against_the_reference(case):
                           torch.from_numpy(g[k + "mask"]).to(dev()))
 
 
-@pytest.mark.parametrize("tiling", ["3"])
-def test_run_time_kernel_variants_match_the_default(tiling, tmp_path):
-    """N3DT_X16_TILING = 3 (16x16x32 MFMA, nerf_fwd_x16b.hip) ships in the library as a run-time switch: against the default
-    tiling and against the reference fixtures (cfg1: 32 samples = one block per ray; tiny_train: ragged 8-sample blocks,
-    jitter).  The switch is read once per process, hence child processes.  (Tiling 2, 4 waves x 64 samples, was withdrawn in
-    round 4: a diagnostic build exposed a latent ordering hazard in that instantiation -- nerf_fwd_x16.hip, tools/tiling_probe.py.)"""
-    tool = os.path.join(REPO, "tools", "variant_check.py")
-    for name in ("cfg1", "tiny_train"):
-        outs = {}
-        for t in ("1", tiling):
-            out = str(tmp_path / ("%s_t%s.npz" % (name, t)))
-            subprocess.run([sys.executable, tool, name, "bf16", out], check=True, env=dict(os.environ, N3DT_X16_TILING=t), timeout=600)
-            outs[t] = np.load(out)
-        a, b = outs["1"], outs[tiling]
-        g, m = load_golden(name)
-        # same products in a different association order: bf16 rounding of the activations differs in the last bit
-        assert np.abs(a["fg_feat"] - b["fg_feat"]).max() <= 5e-3 and np.abs(a["merge_img"] - b["merge_img"]).max() <= 1e-3
-        ref = g["merge_img"] if "merge_img" in g else g["merge_img_q16"].astype(np.float32) / 65535.0
-        assert np.abs(b["merge_img"] - ref).max() <= RGB_TOL["bf16"], (name, tiling)
-
-
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_packed_weight_cache_follows_every_kind_of_weight_write(precision):
     """the packed (MFMA-ordered) weight copies are cached per version counter.  optimizer steps, `copy_` under

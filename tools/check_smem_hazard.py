@@ -17,7 +17,7 @@ region's lanes only and the other lanes of the AGPR keep whatever it held: `dist
 kernel of every file, not only the stream kernels.
 
 The scan runs on build/<name>.s, the device assembly the Makefile keeps from the compile that produced the shipped objects
-(same FLAGS, -save-temps=obj), for every source file: all tilings and the training kernels included.
+(same FLAGS, -save-temps=obj), for every source file: the inference and the training kernels.
 
 usage: python tools/check_smem_hazard.py   or   make -C nerf-3dtalker-code_amd check     (exit code 1 on a finding)
 """

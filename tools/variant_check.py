@@ -1,4 +1,4 @@
-"""Render one fixture geometry with whatever kernel variant the environment selects (N3DT_X16_TILING, N3DT_NR_FUSED,
+"""Render one fixture geometry with whatever renderer variant the environment selects (N3DT_NR_FUSED, N3DT_NR_LAT,
 N3DT_GRAPH ... are read once per process, hence a child process per variant) and save the images / feature maps.
 usage: variant_check.py <fixture name> <precision> <out.npz>"""
 import os
@@ -31,4 +31,4 @@ with torch.no_grad():
 torch.cuda.synchronize()
 np.savez(out, fg_feat=f["fg_feat"].cpu().numpy(), bg_alpha=f["bg_alpha"].cpu().numpy(), weight=f["weight"].cpu().numpy(),
          merge_img=o["merge_img"].cpu().numpy(), bg_img=o["bg_img"].cpu().numpy())
-print("variant_check: %s %s tiling=%s -> %s" % (name, precision, os.environ.get("N3DT_X16_TILING", "default"), out))
+print("variant_check: %s %s %s -> %s" % (name, precision, " ".join("%s=%s" % kv for kv in sorted(os.environ.items()) if kv[0].startswith("N3DT_NR_")) or "defaults", out))
