@@ -303,7 +303,7 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         float rh[3], rl[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const float inv2pi_hi = 0.15915494f, inv2pi_lo = 6.2195e-09f;  // 1/(2 pi) split
+            const float inv2pi_hi = 0.15915494f, inv2pi_lo = 6.4206383e-09f;  // 1/(2 pi) = 0.159154936671257 (the float) + lo
             rh[i] = p[i] * inv2pi_hi;
             rl[i] = fmaf(p[i], inv2pi_hi, -rh[i]) + p[i] * inv2pi_lo;
         }

@@ -382,8 +382,20 @@ __device__ __forceinline__ float pe_fast(const float p0, const float p1, const f
     const int k = cc / 6, w = cc % 6, dim = w >= 3 ? w - 3 : w;
     const float sc = (float)(1 << k);
     const float hi = pick3(dim, h0, h1, h2), lo = pick3(dim, l0, l1, l2);
-    const float r = __builtin_amdgcn_fractf(hi * sc) + lo * sc + (w >= 3 ? 0.25f : 0.0f);  // cos x = sin(x + pi/2)
-    const float sv = __builtin_amdgcn_sinf(r);
+    // The phase is folded to [-1/4, 1/4] revolutions BEFORE the low part is added, every step of the fold exact in fp32
+    // (hi * sc and lo * sc scale by a power of two; t is a fraction; 1/2 - |t| and 1/4 - |t| subtract numbers within a factor of
+    // two of each other wherever the result is near zero): next to a zero crossing the argument of v_sin_f32 is then small and
+    // keeps its low bits.  As fract(hi * sc) + lo * sc (+ 1/4) the sum was rounded at the scale of 1/2 or 1 -- 3e-8 revolutions,
+    // 2e-7 in the sine, three bf16 ulps of a value of 1e-5 (tests/test_gpu_x16_stagewise.py: the PE tiles).
+    const float u = __builtin_amdgcn_fractf(hi * sc);
+    const float t = u - (u >= 0.5f ? 1.0f : 0.0f);                 // [-1/2, 1/2)
+    const float at = __builtin_fabsf(t), ls = lo * sc;
+    const float sl = t < 0.0f ? -ls : ls;                         // the low part, signed along |t|
+    const bool far = at > 0.25f;
+    const float ts = far ? 0.5f - at : at;                        // sin(2 pi t) = sign(t) sin(2 pi ts), ts in [0, 1/4]
+    const float rs = (t < 0.0f ? -1.0f : 1.0f) * (ts + (far ? -sl : sl));
+    const float rc = (0.25f - at) - sl;                           // cos(2 pi x) = sin(2 pi (1/4 - |x|))
+    const float sv = __builtin_amdgcn_sinf(w >= 3 ? rc : rs);
     const float raw = pick3(ch, p0, p1, p2);
     return ch < 3 ? raw : (ch >= N3DT_PE_DIM ? 0.0f : sv);
 }
