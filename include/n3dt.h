@@ -218,6 +218,11 @@ int n3dt_mlp_points(const N3dtGeom* g, size_t m, const N3dtMlpParams* p, const f
                     const float* embed_vds, float* rgb, float* density, void* workspace, size_t workspace_bytes, void* stream);
 int n3dt_composite(int batch, int n_rays, int n_samples, int channels, const float* rgb, const float* density, const float* z_dists,
                    const float* zvals, float* feat, float* bg_alpha, float* depth, float* weight, void* stream);
+/* The rounding step of the fused 16-bit kernels on its own (an addition: the ABI version stays 5): in [n] floats -> out [n] 16-bit
+ * values (bf16 for N3DT_BF16, f16 for N3DT_F16; no other precision), one wave per 512 values, every lane packing eight consecutive
+ * values into one MFMA fragment.  form 0: through the kernels' own pack (two values per conversion instruction); form 1: through
+ * an element-wise cast kept in this probe only -- the two must agree bit for bit.  n: a multiple of 512. */
+int n3dt_x16_pack_probe(int precision, int form, size_t n, const float* in, uint16_t* out, void* stream);
 
 /* ---- 2-D neural renderer: a8..a10 ----------------------------------------------------------------
  * Replaces NeuralRenderer.forward (NetWorks/neural_renderer.py:72-91) including

@@ -33,6 +33,7 @@ void n3dt_launch_mlp_points(const N3dtGeom*, size_t, const N3dtMlpParams*, const
                             hipStream_t);
 void n3dt_launch_composite(int, int, int, int, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
                            hipStream_t);
+void n3dt_launch_x16_pack_probe(int, int, size_t, const float*, unsigned short*, hipStream_t);
 void n3dt_launch_fine_sample(const N3dtGeom*, int, const float*, const float*, const float*, const float*, float*, hipStream_t);
 void n3dt_launch_nerf_fwd_f32(const N3dtGeom*, const N3dtMlpParams*, const void*, const float*, const float*, const float*,
                               const float*, const float*, const float*, float*, float*, hipStream_t);
@@ -356,6 +357,15 @@ extern "C" int n3dt_composite(int batch, int n_rays, int n_samples, int channels
     n3dt_launch_composite(batch, n_rays, n_samples, channels, rgb, density, z_dists, zvals, feat, bg_alpha, depth, weight,
                           (hipStream_t)stream);
     return check_hip("n3dt_composite");
+}
+
+extern "C" int n3dt_x16_pack_probe(int precision, int form, size_t n, const float* in, uint16_t* out, void* stream) {
+    if (precision != N3DT_BF16 && precision != N3DT_F16) return fail(N3DT_EINVAL, "n3dt_x16_pack_probe: precision must be N3DT_BF16 or N3DT_F16");
+    if (form != 0 && form != 1) return fail(N3DT_EINVAL, "n3dt_x16_pack_probe: form must be 0 (pack) or 1 (element-wise cast)");
+    if (n < 512 || n % 512 != 0 || n / 512 > 0x7fffffffu) return fail(N3DT_EINVAL, "n3dt_x16_pack_probe: n must be a multiple of 512, at most 2^40");
+    if (!in || !out) return fail(N3DT_EINVAL, "n3dt_x16_pack_probe: NULL argument");
+    n3dt_launch_x16_pack_probe(precision, form, n, in, out, (hipStream_t)stream);
+    return check_hip("n3dt_x16_pack_probe");
 }
 
 extern "C" int n3dt_fine_sample(const N3dtGeom* g, int n_fine, const float* weight, const float* T, const float* t_rand, const float* u,

@@ -101,10 +101,7 @@ __device__ __forceinline__ void nrf_pack_body(const int C, const int CO, const i
         }
         v[j] = w;
     }
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        o[j] = precision == N3DT_BF16 ? __builtin_bit_cast(unsigned short, (__bf16)v[j]) : __builtin_bit_cast(unsigned short, (_Float16)v[j]);
+    const u16x8 o = precision == N3DT_BF16 ? x16_pack8<N3DT_BF16, u16x8>(v) : x16_pack8<N3DT_F16, u16x8>(v);  // two values per conversion
     *reinterpret_cast<u16x8*>(out + (size_t)P * X16_PIECE + lane * 16) = o;
 }
 __global__ void nrf_pack_kernel(const int C, const int CO, const int precision, const float* __restrict__ W1, const float* __restrict__ b1,

@@ -8,6 +8,7 @@
 // address the sub-modules directly (SURVEY 8b "inner seam kept addressable"): exact fp32, unfused, inference only.
 #include "gemm32.h"
 #include "n3dt_device.h"
+#include "x16_core.h"
 
 // ---- GenSamplePoints ---------------------------------------------------------------------------
 // pts [B,3,Nr,Ns], zvals / z_dists [B,1,Nr,Ns], ray_d [B,3,Nr], ray_l [B,1,Nr]   (any output may be NULL)
@@ -260,4 +261,39 @@ extern "C" void n3dt_launch_composite(int B, int Nr, int Ns, int C, const float*
     const long rays = (long)B * Nr;
     hipLaunchKernelGGL(seam_composite_kernel, dim3((unsigned)((rays + 3) / 4)), dim3(256), sizeof(float) * 4 * Ns, s, B, Nr, Ns, C, rgb,
                        density, z_dists, zvals, feat, bg_alpha, depth, weight);
+}
+
+// ---- X16<PREC>::pack on its own -----------------------------------------------------------------------
+// in [n] floats -> out [n] 16-bit values, one wave per 512 values: lane l packs the eight values 8 l .. 8 l + 7 of its wave's 512
+// into one fragment and stores it.  FORM 0: X16<PREC>::pack, what every fused 16-bit kernel rounds its accumulators with.
+// FORM 1: the element-wise cast that pack used to be (one conversion per value), kept HERE only, as the yardstick the pairwise
+// form is compared against bit for bit.
+template <int PREC, int FORM>
+__global__ void __launch_bounds__(64) x16_pack_probe_kernel(size_t n, const float* __restrict__ in, unsigned short* __restrict__ out) {
+    typedef typename X16<PREC>::frag frag;
+    typedef typename std::conditional<PREC == N3DT_BF16, __bf16, _Float16>::type elem;
+    const size_t base = (size_t)blockIdx.x * 512 + (size_t)threadIdx.x * 8;
+    if (base + 8 > n) return;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = in[base + j];
+    frag f;
+    if constexpr (FORM == 0) {
+        f = X16<PREC>::pack(v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (elem)v[j];
+    }
+    *reinterpret_cast<frag*>(out + base) = f;
+}
+
+extern "C" void n3dt_launch_x16_pack_probe(int precision, int form, size_t n, const float* in, unsigned short* out, hipStream_t s) {
+    const dim3 grid((unsigned)(n / 512)), block(64);
+    if (precision == N3DT_BF16) {
+        if (form == 0) hipLaunchKernelGGL((x16_pack_probe_kernel<N3DT_BF16, 0>), grid, block, 0, s, n, in, out);
+        else hipLaunchKernelGGL((x16_pack_probe_kernel<N3DT_BF16, 1>), grid, block, 0, s, n, in, out);
+    } else {
+        if (form == 0) hipLaunchKernelGGL((x16_pack_probe_kernel<N3DT_F16, 0>), grid, block, 0, s, n, in, out);
+        else hipLaunchKernelGGL((x16_pack_probe_kernel<N3DT_F16, 1>), grid, block, 0, s, n, in, out);
+    }
 }

@@ -9,6 +9,11 @@
 #include "n3dt_layout.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 x16_bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 x16_f16x2 __attribute__((ext_vector_type(2)));
+typedef float x16_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned x16_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned x16_u32x4 __attribute__((ext_vector_type(4)));
 
 #define X16_BS 32
 #define X16_CH 24                      // pieces per chunk (24 KiB)
@@ -18,6 +23,28 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 
+// Two floats -> one dword of two 16-bit values (a in the low half), round to nearest even: ONE v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32
+// with both sources live.  Element-wise casts ((__bf16)v[j] in a loop, or an 8-wide __builtin_convertvector) are scalarised by
+// hipcc into one conversion per VALUE -- the packed instruction with a dead second source, or v_cvt_f16_f32 -- plus a v_perm_b32 /
+// v_pack_b32_f16 per dword to glue the halves together: 24 VALU instructions per 8-value fragment where 4 suffice.  The 2-wide
+// vector conversion is the form it keeps whole.  Same rounding instruction, so every value converts to the same bits.
+template <int PREC>
+__device__ __forceinline__ unsigned x16_cvt2(const float a, const float b) {
+    const x16_f32x2 p = {a, b};
+    if constexpr (PREC == N3DT_BF16)
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(p, x16_bf16x2));
+    else
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(p, x16_f16x2));
+}
+// eight floats -> one fragment, element j = v[j]
+template <int PREC, class FRAG>
+__device__ __forceinline__ FRAG x16_pack8(const float* v) {
+    x16_u32x4 w;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = x16_cvt2<PREC>(v[2 * j], v[2 * j + 1]);
+    return __builtin_bit_cast(FRAG, w);
+}
+
 template <int PREC>
 struct X16;
 template <>
@@ -26,12 +53,7 @@ struct X16<N3DT_BF16> {
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
-    static __device__ __forceinline__ frag pack(const float* v) {
-        frag f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = (__bf16)v[j];
-        return f;
-    }
+    static __device__ __forceinline__ frag pack(const float* v) { return x16_pack8<N3DT_BF16, frag>(v); }
     // ReLU on the packed 16-bit values: a signed 16-bit max with 0 (v_pk_max_i16) clears exactly
     // the negative floats, and rounding commutes with it
     // `lo` = 0: ReLU;  lo = -32768 (the most negative 16-bit pattern): identity -- lets one rolled loop body serve
@@ -67,12 +89,7 @@ struct X16<N3DT_F16> {
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
     }
-    static __device__ __forceinline__ frag pack(const float* v) {
-        frag f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = (_Float16)v[j];
-        return f;
-    }
+    static __device__ __forceinline__ frag pack(const float* v) { return x16_pack8<N3DT_F16, frag>(v); }
     // `lo` = 0: ReLU;  lo = -32768 (the most negative 16-bit pattern): identity -- lets one rolled loop body serve
     // both the ReLU layers and the linear RGB_layer_0
     static __device__ __forceinline__ frag relu(frag f, short lo) {
@@ -404,9 +421,23 @@ enum { MODE_HIDDEN = 0, MODE_LINEAR = 1, MODE_DENSITY = 2, MODE_COMPOSITE = 3 };
 
 
 // sum over the 32 lanes of a half-wave of 32 per-lane values: lane c ends with value index rev5(c)
+// Step 1 (partner lane c ^ 16) is a row swap between two registers: v_permlane16_swap_b32 trades the odd 16-lane rows of v[2i]
+// against the even rows of v[2i + 1], after which v[2i] + v[2i + 1] is own + partner's v[2i] on the lanes with bit 4 clear and
+// partner's + own v[2i + 1] on the others -- the sums the select / ds_bpermute form makes, operands commuted on the upper rows
+// (fp32 addition commutes: same bits), without the two selects and the LDS permute per pair.  Inline asm, not
+// __builtin_amdgcn_permlane16_swap: with both results feeding one add this hipcc emits `v_add v, a, a` (the second result is
+// lost).  The s_nop 1 in front is the two wait states gfx950 wants between a VALU write of either operand and the swap's read
+// (the compiler cannot see into the string); the one behind, in front of the add that reads both results, is caution only
+// (no documented need; the form was measured with it).
 __device__ __forceinline__ float butterfly32(float (&v)[32], const int c) {
 #pragma unroll
-    for (int step = 0; step < 5; ++step) {
+    for (int i = 0; i < 16; ++i) {
+        float a = v[2 * i], b = v[2 * i + 1];
+        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+        v[i] = a + b;
+    }
+#pragma unroll
+    for (int step = 1; step < 5; ++step) {
         const int m = 16 >> step;
         const bool bit = (c & m) != 0;
         const int n = 32 >> step;
@@ -463,8 +494,6 @@ __device__ __forceinline__ unsigned x16_tr_lane_offset_natural(const int lane) {
 // The reads are issued from inline asm (x16_tr_issue) and retired by ONE s_waitcnt (x16_tr_settle) that names every destination:
 // through the builtin hipcc orders them behind the LDS-DMA stream in flight (s_waitcnt vmcnt(0) in front of the first read of
 // every stage -- the stages still loading are then waited for as well, and the pipeline is one stage deep).
-typedef unsigned x16_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned x16_u32x4 __attribute__((ext_vector_type(4)));
 template <int OFF>
 __device__ __forceinline__ void x16_tr_issue(x16_u32x2& d, const unsigned lds_addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(lds_addr), "i"(OFF) : "memory");

@@ -203,6 +203,16 @@ def embed_freqs(pts, n_freqs):
     return pe
 
 
+def x16_pack_probe(x, precision, form=0):
+    """The fused 16-bit kernels' rounding step on its own (n3dt_x16_pack_probe): x fp32, numel a multiple of 512 -> the same shape
+    in bf16 / fp16.  form 0: X16<PREC>::pack; form 1: the element-wise cast kept in the probe kernel."""
+    x = _f32c(x)
+    prec = _lib.PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    out = torch.empty(x.shape, dtype=torch.bfloat16 if prec == _lib.BF16 else torch.float16, device=x.device)
+    check(lib().n3dt_x16_pack_probe(prec, int(form), x.numel(), _ptr(x), _ptr(out), _stream()), "n3dt_x16_pack_probe")
+    return out
+
+
 def ray_vd_bias(geom, w_rgb1, xy, R, Kinv, out=None):
     """include_vd: the per-ray bias of RGB_layer_1 from the ray direction (n3dt_ray_vd_bias).  w_rgb1: the layer's FULL 2-D
     weight [192, 384 + 27 + appea_dim] (contiguous); its columns 384 .. 410 are read in place."""
