@@ -23,6 +23,9 @@
 #ifndef X16_SAVE_DEPTH
 #define X16_SAVE_DEPTH 3  // fragments in flight per wave in the training forward (X16_DEPTH for the others)
 #endif
+#ifndef X16_FWD_ISSUE
+#define X16_FWD_ISSUE 0, 1, 2  // x16_core.h X16Issue: the slots of the three pieces a wave stages per chunk
+#endif
 // One stage: out[N x 32] = W'[N x K] . in[K x 32] + bias (+ activation), NT = N/32 out tiles.
 // The KPE leading k-steps take their B operand from the wave's PE fragments: registers (pe_reg,
 // stage L0) or the wave's LDS copy (pe_lds, skip stage L5); the rest come from hin.
@@ -273,9 +276,17 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
     const int c = lane & 31, h = lane >> 5;
 
     // (the training forward's prefetch depth is its own switch: depth 2 frees four registers and measured the same, 1.32 against 1.32 ms)
-    typedef WeightStream<PREC, WAVES, X16_NCHUNK, X16_NBUF, SAVE ? X16_SAVE_DEPTH : X16_DEPTH> WS;
+    // (the inference kernels issue the stream's LDS-DMA pieces between the MFMAs, X16_FWD_ISSUE; the training forward keeps them
+    // behind the barrier: its A/B has not been run)
+    typedef WeightStream<PREC, WAVES, X16_NCHUNK, X16_NBUF, SAVE ? X16_SAVE_DEPTH : X16_DEPTH,
+                         std::conditional_t<SAVE, X16Issue<>, X16Issue<X16_FWD_ISSUE>>> WS;
     WS ws;
-    ws.gsrc = packed + (size_t)wave * WS::PPW * X16_PIECE + lane * 16;
+    if constexpr (SAVE) {
+        ws.gsrc = packed + (size_t)wave * WS::PPW * X16_PIECE + lane * 16;
+    } else {  // scalar base + lane offset (X16_FWD_ISSUE)
+        ws.gsrc = packed + (size_t)wave * WS::PPW * X16_PIECE;
+        ws.voff = lane * 16;
+    }
     ws.ring = lds;
     ws.lds_addr0 = (unsigned)(size_t)(LDS_AS unsigned char*)lds + lane * 16;
     ws.wave = wave;

@@ -122,8 +122,9 @@ struct X16<N3DT_F16> {
 // X16_DEPTH fragments so that the matrix pipe never waits for an LDS round trip:
 //   * the prologue stages chunks 0 and 1 and meets once;
 //   * rendezvous n (one workgroup barrier) is met X16_DEPTH pieces BEFORE the end of chunk n: it makes chunk
-//     n+1 visible (issued at rendezvous n-1) and issues chunk n+2 into the buffer of chunk n-1, which every
-//     wave has left by then -- so fragment prefetches run across chunk boundaries without a bubble;
+//     n+1 visible (issued after rendezvous n-1) and frees the buffer of chunk n-1, which every wave has left by
+//     then, for chunk n+2 -- so fragment prefetches run across chunk boundaries without a bubble; chunk n+2 is
+//     issued behind the barrier or spread over the pieces up to rendezvous n+1 (X16Issue below);
 //   (a half-chunk stagger of the SIMD partner waves and an epilogue deferred onto a second accumulator set were
 //   measured perf-neutral or worse in round 1 -- DESIGN 3.1 log items 3, 8, 11 -- and are gone from the source.)
 #ifndef X16_DEPTH
@@ -133,6 +134,30 @@ struct X16<N3DT_F16> {
 #define X16_NBUF 3  // chunk buffers of the ring (4 measured no faster for the render kernel and the renderer blocks)
 #endif
 #define X16_CHUNK_BYTES (X16_CH * X16_PIECE)
+
+// WHERE a chunk's LDS-DMA pieces are issued: a compile-time schedule, template argument of WeightStream.
+//   X16Issue<>             every piece right behind the rendezvous barrier, at piece X16_CH - DEPTH, each addressed through a
+//                          per-lane 64-bit pointer: the form every kernel had, and the one the kernels without an A/B of their
+//                          own keep (that path is the code it was);
+//   X16Issue<S0, S1, ..>   piece i of the chunk a wave stages is issued by next<P>() when P % X16_CH == Si: PPW positions after
+//                          the rendezvous piece and before the next one, i.e. from X16_CH - DEPTH + 1 .. X16_CH - 1, 0 ..
+//                          X16_CH - DEPTH - 1, given in that order, so that the DMA instructions sit between MFMAs and not, all
+//                          waves at once, beside the barrier wait, the matrix pipe's drain and a tile's epilogue.  The pieces are
+//                          addressed from a scalar base (WeightStream::gsrc, voff).
+// Invariants (WeightStream keeps them for every schedule; tests/test_host_stream_issue.py reads them off the assembly):
+//   1. every piece of chunk c is issued, in program order, AFTER the rendezvous that frees the buffer of chunk c - NBUF (the one
+//      met in chunk c - NBUF + 1) and BEFORE the next rendezvous, whose counted wait is the first that may have to cover it;
+//   2. the tail of the stream (meets + NBUF - 1 >= limit) issues nothing;
+//   3. the prologue stages its NBUF - 1 chunks whole, whatever the schedule;
+//   4. the slots are positions P % X16_CH, so stages whose tiles are not one chunk (KS = 4, KS = 28) need no special case.
+template <int... S>
+struct X16Issue {
+    static constexpr int count = sizeof...(S);
+    static constexpr int at(const int i) {
+        const int v[] = {S..., 0};
+        return v[i];
+    }
+};
 
 // Diagnostic build only (-DX16_STAMP): per-wave cycle sums of the three phases of a tile, written to the
 // `wlocal` debug buffer (never read by the library).  Not for timing the kernel: the stamps fence overlap.
@@ -195,12 +220,17 @@ __device__ __forceinline__ void x16_pin_v(T*& p) {  // per-lane pointers
 #define X16_NT_STORE 1  // saved tiles are streamed (written once, read by a later kernel): nontemporal stores (fwd 1.65 -> 1.35 ms)
 #endif
 // DEPTH: fragments in flight per wave (DEPTH; the training forward runs with 2 to stay inside its register budget)
-template <int PREC, int WAVES, int NCHUNK = X16_NCHUNK, int NBUF = X16_NBUF, int DEPTH = X16_DEPTH>
+template <int PREC, int WAVES, int NCHUNK = X16_NCHUNK, int NBUF = X16_NBUF, int DEPTH = X16_DEPTH, class SCHED = X16Issue<>>
 struct WeightStream {
     X16_T(unsigned long long t_rv = 0; unsigned long long t_mfma = 0; unsigned long long t_epi = 0; unsigned long long t_bias = 0;
           int tile_no = 0; float* tl = nullptr;)
     typedef typename X16<PREC>::frag frag;
-    const unsigned char* gsrc;  // per-lane: packed + (wave*PPW)*1KiB + lane*16
+    // Source of this wave's first piece: packed + (wave*PPW)*1KiB + lane*16.  X16Issue<>: gsrc is that per-lane pointer.  A spread
+    // schedule: gsrc is its wave-uniform part and voff = lane*16, and a piece addresses as a scalar base (advanced by scalar
+    // arithmetic) plus that one persistent 32-bit register, `global_load_lds_dwordx4 v, s[n:n+1]`, with no 64-bit vector add and
+    // no register pair per piece.
+    const unsigned char* gsrc;
+    unsigned voff;
     unsigned char* ring;        // LDS, 3 chunk buffers
     unsigned lds_addr0;         // LDS byte address of ring + lane*16
     unsigned cur_addr, nxt_addr;  // LDS byte addresses (+ lane*16) of the buffers of chunk `chunk` and `chunk`+1
@@ -216,17 +246,54 @@ struct WeightStream {
     int src_c;                  // source chunk of the next issue (wraps at NCHUNK: every pass streams the same weights)
     frag a[DEPTH];          // piece p sits in a[p % DEPTH]
     static constexpr int PPW = X16_CH / WAVES;  // pieces each wave stages per chunk
+    // the issue schedule (X16Issue above)
+    static constexpr bool SPREAD = SCHED::count != 0;
+    static constexpr int RV = X16_CH - DEPTH;  // piece of a chunk at which the rendezvous is met
+    static constexpr bool slots_in_order() {  // each in RV + 1 .. X16_CH - 1, 0 .. RV - 1, and in that order
+        for (int i = 0; i < SCHED::count; ++i) {
+            const int s = SCHED::at(i), prev = i ? SCHED::at(i - 1) : RV + 1;
+            if (s < 0 || s >= X16_CH || s == RV || (s + X16_CH - RV - 1) % X16_CH < (prev + X16_CH - RV - 1) % X16_CH) return false;
+        }
+        return true;
+    }
+    static_assert(!SPREAD || SCHED::count == PPW, "one slot per piece a wave stages");
+    static_assert(slots_in_order(), "slots lie between two rendezvous and are given in the order the stream passes them");
+    int stage_c = -1;           // spread schedule: chunk (count since the prologue) whose pieces the slots are issuing; -1: none
+    int stage_src;              // its source chunk
 
     __device__ __forceinline__ void issue(int c) {  // c: chunk count since the prologue (picks the ring buffer)
-        const unsigned char* src = gsrc + (size_t)src_c * X16_CHUNK_BYTES;
-        src_c = src_c + 1 == NCHUNK ? 0 : src_c + 1;
-        unsigned char* dst = ring + (c % NBUF) * X16_CHUNK_BYTES + wave * PPW * X16_PIECE;
-        // (the instruction's immediate offset is not used: with one M0 and offsets 0 / 1 KiB / 2 KiB, and with a per-piece
-        // M0 plus the offset on top, the fused kernel's results were wrong -- its effect on the LDS address was not pinned down)
+        if constexpr (SPREAD) {
+            stage(c);
+            static_for<0, PPW>([&](auto i_c) { issue_piece<decltype(i_c)::value>(); });
+            stage_c = -1;
+        } else {
+            const unsigned char* src = gsrc + (size_t)src_c * X16_CHUNK_BYTES;
+            src_c = src_c + 1 == NCHUNK ? 0 : src_c + 1;
+            unsigned char* dst = ring + (c % NBUF) * X16_CHUNK_BYTES + wave * PPW * X16_PIECE;
+            // (the instruction's immediate offset is not used: with one M0 and offsets 0 / 1 KiB / 2 KiB, and with a per-piece
+            // M0 plus the offset on top, the fused kernel's results were wrong -- its effect on the LDS address was not pinned down)
 #pragma unroll
-        for (int i = 0; i < PPW; ++i)
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src + i * X16_PIECE), (LDS_AS void*)(dst + i * X16_PIECE), 16, 0,
-                                             0);
+            for (int i = 0; i < PPW; ++i)
+                __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src + i * X16_PIECE), (LDS_AS void*)(dst + i * X16_PIECE), 16,
+                                                 0, 0);
+        }
+    }
+    // spread schedule: chunk c is the next to be staged (the source wraps at NCHUNK); next<P>() issues its pieces at their slots
+    __device__ __forceinline__ void stage(const int c) {
+        stage_c = c;
+        stage_src = src_c;
+        src_c = src_c + 1 == NCHUNK ? 0 : src_c + 1;
+    }
+    template <int I>  // piece I of the PPW this wave stages of chunk stage_c
+    __device__ __forceinline__ void issue_piece() {
+        // The piece's scalar base and the lane offset are made opaque HERE: otherwise hipcc folds gsrc + voff into one per-lane
+        // 64-bit pointer again (a v_lshl_add_u64 into a register pair per piece), or, with the zero-extension of voff hoisted
+        // out of the block, no longer sees base + 32-bit offset and does the same.  (No immediate offset: see issue().)
+        unsigned long long b = (unsigned long long)(gsrc + (size_t)stage_src * X16_CHUNK_BYTES + I * X16_PIECE);
+        asm volatile("" : "+s"(b), "+v"(voff));
+        const unsigned char* src = (const unsigned char*)(const GLOBAL_AS unsigned char*)b + voff;
+        unsigned char* dst = ring + (stage_c % NBUF) * X16_CHUNK_BYTES + (wave * PPW + I) * X16_PIECE;
+        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)src, (LDS_AS void*)dst, 16, 0, 0);
     }
     __device__ __forceinline__ void prologue_issue(const int passes = 1) {
         limit = passes * NCHUNK;
@@ -257,8 +324,13 @@ struct WeightStream {
     }
     // The wait of a rendezvous is COUNTED.  Chunk meets+1 was issued NBUF-2 rendezvous ago; vector-memory operations retire in
     // order (loads and stores share vmcnt on gfx9-family parts), so "at most K operations outstanding", K = what this wave has
-    // issued SINCE that chunk's loads, means they have landed.  K = the (NBUF-3) newer chunks' loads plus the stores the kernel
-    // reports through note_stores() -- the training kernels write 2-3 KiB per tile, and with a plain vmcnt(0) every rendezvous
+    // issued SINCE THE LAST PIECE of that chunk, means its pieces have landed.  K = the (NBUF-3) newer chunks' loads plus the
+    // stores the kernel reports through note_stores() AFTER that last piece.  A store reported before it (between the pieces of
+    // a spread schedule, or ahead of them) is OLDER than the piece: counted, it would let vmcnt(K) pass with the piece still in
+    // flight.  So the count restarts (restart_count) where a chunk's last piece is issued: behind the barrier for X16Issue<>, as
+    // it always did, at the last slot for a spread schedule -- and at the rendezvous itself where it stages nothing (the tail;
+    // stricter than needed), so that it restarts exactly once per period and vm_prev is the period before the current one.
+    // The training kernels write 2-3 KiB per tile, and with a plain vmcnt(0) every rendezvous
     // also waited for the acknowledgement of the stores issued a tile ago (the write path runs near the HBM write bandwidth
     // there: the forward with SAVE took 1.58 ms against 0.92 ms without).  Safety: K must never exceed the true count, so only
     // stores that are issued UNCONDITIONALLY at their program point may be reported (dead waves write a dump record); loads and
@@ -275,8 +347,12 @@ struct WeightStream {
     // -DX16_RV_RAW=1 (diagnostic) replaces __syncthreads() by a raw s_barrier between compiler barriers: what the barrier orders
     // needs no fence -- this wave's pieces of chunk meets+1 are awaited just above, and a wave's reads of chunk meets-1 (whose
     // buffer is overwritten next) were consumed by MFMAs a chunk ago.
-    int vm_cur = 0, vm_prev = 0;  // reported stores since the last rendezvous / in the period before it
+    int vm_cur = 0, vm_prev = 0;  // reported stores since the count last restarted / in the period before that
     __device__ __forceinline__ void note_stores(const int n) { vm_cur += n; }
+    __device__ __forceinline__ void restart_count() {
+        vm_prev = vm_cur;
+        vm_cur = 0;
+    }
     template <int K>
     __device__ __forceinline__ static void wait_vm() {
         asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
@@ -296,11 +372,22 @@ struct WeightStream {
 #else
         __syncthreads();
 #endif
+        // the buffer of chunk meets-1 is free for chunk meets+NBUF-1
+        if constexpr (SPREAD) {
+            bool staged = false;
 #ifndef X16_NODMA  // diagnostic build: the stream stops after the prologue (results are garbage, the timing is the point)
-        if (meets + NBUF - 1 < limit) issue(meets + NBUF - 1);
+            if (meets + NBUF - 1 < limit) {
+                stage(meets + NBUF - 1);  // next<P>() issues its pieces at their slots and restarts the count at the last
+                staged = true;
+            }
 #endif
-        vm_prev = vm_cur;
-        vm_cur = 0;
+            if (!staged) restart_count();
+        } else {
+#ifndef X16_NODMA
+            if (meets + NBUF - 1 < limit) issue(meets + NBUF - 1);
+#endif
+            restart_count();
+        }
         ++meets;
     }
     // The fragment reads are issued from inline asm so that their completion can be awaited with a COUNTED
@@ -328,12 +415,24 @@ struct WeightStream {
     static constexpr int depth = DEPTH;
     template <bool LAST, int NP, int P, int EXTRA = 0>
     __device__ __forceinline__ frag next() {
-        constexpr int rv = X16_CH - DEPTH;
-        if (P % X16_CH == rv) {
+        if (P % X16_CH == RV) {
             X16_T(const unsigned long long r0 = x16_now();)
             rendezvous();
             X16_T(t_rv += x16_now() - r0;)
         }
+        // the pieces of the staged chunk whose slot this is (stage_c < 0: none staged -- the stream's tail issues nothing)
+        if constexpr (SPREAD)
+            static_for<0, PPW>([&](auto i_c) {
+                constexpr int I = decltype(i_c)::value;
+                if constexpr (SCHED::at(I) == P % X16_CH)
+                    if (stage_c >= 0) {
+                        issue_piece<I>();
+                        if constexpr (I == PPW - 1) {  // the chunk's last piece: the counted waits count from here
+                            restart_count();
+                            stage_c = -1;
+                        }
+                    }
+            });
         constexpr int Q = P + DEPTH - 1;
 #ifdef X16_NOLDS  // diagnostic build: no fragment reads at all (garbage results)
         if ((P + 1) % X16_CH == 0) ++chunk;

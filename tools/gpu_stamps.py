@@ -20,17 +20,19 @@ with torch.no_grad():
                                   d["batch_Tvecs"], d["batch_inv_inmats"], want_weight=True)
 torch.cuda.synchronize()
 from n3dt import ops  # noqa: E402
-ws = ops.WORKSPACE.buf[("render", 0)]
-# the wlocal region is the tail of the render workspace: blocks * 32 floats
+ws = next(b for k, b in ops.WORKSPACE.buf.items() if k[0] == "render")  # keyed by (role, device, stream)
+# the wlocal region (blocks * 32 floats) is the last but one of the render workspace; the background map transposed to
+# [N_r][C] fp32 lies behind it (csrc/n3dt_api.hip: render_carve).  The stamps are big integers stored as floats in the first
+# 4 slots of each 32-float record.
 blocks = 8 * 4096 * 2
-wl = ws.view(torch.float32)[-(blocks * 32 + 64):]
-# find by scanning: stamps are big integers stored as floats in the first 4 slots of each 32-float record
 import ctypes  # noqa: E402
 from n3dt import _lib  # noqa: E402
 g = net._geom(8, 4096, d["batch_xy"])
 total = _lib.lib().n3dt_render_workspace_bytes(ctypes.byref(g), 1)
 wl_bytes = ((blocks * 32 * 4 + 255) // 256) * 256
-full = ws[total - wl_bytes: total - wl_bytes + blocks * 32 * 4].view(torch.float32).view(blocks, 32).double()
+bg_bytes = ((4096 * 256 * 4 + 255) // 256) * 256
+at = total - bg_bytes - wl_bytes
+full = ws[at: at + blocks * 32 * 4].view(torch.float32).view(blocks, 32).double()
 wl = full[:, :4]
 m = wl.mean(0)
 tot = m.sum()
