@@ -324,6 +324,27 @@ int n3dt_neural_render_bwd(const N3dtGeom* g, int nb, int precision, const N3dtR
  *   img [n_images,3,pixels] float in (0,1)  ->  out [n_images,pixels,3] uint8 */
 int n3dt_img_to_uint8(int n_images, int pixels, const float* img, unsigned char* out, void* stream);
 
+/* ---- validation metrics: SSIM and PSNR of rendered frames (Utils/Eval_utils.py:11-48,54-66,101-106) ---------------------
+ * What the reference's validation() scores a frame with, for every image pair of the call:
+ *   q      = (unsigned char) min(max(x * 255.0f, 0.0f), 255.0f), NaN -> 0: `(x * 255).astype(np.uint8)` inside [0,1]; outside
+ *            it numpy's cast is undefined and the clamp is this library's definition
+ *   grey   = (q0 * 3735 + q1 * 19235 + q2 * 9798 + 16384) >> 15: cv2.cvtColor(COLOR_BGR2GRAY) on uint8, channel 0 taken as B
+ *            although the image is RGB (the reference's quirk, kept)
+ *   ssim   = skimage.metrics.structural_similarity(grey1, grey2), every default on uint8: float64, 7x7 uniform window,
+ *            data_range 255, K1 0.01, K2 0.03, sample covariance, the mean over the image cropped by 3 on every side
+ *   psnr   = cv2.PSNR(q1, q2) on the colour bytes: 20 log10(255 / (sqrt(SSE / (3 H W)) + DBL_EPSILON)); identical images
+ *            give 361.20..., not infinity
+ * pred, gt [n_images, 3, height, width] fp32 contiguous -> ssim [n_images], psnr [n_images] doubles.  Two launches whatever
+ * n_images is: one workgroup per 32x32 tile forms the window sums and the squared error as exact integers and one
+ * (double, uint64) partial; one workgroup per image adds its partials in index order.  No atomics: the result is bitwise
+ * reproducible.  workspace: n3dt_eval_metrics_workspace_bytes, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size query returns 0 and sets n3dt_last_error):
+ * n_images >= 1, height >= 7, width >= 7, height * width < 2^31; no NULL pointer; ssim, psnr and the workspace 8-byte aligned
+ * (they are written as doubles and (double, uint64) records), pred and gt 4-byte aligned; workspace_bytes at least the query's. */
+size_t n3dt_eval_metrics_workspace_bytes(int n_images, int height, int width);
+int n3dt_eval_metrics(int n_images, int height, int width, const float* pred, const float* gt, double* ssim, double* psnr,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

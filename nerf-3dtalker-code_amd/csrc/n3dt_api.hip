@@ -11,6 +11,7 @@
 
 #include "../../include/n3dt.h"
 #include "n3dt_layout.h"
+#include "eval_metrics_core.h"
 
 extern "C" {
 void n3dt_launch_pack(const N3dtGeom*, int, const N3dtMlpParams*, void*, hipStream_t);
@@ -85,6 +86,8 @@ void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* c
 void n3dt_launch_a2s_bwd(int, const N3dtA2sParams*, const float*, const void*, float*, void*, hipStream_t);
 void n3dt_launch_flat_adam(const void*, const void*, int, const void*, int, void*, hipStream_t);
 void n3dt_launch_flat_adam_guarded(const void*, const void*, int, const void*, int, void*, void*, void*, hipStream_t);
+size_t n3dt_eval_metrics_ws_bytes(int, int, int);
+void n3dt_launch_eval_metrics(int, int, int, const float*, const float*, double*, double*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -645,6 +648,42 @@ extern "C" int n3dt_flat_adam_guarded_step(const void* tensor_table, const void*
     }
     n3dt_launch_flat_adam_guarded(tensor_table, chunk_table, n_chunks, group_table, n_groups, step_counter, partials, guard,
                                   (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// validation metrics (csrc/eval_metrics.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* eval_metrics_geometry(int n_images, int height, int width) {
+    if (n_images < 1) return "n_images must be >= 1";
+    if (height < EVM_WIN || width < EVM_WIN) return "height and width must be >= 7 (one 7x7 window)";
+    if ((long long)height * (long long)width >= EVM_MAX_HW) return "height * width must stay below 2^31";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_eval_metrics_workspace_bytes(int n_images, int height, int width) {
+    const char* what = eval_metrics_geometry(n_images, height, width);
+    if (what) {
+        snprintf(g_err, sizeof(g_err), "n3dt_eval_metrics_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_eval_metrics_ws_bytes(n_images, height, width);
+}
+
+extern "C" int n3dt_eval_metrics(int n_images, int height, int width, const float* pred, const float* gt, double* ssim, double* psnr,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_eval_metrics";
+    char msg[160];
+    const char* what = eval_metrics_geometry(n_images, height, width);
+    if (!what) {
+        if (!pred || !gt || !ssim || !psnr || !workspace) what = "NULL pointer";
+        else if ((((size_t)ssim) | ((size_t)psnr) | ((size_t)workspace)) & 7) what = "ssim, psnr and the workspace must be 8-byte aligned";
+        else if ((((size_t)pred) | ((size_t)gt)) & 3) what = "pred and gt must be 4-byte aligned";
+        else if (workspace_bytes < n3dt_eval_metrics_ws_bytes(n_images, height, width)) what = "workspace too small";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_eval_metrics(n_images, height, width, pred, gt, ssim, psnr, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -99,6 +99,7 @@ EXPORTS = [
     "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
     "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
     "n3dt_x16_pack_probe",
+    "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
 ]
 
 # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
@@ -235,6 +236,10 @@ def lib():
     L.n3dt_flat_adam_record_bytes.argtypes = [ci]
     L.n3dt_flat_adam_step.restype = ci
     L.n3dt_flat_adam_step.argtypes = [vp, vp, ci, vp, ci, vp, vp]
+    L.n3dt_eval_metrics_workspace_bytes.restype = sz
+    L.n3dt_eval_metrics_workspace_bytes.argtypes = [ci, ci, ci]
+    L.n3dt_eval_metrics.restype = ci
+    L.n3dt_eval_metrics.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
     L.n3dt_flat_adam_guard_bytes.restype = sz
     L.n3dt_flat_adam_guard_bytes.argtypes = []
     L.n3dt_flat_adam_guarded_step.restype = ci
