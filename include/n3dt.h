@@ -345,6 +345,41 @@ size_t n3dt_eval_metrics_workspace_bytes(int n_images, int height, int width);
 int n3dt_eval_metrics(int n_images, int height, int width, const float* pred, const float* gt, double* ssim, double* psnr,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- validation metrics: LPIPS with AlexNet features (Utils/Eval_utils.py:108-115; an addition, the ABI version stays 5) ---
+ * lpips.LPIPS(net='alex') (version 0.1, spatial=False, eval mode) of every image pair of the call, as the reference calls it.
+ * The lpips package is not a dependency: what is written here about it is from knowledge of lpips 0.1.4, so parity is unpinned
+ * to the dependency.
+ *   input   N3DT_LPIPS_REFERENCE: the quantiser q above, then the bytes of the [H,W,3] image read as [3,H,W] WITHOUT a transpose
+ *           (the reference's reshape(-1,3,h,w): element [c',y',x'] is flat byte c' H W + y' W + x' of the HWC buffer), values
+ *           0..255.  N3DT_LPIPS_STANDARD: 2 clamp(x,0,1) - 1, NaN -> -1, channels as given (the metric as its authors define it).
+ *   scaling (v - shift) / scale in fp32, shift (-.030,-.088,-.188), scale (.458,.448,.450); the convolution's zero padding follows
+ *   relu1..5 torchvision alexnet().features: conv 3->64 k11 s4 p2 | pool 3/2, conv 64->192 k5 p2 | pool 3/2, conv 192->384 k3 p1 |
+ *           conv 384->256 k3 p1 | conv 256->256 k3 p1, a ReLU after each; implicit GEMMs on the bf16 MFMA with every operand split
+ *           hi + lo and three products per term (the N3DT_F32 mode of the VGG term; the only mode)
+ *   layer   mean over pixels of sum_c w_c (n0_c - n1_c)^2, n = f / (sqrt(sum_c f^2) + 1e-10), w = lin[l] [C_out], float64
+ *   out     the five layer values added in layer order
+ * n3dt_lpips_pack re-lays weight[l] [C_out, C_in, k, k], bias[l] [C_out] and lin[l] [C_out] (device fp32, torchvision order) into
+ * `packed` (n3dt_lpips_packed_bytes, 256-byte aligned).  n3dt_lpips: pred, gt [batch,3,height,width] fp32 contiguous ->
+ * out [batch] doubles and, unless NULL, layers [5, batch] doubles.  Fixed launch sequence, no atomics, partial sums laid out per
+ * image pair: the result is bitwise reproducible, exactly 0 for identical images, symmetric in (pred, gt), and independent of a
+ * pair's position in the batch and of the batch size.  workspace: n3dt_lpips_workspace_bytes, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size query returns 0 and sets n3dt_last_error): 1 <= batch <= 64,
+ * 31 <= height, width <= 2048 (31 is the smallest size every layer has a pixel of); no NULL pointer but `layers`; out and layers
+ * 8-byte, pred and gt 4-byte, packed and workspace 256-byte aligned; workspace_bytes at least the query's. */
+#define N3DT_LPIPS_LAYERS 5
+#define N3DT_LPIPS_REFERENCE 0
+#define N3DT_LPIPS_STANDARD 1
+typedef struct N3dtLpipsParams {
+    const float* weight[N3DT_LPIPS_LAYERS];
+    const float* bias[N3DT_LPIPS_LAYERS];
+    const float* lin[N3DT_LPIPS_LAYERS];
+} N3dtLpipsParams;
+size_t n3dt_lpips_packed_bytes(void);
+int n3dt_lpips_pack(const N3dtLpipsParams* p, void* packed, void* stream);
+size_t n3dt_lpips_workspace_bytes(int batch, int height, int width);
+int n3dt_lpips(int batch, int height, int width, int input_mode, const void* packed, const float* pred, const float* gt, double* out,
+               double* layers, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

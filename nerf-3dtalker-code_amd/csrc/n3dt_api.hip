@@ -12,6 +12,7 @@
 #include "../../include/n3dt.h"
 #include "n3dt_layout.h"
 #include "eval_metrics_core.h"
+#include "lpips_core.h"
 
 extern "C" {
 void n3dt_launch_pack(const N3dtGeom*, int, const N3dtMlpParams*, void*, hipStream_t);
@@ -88,6 +89,10 @@ void n3dt_launch_flat_adam(const void*, const void*, int, const void*, int, void
 void n3dt_launch_flat_adam_guarded(const void*, const void*, int, const void*, int, void*, void*, void*, hipStream_t);
 size_t n3dt_eval_metrics_ws_bytes(int, int, int);
 void n3dt_launch_eval_metrics(int, int, int, const float*, const float*, double*, double*, void*, hipStream_t);
+size_t n3dt_lpips_packed_layout_bytes(void);
+size_t n3dt_lpips_ws_bytes(int, int, int);
+void n3dt_launch_lpips_pack(const N3dtLpipsParams*, void*, hipStream_t);
+void n3dt_launch_lpips(int, int, int, int, const void*, const float*, const float*, double*, double*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -684,6 +689,55 @@ extern "C" int n3dt_eval_metrics(int n_images, int height, int width, const floa
         return fail(N3DT_EINVAL, msg);
     }
     n3dt_launch_eval_metrics(n_images, height, width, pred, gt, ssim, psnr, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// LPIPS (csrc/lpips.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* lpips_geometry(int batch, int height, int width) {
+    if (batch < 1 || batch > LP_MAX_BATCH) return "batch outside 1..64";
+    if (height < LP_MIN_HW || width < LP_MIN_HW) return "height and width must be >= 31 (one pixel of every layer)";
+    if (height > LP_MAX_HW || width > LP_MAX_HW) return "height and width must be <= 2048";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_lpips_packed_bytes(void) { return n3dt_lpips_packed_layout_bytes(); }
+
+extern "C" int n3dt_lpips_pack(const N3dtLpipsParams* p, void* packed, void* stream) {
+    if (!p || !packed) return fail(N3DT_EINVAL, "n3dt_lpips_pack: NULL argument");
+    if (((size_t)packed) & 255) return fail(N3DT_EINVAL, "n3dt_lpips_pack: packed must be 256-byte aligned");
+    for (int l = 0; l < N3DT_LPIPS_LAYERS; ++l)
+        if (!p->weight[l] || !p->bias[l] || !p->lin[l]) return fail(N3DT_EINVAL, "n3dt_lpips_pack: NULL parameter pointer");
+    n3dt_launch_lpips_pack(p, packed, (hipStream_t)stream);
+    return check_hip("n3dt_lpips_pack");
+}
+
+extern "C" size_t n3dt_lpips_workspace_bytes(int batch, int height, int width) {
+    const char* what = lpips_geometry(batch, height, width);
+    if (what) {
+        snprintf(g_err, sizeof(g_err), "n3dt_lpips_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_lpips_ws_bytes(batch, height, width);
+}
+
+extern "C" int n3dt_lpips(int batch, int height, int width, int input_mode, const void* packed, const float* pred, const float* gt,
+                          double* out, double* layers, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_lpips";
+    char msg[160];
+    const char* what = lpips_geometry(batch, height, width);
+    if (!what) {
+        if (input_mode != N3DT_LPIPS_REFERENCE && input_mode != N3DT_LPIPS_STANDARD) what = "input_mode must be N3DT_LPIPS_REFERENCE or N3DT_LPIPS_STANDARD";
+        else if (!packed || !pred || !gt || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)out) | ((size_t)layers)) & 7) what = "out and layers must be 8-byte aligned";
+        else if ((((size_t)pred) | ((size_t)gt)) & 3) what = "pred and gt must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_lpips_ws_bytes(batch, height, width)) what = "workspace too small";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_lpips(batch, height, width, input_mode, packed, pred, gt, out, layers, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
 

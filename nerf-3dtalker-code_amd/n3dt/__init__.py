@@ -3,6 +3,6 @@ from .options import BaseOptions  # noqa: F401
 from .headnerf import HeadNeRFNet, NeuralRenderer, MLPforNeRF  # noqa: F401
 from .audio import Audio2style  # noqa: F401
 from .optim import FlatAdam  # noqa: F401
-from .eval_utils import image_metrics, calc_eval_metrics  # noqa: F401
+from .eval_utils import image_metrics, calc_eval_metrics, LPIPS  # noqa: F401
 from .train import validate  # noqa: F401
 from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils  # noqa: F401,E402

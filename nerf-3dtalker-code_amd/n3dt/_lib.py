@@ -36,6 +36,14 @@ class VggParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * VGG_CONVS), ("bias", ctypes.c_void_p * VGG_CONVS)]
 
 
+LPIPS_LAYERS = 5
+LPIPS_INPUT_MODES = {"reference": 0, "standard": 1}
+
+
+class LpipsParams(ctypes.Structure):
+    _fields_ = [("weight", ctypes.c_void_p * LPIPS_LAYERS), ("bias", ctypes.c_void_p * LPIPS_LAYERS), ("lin", ctypes.c_void_p * LPIPS_LAYERS)]
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -100,6 +108,7 @@ EXPORTS = [
     "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
     "n3dt_x16_pack_probe",
     "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
+    "n3dt_lpips_packed_bytes", "n3dt_lpips_pack", "n3dt_lpips_workspace_bytes", "n3dt_lpips",
 ]
 
 # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
@@ -240,6 +249,14 @@ def lib():
     L.n3dt_eval_metrics_workspace_bytes.argtypes = [ci, ci, ci]
     L.n3dt_eval_metrics.restype = ci
     L.n3dt_eval_metrics.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
+    L.n3dt_lpips_packed_bytes.restype = sz
+    L.n3dt_lpips_packed_bytes.argtypes = []
+    L.n3dt_lpips_pack.restype = ci
+    L.n3dt_lpips_pack.argtypes = [ctypes.POINTER(LpipsParams), vp, vp]
+    L.n3dt_lpips_workspace_bytes.restype = sz
+    L.n3dt_lpips_workspace_bytes.argtypes = [ci, ci, ci]
+    L.n3dt_lpips.restype = ci
+    L.n3dt_lpips.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
     L.n3dt_flat_adam_guard_bytes.restype = sz
     L.n3dt_flat_adam_guard_bytes.argtypes = []
     L.n3dt_flat_adam_guarded_step.restype = ci

@@ -342,6 +342,22 @@ def vgg16_features_state_dict(seed=0):
     return sd
 
 
+def lpips_alex_state_dict(seed=0):
+    """Seeded stand-in for the weights lpips.LPIPS(net='alex') loads (neither torchvision's pretrained AlexNet nor the package's
+    linear layers can be fetched offline): the five convolutions under torchvision's names `features.{0,3,6,8,10}.{weight,bias}`,
+    He-normal with std = sqrt(2 / (C_in k^2)) and biases in +-0.01, and the 1x1 linear layers under lpips's names
+    `lin{k}.model.1.weight` [1, C, 1, 1] as |randn| (the trained ones are non-negative)."""
+    from .eval_utils import ALEXNET_CONVS
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for idx, cin, cout, k, _, _ in ALEXNET_CONVS:
+        sd["features.%d.weight" % idx] = torch.randn(cout, cin, k, k, generator=gen) * math.sqrt(2.0 / (cin * k * k))
+        sd["features.%d.bias" % idx] = (torch.rand(cout, generator=gen) - 0.5) * 0.02
+    for layer, (_, _, cout, _, _, _) in enumerate(ALEXNET_CONVS):
+        sd["lin%d.model.1.weight" % layer] = torch.randn(1, cout, 1, 1, generator=gen).abs()
+    return sd
+
+
 def mel_batch(B, seed=0):
     """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
     range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""

@@ -227,23 +227,26 @@ class GraphedTrainStep:
 _RENDER_KEYS = ("shape_code", "appea_code", "batch_Rmats", "batch_Tvecs", "batch_inv_inmats")
 
 
-def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None):
+def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lpips=None):
     """The reference's validation pass (talker_trainer.py:1087-1150): render every held-out batch with net("test", ...) and score
-    it with n3dt.eval_utils (SSIM and PSNR on the device; no LPIPS unless `lpips_fn` is given, see calc_eval_metrics).
+    it with n3dt.eval_utils (SSIM and PSNR on the device; LPIPS only with `lpips` or `lpips_fn`, see calc_eval_metrics).
     `batches`: an iterable of dicts with the keys of synthetic.frame_inputs plus "gt_rgb" [B,3,P,P], "mask" (accepted and ignored,
     as the reference's metrics ignore it) and, for `audio2style`, "mel" (the encoder's input; audiostyle = audio2style(mel) then
     replaces the batch's own, talker_trainer.py:1113-1119; the encoder's train / eval mode is the caller's).
     all_images=False is the reference: image 0 of each batch, the mean over batches.  all_images=True averages every image.
     Returns {"SSIM", "PSNR", "count"}, `count` being the number of images scored.  With `lpips_fn(img1_u8, img2_u8) -> float`
     also "LPIPS": its mean over the SAME images (one call per scored image, on [P,P,3] uint8 arrays), at the cost of one copy to
-    the host and one synchronisation per batch.
+    the host and one synchronisation per batch.  With `lpips`, an eval_utils.LPIPS object, "LPIPS" is computed on the device
+    and accumulated there with the other two: still one synchronisation.  Giving both raises.
     net.invalidate_packed() runs first, so weights written through `.data` or by a replayed training graph since the last
     render are the ones rendered; the metrics accumulate on the device and the host synchronises once, at the end.
     The reference calls model.eval() first and never switches back; the "test" forward does not read net.training, so this
     function does not touch it: net.training is left as it was found."""
     from . import eval_utils, ops
+    if lpips is not None and lpips_fn is not None:
+        raise ValueError("validate: give lpips= (on the device) or lpips_fn= (a host callback), not both")
     net.invalidate_packed()
-    total, count, lpips = None, 0, 0.0
+    total, count, lpips_sum = None, 0, 0.0
     with torch.no_grad():
         for b in batches:
             audiostyle = b["audiostyle"] if audio2style is None else audio2style(b["mel"])
@@ -252,16 +255,20 @@ def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None):
             if not all_images:
                 merge, gt = merge[:1], gt[:1]
             m = eval_utils._metrics(merge, gt).sum(dim=1)  # [2]: this batch's sums of SSIM and PSNR
+            if lpips is not None:
+                m = torch.cat([m, lpips(merge, gt).sum(dim=0, keepdim=True)])  # [3]: and of LPIPS
             total = m if total is None else total + m
             n = merge.shape[0]
             count += n
             if lpips_fn is not None:
                 u8 = ops.img_to_uint8(torch.cat([merge, gt])).cpu().numpy()
-                lpips += sum(float(lpips_fn(u8[i], u8[n + i])) for i in range(n))
+                lpips_sum += sum(float(lpips_fn(u8[i], u8[n + i])) for i in range(n))
     if count == 0:
         raise ValueError("validate: no batches")
-    ssim, psnr = (total / count).tolist()
-    res = {"SSIM": ssim, "PSNR": psnr, "count": count}
+    means = (total / count).tolist()
+    res = {"SSIM": means[0], "PSNR": means[1], "count": count}
+    if lpips is not None:
+        res["LPIPS"] = means[2]
     if lpips_fn is not None:
-        res["LPIPS"] = lpips / count
+        res["LPIPS"] = lpips_sum / count
     return res
