@@ -380,6 +380,36 @@ size_t n3dt_lpips_workspace_bytes(int batch, int height, int width);
 int n3dt_lpips(int batch, int height, int width, int input_mode, const void* packed, const float* pred, const float* gt, double* out,
                double* layers, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- audio front end: waveform -> mel spectrogram -> Audio2style windows -----------------------------------------------
+ * The reference computes Audio2style's input on the CPU (wav_audio.melspectrogram with wav_hparams.py, then 16-column windows
+ * cut by the data loader, XGaze_utils/data_loader_xgaze.py:256-270).  Here, in float64 on the device (csrc/mel.hip, the
+ * arithmetic in csrc/mel_core.h, the formulation in DESIGN section 3.15):
+ *   y[0] = x[0], y[n] = x[n] - 0.97 x[n-1]; reflect padding of 400 without the edge sample; frame t = 800 padded samples from
+ *   200 t, T = 1 + L / 200 frames; periodic Hann window; |DFT| of 401 bins; basis [80, 401] . |D|; 20 log10(max(1e-5, .)) - 20;
+ *   8 (S + 100) / 100 - 4 clipped to [-4, 4].
+ * n3dt_mel_spectrogram computes the frames first_frame .. first_frame + n_frames - 1 of a signal from a RUN of it:
+ * wav[0 .. n_samples) are the samples wav_offset .. wav_offset + n_samples of the signal, *prev_sample is the sample
+ * wav_offset - 1 (device memory; read only when wav_offset > 0, where it carries the pre-emphasis across the cut), and
+ * total_samples is the signal's length, or -1 while its end is unknown (no frame may then reach past the run).  The whole
+ * signal at once is wav_offset 0, prev_sample NULL, total_samples n_samples, first_frame 0, n_frames 1 + n_samples / 200; a
+ * stream computes its interior frames from a buffer that starts mid-signal.  A frame's value depends on the samples it reads,
+ * `table` and `basis` alone -- not on the run, the frame's position in the call or n_frames -- and is bitwise reproducible.
+ * basis: [80, 401] fp32 (device); table: cos(2 pi n / 800), n = 0 .. 799, doubles (device); both are the caller's.
+ * out: [80, out_ld] with frame first_frame + f in column f, doubles when out_is_f64, else floats (one conversion at the store).
+ * NaN samples give NaN values.  Two launches.  workspace: n3dt_mel_workspace_bytes (the basis transposed for the kernel).
+ * n3dt_mel_windows: mel [80, mel_ld] with T valid columns, start [n_windows] int32 (device) -> out [n_windows, 80, 16] fp32,
+ * out[w, i, c] = mel[i, clamp(start[w] + c, 0, T - 1)].  One launch.
+ * Limits (N3DT_EINVAL before anything is enqueued): n_samples >= 401; 1 <= n_frames <= 2^24; the run must hold every sample the
+ * frames read (the left reflection needs wav_offset 0, the right one total_samples); out_ld >= n_frames, mel_ld >= T >= 1,
+ * n_windows >= 1; no NULL pointer; table and a double `out` / `mel` 8-byte aligned, the rest 4-byte aligned; workspace_bytes at
+ * least the query's. */
+size_t n3dt_mel_workspace_bytes(void);
+int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t wav_offset, const float* prev_sample, int64_t total_samples,
+                         int64_t first_frame, int n_frames, const float* basis, const double* table, void* out, int64_t out_ld,
+                         int out_is_f64, void* workspace, size_t workspace_bytes, void* stream);
+int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int mel_is_f64, int n_windows, const int32_t* start, float* out,
+                     void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

@@ -13,6 +13,7 @@
 #include "n3dt_layout.h"
 #include "eval_metrics_core.h"
 #include "lpips_core.h"
+#include "mel_core.h"
 
 extern "C" {
 void n3dt_launch_pack(const N3dtGeom*, int, const N3dtMlpParams*, void*, hipStream_t);
@@ -93,6 +94,9 @@ size_t n3dt_lpips_packed_layout_bytes(void);
 size_t n3dt_lpips_ws_bytes(int, int, int);
 void n3dt_launch_lpips_pack(const N3dtLpipsParams*, void*, hipStream_t);
 void n3dt_launch_lpips(int, int, int, int, const void*, const float*, const float*, double*, double*, void*, hipStream_t);
+size_t n3dt_mel_ws_bytes(void);
+void n3dt_launch_mel_spectrogram(const MelSignal*, long long, int, const float*, const double*, void*, long long, int, void*, hipStream_t);
+void n3dt_launch_mel_windows(const void*, long long, long long, int, const int*, int, float*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -738,6 +742,58 @@ extern "C" int n3dt_lpips(int batch, int height, int width, int input_mode, cons
         return fail(N3DT_EINVAL, msg);
     }
     n3dt_launch_lpips(batch, height, width, input_mode, packed, pred, gt, out, layers, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// audio front end (csrc/mel.hip): the limits of include/n3dt.h, checked before anything is enqueued
+extern "C" size_t n3dt_mel_workspace_bytes(void) { return n3dt_mel_ws_bytes(); }
+
+extern "C" int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t wav_offset, const float* prev_sample, int64_t total_samples,
+                                    int64_t first_frame, int n_frames, const float* basis, const double* table, void* out, int64_t out_ld,
+                                    int out_is_f64, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_mel_spectrogram";
+    char msg[200];
+    const char* what = nullptr;
+    if (n_samples < MEL_MIN_SAMPLES) what = "n_samples must be >= 401 (the reflect padding of 400 needs 401 samples)";
+    else if (n_frames < 1 || n_frames > MEL_MAX_FRAMES) what = "n_frames outside 1..2^24";
+    else if (!wav || !basis || !table || !out || !workspace) what = "NULL pointer";
+    else if (n_samples > ((int64_t)1 << 40) || wav_offset > ((int64_t)1 << 40) || first_frame > ((int64_t)1 << 32)) what = "signal position out of range";
+    else what = mel_run_covers(n_samples, wav_offset, total_samples, prev_sample != nullptr, first_frame, n_frames);
+    if (!what) {
+        if (out_ld < n_frames) what = "out_ld must be >= n_frames";
+        else if (((size_t)table) & 7 || (out_is_f64 && ((size_t)out) & 7)) what = "table and a double out must be 8-byte aligned";
+        else if ((((size_t)wav) | ((size_t)prev_sample) | ((size_t)basis) | ((size_t)out) | ((size_t)workspace)) & 3)
+            what = "wav, prev_sample, basis, out and the workspace must be 4-byte aligned";
+        else if (workspace_bytes < n3dt_mel_ws_bytes()) what = "workspace too small";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    MelSignal sig;
+    sig.wav = wav;
+    sig.prev = prev_sample;
+    sig.n_samples = n_samples;
+    sig.offset = wav_offset;
+    sig.total = total_samples < 0 ? -1 : total_samples;
+    n3dt_launch_mel_spectrogram(&sig, first_frame, n_frames, basis, table, out, out_ld, out_is_f64, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int mel_is_f64, int n_windows, const int32_t* start, float* out,
+                                void* stream) {
+    static const char* who = "n3dt_mel_windows";
+    char msg[160];
+    const char* what = nullptr;
+    if (T < 1 || mel_ld < T || mel_ld > ((int64_t)1 << 40)) what = "need 1 <= T <= mel_ld";
+    else if (n_windows < 1) what = "n_windows must be >= 1";
+    else if (!mel || !start || !out) what = "NULL pointer";
+    else if ((((size_t)mel) & (mel_is_f64 ? 7 : 3)) || (((size_t)start) | ((size_t)out)) & 3) what = "mel, start or out misaligned";
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_mel_windows(mel, T, mel_ld, mel_is_f64, start, n_windows, out, (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -109,6 +109,7 @@ EXPORTS = [
     "n3dt_x16_pack_probe",
     "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
     "n3dt_lpips_packed_bytes", "n3dt_lpips_pack", "n3dt_lpips_workspace_bytes", "n3dt_lpips",
+    "n3dt_mel_workspace_bytes", "n3dt_mel_spectrogram", "n3dt_mel_windows",
 ]
 
 # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
@@ -257,6 +258,13 @@ def lib():
     L.n3dt_lpips_workspace_bytes.argtypes = [ci, ci, ci]
     L.n3dt_lpips.restype = ci
     L.n3dt_lpips.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+    i64 = ctypes.c_int64
+    L.n3dt_mel_workspace_bytes.restype = sz
+    L.n3dt_mel_workspace_bytes.argtypes = []
+    L.n3dt_mel_spectrogram.restype = ci
+    L.n3dt_mel_spectrogram.argtypes = [i64, vp, i64, vp, i64, i64, ci, vp, vp, vp, i64, ci, vp, sz, vp]
+    L.n3dt_mel_windows.restype = ci
+    L.n3dt_mel_windows.argtypes = [i64, vp, i64, ci, ci, vp, vp, vp]
     L.n3dt_flat_adam_guard_bytes.restype = sz
     L.n3dt_flat_adam_guard_bytes.argtypes = []
     L.n3dt_flat_adam_guarded_step.restype = ci

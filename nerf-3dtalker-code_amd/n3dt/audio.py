@@ -228,3 +228,20 @@ class Audio2style(nn.Module):
             masks = None
             self.last_masks = None
         return _A2sFn.apply(self, x, masks, *self.trained_parameters())
+
+
+def clip_audiostyle(a2s, front, wav, n_frames, fps=25.0, frames_per_sequence=1):
+    """From a clip's waveform to its audiostyle codes: [n_frames, 64].
+
+    `front` (n3dt.MelFrontend) computes the mel spectrogram of `wav` ([L] fp32 at 16 kHz on the GPU) and cuts the "chunk" window
+    of every video frame 0 .. n_frames - 1; `a2s` is then called on groups of `frames_per_sequence` consecutive frames (the last
+    group may be shorter).  The frames of one call are ONE LSTM sequence, as in the reference: 1 is its inference use
+    (one frame per call), the training batch size is the other natural value; at most MAX_T.  `a2s` is used as it stands --
+    its train/eval mode, and with it the dropout of the reference's always-training module, are the caller's choice."""
+    n_frames, per = int(n_frames), int(frames_per_sequence)
+    if n_frames < 1:
+        raise ValueError("clip_audiostyle: n_frames must be >= 1, got %d" % n_frames)
+    if not 1 <= per <= MAX_T:
+        raise ValueError("clip_audiostyle: frames_per_sequence must be in 1..%d, got %d" % (MAX_T, per))
+    windows = front.windows(front.melspectrogram(wav), range(n_frames), fps=fps, rule="chunk")
+    return torch.cat([a2s(windows[i:i + per]) for i in range(0, n_frames, per)])
