@@ -223,6 +223,13 @@ int n3dt_composite(int batch, int n_rays, int n_samples, int channels, const flo
  * values into one MFMA fragment.  form 0: through the kernels' own pack (two values per conversion instruction); form 1: through
  * an element-wise cast kept in this probe only -- the two must agree bit for bit.  n: a multiple of 512. */
 int n3dt_x16_pack_probe(int precision, int form, size_t n, const float* in, uint16_t* out, void* stream);
+/* The positional encoder of the fused 16-bit kernels on its own (an addition: the ABI version stays 5): points [n][3] floats ->
+ * out [n / 32][4][64][8] 16-bit values (bf16 / f16 as above), one wave per 32 points, out = that wave's four MFMA B fragments as
+ * the kernels hold them: piece ks, lane (c, h), element j is channel 16 ks + 8 (j >> 2) + 4 h + (j & 3) of point 32 wave + c (channels
+ * 0-2 the point, 3 + 6 k + {0, 1, 2} the sines and 3 + 6 k + {3, 4, 5} the cosines of octave k, 63 zero).  form 0: the kernels' own
+ * encoder (every octave and axis once, sine and cosine together, through the wave's LDS copy); form 1: the per-channel encoder
+ * it replaced, kept in this probe -- the two must agree bit for bit.  n: a multiple of 32. */
+int n3dt_x16_pe_probe(int precision, int form, size_t n, const float* points, uint16_t* out, void* stream);
 
 /* ---- 2-D neural renderer: a8..a10 ----------------------------------------------------------------
  * Replaces NeuralRenderer.forward (NetWorks/neural_renderer.py:72-91) including

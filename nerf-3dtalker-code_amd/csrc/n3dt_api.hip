@@ -37,6 +37,7 @@ void n3dt_launch_mlp_points(const N3dtGeom*, size_t, const N3dtMlpParams*, const
 void n3dt_launch_composite(int, int, int, int, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
                            hipStream_t);
 void n3dt_launch_x16_pack_probe(int, int, size_t, const float*, unsigned short*, hipStream_t);
+void n3dt_launch_x16_pe_probe(int, int, size_t, const float*, unsigned short*, hipStream_t);
 void n3dt_launch_fine_sample(const N3dtGeom*, int, const float*, const float*, const float*, const float*, float*, hipStream_t);
 void n3dt_launch_nerf_fwd_f32(const N3dtGeom*, const N3dtMlpParams*, const void*, const float*, const float*, const float*,
                               const float*, const float*, const float*, float*, float*, hipStream_t);
@@ -378,6 +379,15 @@ extern "C" int n3dt_x16_pack_probe(int precision, int form, size_t n, const floa
     if (!in || !out) return fail(N3DT_EINVAL, "n3dt_x16_pack_probe: NULL argument");
     n3dt_launch_x16_pack_probe(precision, form, n, in, out, (hipStream_t)stream);
     return check_hip("n3dt_x16_pack_probe");
+}
+
+extern "C" int n3dt_x16_pe_probe(int precision, int form, size_t n, const float* points, uint16_t* out, void* stream) {
+    if (precision != N3DT_BF16 && precision != N3DT_F16) return fail(N3DT_EINVAL, "n3dt_x16_pe_probe: precision must be N3DT_BF16 or N3DT_F16");
+    if (form != 0 && form != 1) return fail(N3DT_EINVAL, "n3dt_x16_pe_probe: form must be 0 (by octave half) or 1 (per channel)");
+    if (n < 32 || n % 32 != 0 || n / 32 > 0x7fffffffu) return fail(N3DT_EINVAL, "n3dt_x16_pe_probe: n must be a multiple of 32, at most 2^36");
+    if (!points || !out) return fail(N3DT_EINVAL, "n3dt_x16_pe_probe: NULL argument");
+    n3dt_launch_x16_pe_probe(precision, form, n, points, out, (hipStream_t)stream);
+    return check_hip("n3dt_x16_pe_probe");
 }
 
 extern "C" int n3dt_fine_sample(const N3dtGeom* g, int n_fine, const float* weight, const float* T, const float* t_rand, const float* u,

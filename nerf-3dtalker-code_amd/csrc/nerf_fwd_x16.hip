@@ -245,7 +245,7 @@ __device__ __forceinline__ void x16_stage(WS& ws, X16TileInit& ti, const float* 
             }
         }
         X16_T(const unsigned long long s3 = x16_now(); ws.t_bias += s1 - s0; ws.t_mfma += (s2 - s1) - (ws.t_rv - rv0); ws.t_epi += s3 - s2;
-              if (ws.tl && ws.tile_no >= 20 && ws.tile_no < 34 && (threadIdx.x & 63) == 0) {
+              if (ws.tl && ws.tile_no >= 20 && ws.tile_no < 33 && (threadIdx.x & 63) == 0) {
                   ws.tl[4 + 2 * (ws.tile_no - 20)] = (float)(s1 & 0xFFFFFF);
                   ws.tl[5 + 2 * (ws.tile_no - 20)] = (float)(s2 & 0xFFFFFF);
               }
@@ -274,6 +274,7 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
     typedef typename X16<PREC>::frag frag;
     const int lane = threadIdx.x & 63;
     const int c = lane & 31, h = lane >> 5;
+    X16_T(const unsigned long long t_entry = x16_now();)  // the head: kernel entry .. behind prologue_wait()
 
     // (the training forward's prefetch depth is its own switch: depth 2 frees four registers and measured the same, 1.32 against 1.32 ms)
     // (the inference kernels issue the stream's LDS-DMA pieces between the MFMAs, X16_FWD_ISSUE; the training forward keeps them
@@ -310,24 +311,9 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
     {
         float p[3];
         n3dt_sample_point(g, xy, R, T, Kinv, t_rand, frame, ray, sb * X16_BS + c, p, dist, zval);
-        // phase in revolutions as hi + lo, so that the 2^k scaling of the encoder stays exact
-        float rh[3], rl[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float inv2pi_hi = 0.15915494f, inv2pi_lo = 6.4206383e-09f;  // 1/(2 pi) = 0.159154936671257 (the float) + lo
-            rh[i] = p[i] * inv2pi_hi;
-            rl[i] = fmaf(p[i], inv2pi_hi, -rh[i]) + p[i] * inv2pi_lo;
-        }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                v[j] = pe_fast(p[0], p[1], p[2], rh[0], rh[1], rh[2], rl[0], rl[1], rl[2],
-                               32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3));
-            pe[ks] = X16<PREC>::pack(v);
-            *reinterpret_cast<frag*>(pe_lds + ks * X16_PIECE) = pe[ks];
-        }
+        // every (octave, axis) once, by octave half, through the wave's LDS copy into the fragments (x16_core.h); the reads
+        // are in flight from here to pe_settle()
+        pe_encode<PREC>(p, h, pe_lds, pe);
     }
     const float* fb = fold + (size_t)__builtin_amdgcn_readfirstlane(frame) * N3DT_FOLD_STRIDE;
     // include_vd: the merged RGB stage's bias is per RAY (frame entry + view-direction term; the table sits behind the fold table,
@@ -341,6 +327,7 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
     const long rec = live ? blk : total_blocks;
     if constexpr (SAVE) {
         xT_blk = tsv.xT + (size_t)rec * X16_XT_TILES * 2 * X16_PIECE + x16_image_lane_offset(lane);
+        pe_settle(pe);
         x16_image_store<PREC>(pe[0], pe[1], xT_blk);
         x16_image_store<PREC>(pe[2], pe[3], xT_blk + 2 * X16_PIECE);
     }
@@ -375,7 +362,9 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         }
         return bl.at(k & 1);
     };
+    if constexpr (!SAVE) pe_settle(pe);  // the encoder's one wait, as late as its fragments allow
     ws.prologue_wait();  // (vmcnt(0): table 0 is in its slot)
+    X16_T(const unsigned long long t_head = x16_now() - t_entry;)
     X16_T(if (wlocal && live) ws.tl = wlocal + (size_t)blk * X16_BS;)
     X16TileInit ti;
     if constexpr (BIAS == X16_BIAS_LDS_C) ti.template issue<0, 0>(bl.at(0));
@@ -444,6 +433,7 @@ __device__ __forceinline__ void nerf_fwd_x16_body(
         dbg[1] = (float)ws.t_mfma;
         dbg[2] = (float)ws.t_epi;
         dbg[3] = (float)ws.t_rv;
+        dbg[30] = (float)t_head;  // (the tile timeline ends at slot 29: tiles 20 .. 32)
     }
 #endif
 }

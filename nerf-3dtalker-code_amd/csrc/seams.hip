@@ -287,6 +287,51 @@ __global__ void __launch_bounds__(64) x16_pack_probe_kernel(size_t n, const floa
     *reinterpret_cast<frag*>(out + base) = f;
 }
 
+// ---- the fused 16-bit kernels' positional encoder on its own ------------------------------------------------
+// points [n][3] floats -> out [n / 32][4][64][8] 16-bit: one wave per 32 points, out = the wave's four B fragments as
+// nerf_fwd_x16_body holds them (piece ks, lane (c, h), element j = channel 16 ks + 8 (j >> 2) + 4 h + (j & 3) of point c).
+// FORM 0: pe_encode, the function the kernels call (by octave half, through a 4 KiB LDS copy).  FORM 1: the per-channel
+// pe_fast loop the kernels used to run, kept HERE as the yardstick form 0 is compared against bit for bit.
+template <int PREC, int FORM>
+__global__ void __launch_bounds__(64) x16_pe_probe_kernel(size_t n, const float* __restrict__ points, unsigned short* __restrict__ out) {
+    typedef typename X16<PREC>::frag frag;
+    __shared__ __attribute__((aligned(16))) unsigned char pe_wave[4 * X16_PIECE];
+    const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
+    const size_t pt = (size_t)blockIdx.x * 32 + c;
+    if ((size_t)blockIdx.x * 32 + 32 > n) return;  // (wave-uniform)
+    const float p[3] = {points[3 * pt], points[3 * pt + 1], points[3 * pt + 2]};
+    frag pe[4];
+    if constexpr (FORM == 0) {
+        pe_encode<PREC>(p, h, pe_wave + 16 * lane, pe);
+        pe_settle(pe);
+    } else {
+        float rh[3], rl[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pe_phase(p[i], rh[i], rl[i]);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                v[j] = pe_fast(p[0], p[1], p[2], rh[0], rh[1], rh[2], rl[0], rl[1], rl[2], 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3));
+            pe[ks] = X16<PREC>::pack(v);
+        }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) *reinterpret_cast<frag*>(out + (((size_t)blockIdx.x * 4 + ks) * 64 + lane) * 8) = pe[ks];
+}
+
+extern "C" void n3dt_launch_x16_pe_probe(int precision, int form, size_t n, const float* points, unsigned short* out, hipStream_t s) {
+    const dim3 grid((unsigned)(n / 32)), block(64);
+    if (precision == N3DT_BF16) {
+        if (form == 0) hipLaunchKernelGGL((x16_pe_probe_kernel<N3DT_BF16, 0>), grid, block, 0, s, n, points, out);
+        else hipLaunchKernelGGL((x16_pe_probe_kernel<N3DT_BF16, 1>), grid, block, 0, s, n, points, out);
+    } else {
+        if (form == 0) hipLaunchKernelGGL((x16_pe_probe_kernel<N3DT_F16, 0>), grid, block, 0, s, n, points, out);
+        else hipLaunchKernelGGL((x16_pe_probe_kernel<N3DT_F16, 1>), grid, block, 0, s, n, points, out);
+    }
+}
+
 extern "C" void n3dt_launch_x16_pack_probe(int precision, int form, size_t n, const float* in, unsigned short* out, hipStream_t s) {
     const dim3 grid((unsigned)(n / 512)), block(64);
     if (precision == N3DT_BF16) {

@@ -516,6 +516,84 @@ __device__ __forceinline__ float pe_fast(const float p0, const float p1, const f
     return ch < 3 ? raw : (ch >= N3DT_PE_DIM ? 0.0f : sv);
 }
 
+// the sample position as a phase in revolutions, hi + lo, so that the 2^k scaling of the encoder stays exact
+__device__ __forceinline__ void pe_phase(const float p, float& hi, float& lo) {
+    const float inv2pi_hi = 0.15915494f, inv2pi_lo = 6.4206383e-09f;  // 1/(2 pi) = 0.159154936671257 (the float) + lo
+    hi = p * inv2pi_hi;
+    lo = fmaf(p, inv2pi_hi, -hi) + p * inv2pi_lo;
+}
+
+// One (octave, axis) of the encoding: s = pe_fast's channel 3 + 6k + dim, c = its channel 3 + 6k + 3 + dim, for sc = 2^k and the
+// axis' phase hi + lo.  pe_fast's operations in pe_fast's order on either value (same floats, -ffp-contract=off); what the two
+// channels share -- the reduced phase u, t, |t| and the signed low part -- is computed once, nothing is decoded from a channel
+// index and neither argument is formed to be thrown away.
+__device__ __forceinline__ void pe_pair(const float hi, const float lo, const float sc, float& s, float& c) {
+    const float u = __builtin_amdgcn_fractf(hi * sc);
+    const float t = u - (u >= 0.5f ? 1.0f : 0.0f);                 // [-1/2, 1/2)
+    const float at = __builtin_fabsf(t), ls = lo * sc;
+    const float sl = t < 0.0f ? -ls : ls;
+    const bool far = at > 0.25f;
+    const float ts = far ? 0.5f - at : at;
+    const float rs = (t < 0.0f ? -1.0f : 1.0f) * (ts + (far ? -sl : sl));
+    const float rc = (0.25f - at) - sl;
+    s = __builtin_amdgcn_sinf(rs);
+    c = __builtin_amdgcn_sinf(rc);
+}
+
+// Byte offset of channel ch (0..63) of sample 0 in a wave's four lane-linear PE pieces (piece ks = the B fragment of k-step ks,
+// lane (c, h) element j = channel 16 ks + 8 (j >> 2) + 4 h + (j & 3)); sample c sits 16 c bytes further on.
+constexpr int pe_slot_offset(const int ch) { return (ch / 16) * X16_PIECE + 512 * ((ch % 8) / 4) + 8 * ((ch % 16) / 8) + 2 * (ch % 4); }
+
+// The whole encoding of a wave's 32 samples into its four B fragments.  Both lanes of a sample (c, h = 0 / 1) hold its position
+// p.  Ownership is by OCTAVE half, not by fragment slot: lane (c, h) encodes octaves k = j + 5 h, j = 0 .. 4, on all three
+// axes -- 15 pe_pair calls, 30 sines, every one of them used -- i.e. the consecutive channels 3 + 30 h .. 32 + 30 h, and the
+// h = 0 lane adds the raw coordinates (channels 0 .. 2), the h = 1 lane the zero of channel 63.  The values reach their
+// fragment slots through the wave's 4 KiB LDS copy (pe_lane = the copy + 16 lane; the skip stage reads it anyway): each is rounded as
+// X16<PREC>::pack rounds it, channel pairs (even, odd) share a dword and go out as one 32-bit store, the seams (channels 2, 3
+// and 32 on h = 0, 33 on h = 1) as 16-bit stores; the destination of a store is one of two compile-time offsets, picked by h.
+// To keep the halves in lockstep without a branch the h = 1 lane repeats two of its stores (same value, same address).  Then
+// four ds_read_b128 fetch the lane's fragments; LDS executes a wave's operations in order, so nothing waits in between.  The
+// reads are NOT awaited here: the caller retires them with pe_settle() before the first use.
+template <int PREC>
+__device__ __forceinline__ void pe_encode(const float (&p)[3], const int h, unsigned char* pe_lane,
+                                          typename X16<PREC>::frag (&pe)[4]) {
+    float rh[3], rl[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pe_phase(p[i], rh[i], rl[i]);
+    float e[30];  // e[6 j + w] = channel 3 + 30 h + 6 j + w
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const float sc = h ? (float)(32 << j) : (float)(1 << j);  // 2^(j + 5 h): hi * sc and lo * sc are pe_fast's products
+#pragma unroll
+        for (int dim = 0; dim < 3; ++dim) pe_pair(rh[dim], rl[dim], sc, e[6 * j + dim], e[6 * j + 3 + dim]);
+    }
+    LDS_AS unsigned char* const own = (LDS_AS unsigned char*)pe_lane;  // the lane's own 16 bytes of piece 0
+    LDS_AS unsigned char* const row = own - 512 * h;                   // sample c's 16 bytes on the h = 0 side
+    typedef unsigned __attribute__((may_alias)) u32;
+    typedef unsigned short __attribute__((may_alias)) u16;
+    // h = 0: channels 0, 1 = p0, p1;  h = 1: channels 62, 63 = e29, 0
+    *(LDS_AS u32*)(row + (h ? pe_slot_offset(62) : pe_slot_offset(0))) = x16_cvt2<PREC>(h ? e[29] : p[0], h ? 0.0f : p[1]);
+    // h = 0: channel 2 = p2;  h = 1: channel 33 = e0
+    *(LDS_AS u16*)(row + (h ? pe_slot_offset(33) : pe_slot_offset(2))) = (unsigned short)x16_cvt2<PREC>(h ? e[0] : p[2], 0.0f);
+    // h = 0: channels 3 and 32;  h = 1: 33 and 62 once more
+    *(LDS_AS u16*)(row + (h ? pe_slot_offset(33) : pe_slot_offset(3))) = (unsigned short)x16_cvt2<PREC>(e[0], 0.0f);
+    *(LDS_AS u16*)(row + (h ? pe_slot_offset(62) : pe_slot_offset(32))) = (unsigned short)x16_cvt2<PREC>(e[29], 0.0f);
+#pragma unroll
+    for (int i = 0; i < 14; ++i)  // channels 4 + 2 i, 5 + 2 i (h = 0) / 34 + 2 i, 35 + 2 i (h = 1)
+        *(LDS_AS u32*)(row + (h ? pe_slot_offset(34 + 2 * i) : pe_slot_offset(4 + 2 * i))) = x16_cvt2<PREC>(e[2 * i + 1], e[2 * i + 2]);
+    const unsigned at = (unsigned)(size_t)own;
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
+                 "ds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
+                 : "=&v"(pe[0]), "=&v"(pe[1]), "=&v"(pe[2]), "=&v"(pe[3])
+                 : "v"(at)
+                 : "memory");
+}
+// the one wait of the encoder, before the first use of its fragments (which stay reserved up to here)
+template <class FRAG>
+__device__ __forceinline__ void pe_settle(FRAG (&pe)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pe[0]), "+v"(pe[1]), "+v"(pe[2]), "+v"(pe[3]));
+}
+
 enum { MODE_HIDDEN = 0, MODE_LINEAR = 1, MODE_DENSITY = 2, MODE_COMPOSITE = 3 };
 
 

@@ -106,7 +106,7 @@ EXPORTS = [
     "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
     "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
     "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
-    "n3dt_x16_pack_probe",
+    "n3dt_x16_pack_probe", "n3dt_x16_pe_probe",
     "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
     "n3dt_lpips_packed_bytes", "n3dt_lpips_pack", "n3dt_lpips_workspace_bytes", "n3dt_lpips",
     "n3dt_mel_workspace_bytes", "n3dt_mel_spectrogram", "n3dt_mel_windows",
@@ -212,6 +212,8 @@ def lib():
     L.n3dt_composite.argtypes = [ci, ci, ci, ci] + [vp] * 8 + [vp]
     L.n3dt_x16_pack_probe.restype = ci
     L.n3dt_x16_pack_probe.argtypes = [ci, ci, sz, vp, vp, vp]
+    L.n3dt_x16_pe_probe.restype = ci
+    L.n3dt_x16_pe_probe.argtypes = [ci, ci, sz, vp, vp, vp]
     L.n3dt_stage_inputs.restype = ci
     L.n3dt_stage_inputs.argtypes = [ctypes.POINTER(Stage), vp]
     L.n3dt_graph_begin.restype = ci

@@ -213,6 +213,18 @@ def x16_pack_probe(x, precision, form=0):
     return out
 
 
+def x16_pe_probe(points, precision, form=0):
+    """The fused 16-bit kernels' positional encoder on its own (n3dt_x16_pe_probe): points fp32 [n, 3], n a multiple of 32 ->
+    [n / 32, 4, 64, 8] bf16 / fp16, each wave's four MFMA fragments.  form 0: the kernels' encoder; form 1: the per-channel one."""
+    points = _f32c(points)
+    assert points.dim() == 2 and points.shape[1] == 3, "points must be [n, 3]"
+    n = points.shape[0]
+    prec = _lib.PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    out = torch.empty((n // 32, 4, 64, 8), dtype=torch.bfloat16 if prec == _lib.BF16 else torch.float16, device=points.device)
+    check(lib().n3dt_x16_pe_probe(prec, int(form), n, _ptr(points), _ptr(out), _stream()), "n3dt_x16_pe_probe")
+    return out
+
+
 def ray_vd_bias(geom, w_rgb1, xy, R, Kinv, out=None):
     """include_vd: the per-ray bias of RGB_layer_1 from the ray direction (n3dt_ray_vd_bias).  w_rgb1: the layer's FULL 2-D
     weight [192, 384 + 27 + appea_dim] (contiguous); its columns 384 .. 410 are read in place."""

@@ -39,12 +39,16 @@ tot = m.sum()
 print("per wave mean cycles: bias-init %.0f  mfma-loop %.0f  epilogue %.0f  rendezvous %.0f  (sum %.0f)" % (*m.tolist(), tot))
 print("shares: bias %.1f%%  mfma %.1f%%  epilogue %.1f%%  rendezvous %.1f%%" % tuple((100 * m / tot).tolist()))
 print("per tile (107 tiles): bias %.0f mfma %.0f epi %.0f rv %.0f" % tuple((m / 107).tolist()))
+# the head: kernel entry .. behind prologue_wait() (slot 30), per wave and per workgroup (its slowest wave)
+head = full[:, 30]
+print("head (kernel entry .. behind the prologue's barrier): per wave mean %.0f, per workgroup (slowest of 8 waves) mean %.0f, "
+      "median %.0f stamp ticks" % (head.mean(), head.view(-1, 8).max(1).values.mean(), head.view(-1, 8).max(1).values.median()))
 
 # timeline of one workgroup (8 consecutive waves): MFMA-loop [start, end] of stream tiles 20..33, relative to wave 0's first
 for wg in (0, 1000):
-    rows = full[wg * 8: wg * 8 + 8, 4:32]
+    rows = full[wg * 8: wg * 8 + 8, 4:30]
     base = rows[0, 0]
-    print("workgroup %d: per wave (start,end) of the MFMA loop for tiles 20..25, cycles relative to wave 0" % wg)
+    print("workgroup %d: per wave (start,end) of the MFMA loop for tiles 20..25 (the record holds 20..32), cycles relative to wave 0" % wg)
     for w in range(8):
         r = ((rows[w] - base) % (1 << 24)).tolist()
         print("  wave %d: " % w + "  ".join("(%5d,%5d)" % (r[2 * i], r[2 * i + 1]) for i in range(6)))
