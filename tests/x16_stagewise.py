@@ -338,13 +338,14 @@ class Workspace:
 # ---------------------------------------------------------------------------------------------
 # the comparison rule
 # ---------------------------------------------------------------------------------------------
-def check_bf16(stored_bits, z64, delta, relu=False, gate=None):
+def check_bf16(stored_bits, z64, delta, relu=False, gate=None, act=None):
     """See the module docstring.  gate (bool, or None): entries whose gate is closed must be stored as zero.
+    act: a monotone activation in place of the ReLU (the 2-D renderer's LeakyReLU, nr_restatement.py); the rule is unchanged.
     Returns dict(n, ambiguous, mismatches, max_ulp, worst): `worst` lists (flat index, stored, expected, z64, delta) of up to eight
     failing entries."""
     z64 = np.asarray(z64, dtype=np.float64)
     delta = np.broadcast_to(np.asarray(delta, dtype=np.float64), z64.shape)
-    act = (lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v)
+    act = act or ((lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v))
     e, a, b = bf16_bits(act(z64)), bf16_bits(act(z64 - delta)), bf16_bits(act(z64 + delta))
     if gate is not None:
         closed = ~np.asarray(gate, dtype=bool)
@@ -362,10 +363,10 @@ def check_bf16(stored_bits, z64, delta, relu=False, gate=None):
             "wide": int(wide.sum()), "max_ulp_wide": int(dist[wide].max()) if wide.any() else 0, "worst": worst}
 
 
-def ambiguous_share(z64, delta, relu=False, gate=None):
+def ambiguous_share(z64, delta, relu=False, gate=None, act=None):
     """(share of ambiguous entries, share of wide-delta entries) of a stage"""
     z64 = np.asarray(z64, dtype=np.float64)
-    act = (lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v)
+    act = act or ((lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v))
     span = ordinal(bf16_bits(act(z64 + delta))) - ordinal(bf16_bits(act(z64 - delta)))
     if gate is not None:
         span = np.where(np.asarray(gate, dtype=bool), span, 0)
