@@ -417,6 +417,52 @@ int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t wav_offset
 int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int mel_is_f64, int n_windows, const int32_t* start, float* out,
                      void* stream);
 
+/* ---- lip-sync metric: Wav2Lip's expert SyncNet_color, frozen, inference only (an addition, the ABI version stays 5) ---------
+ * The reference's wav_models/syncnet.py: a 17-block face encoder over windows [15,48,96] (five consecutive lower-half face crops,
+ * BGR, channel 3 t + c) and a 14-block audio encoder over mel windows [1,80,16]; each block is Conv2d + BatchNorm2d (eval mode,
+ * eps 1e-5), then for residual blocks the block's own input, then ReLU (wav_models/conv.py:15-19); both encoders end in a
+ * 512-vector, normalised x / max(||x||_2, 1e-12); the cosine of the two is the sync probability.  csrc/syncnet.hip; the 31-row
+ * geometry table and the address arithmetic are csrc/syncnet_core.h; DESIGN section 3.16.
+ *   pack    batch norm folded in float64: s = gamma / sqrt(var + 1e-5), w' = fp32(w s), b' = fp32((b - mean) s + beta); w' split
+ *           into hi + lo bf16 in MFMA fragment order.  weight[b] [C_out, C_in, kh, kw], the other five [C_out], device fp32, block
+ *           b = 0..16 the face encoder's, 17..30 the audio encoder's.  `packed`: n3dt_syncnet_packed_bytes, 256-byte aligned.
+ *   blocks  implicit GEMMs on the bf16 MFMA, every operand split hi + lo, three products per term, fp32 accumulation; the only mode
+ *   tail    normalisation and cosine in float64, fixed summation order
+ * n3dt_syncnet_fwd: mel_windows [n,1,80,16] and EITHER face_windows [n,15,48,96] OR frames [n + 4, 3, height, width] (fp32 RGB in
+ * [0,1]; window i is frames i .. i + 4) with boxes [n_boxes, 4] int32 (device) = (y1, y2, x1, x2) per frame, n_boxes = n + 4 or 1
+ * (one box for all) -> audio_emb, face_emb [n,512] fp32 and cos [n] doubles (each nullable).  All contiguous.
+ * n3dt_syncnet_face_windows is that prologue alone: crop rows y1..y2-1 and columns x1..x2-1, values clamped to [0,1] (NaN -> 0),
+ * bilinear resample to 96 x 96 with half-pixel centres (F.interpolate(mode="bilinear", align_corners=False, antialias=False)) in
+ * float64, rows 48..95, RGB reversed to BGR -> face_windows [n,15,48,96].  A box reaching outside the frame is clamped into it.
+ * n3dt_syncnet_block runs ONE block of the table on in [n, C_in, Hi, Wi] -> out [n, C_out, Ho, Wo] (a debugging aid: the tests
+ * judge blocks one at a time with it).
+ * A window's results depend on that window's inputs and the packed weights alone -- not on its position in the call or on n -- and
+ * are bitwise reproducible.  Everything is enqueued on `stream`, nothing synchronises, no atomics.
+ * workspace: n3dt_syncnet_workspace_bytes(n), 256-byte aligned, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size query returns 0 and sets n3dt_last_error): 1 <= n <= 1024;
+ * 2 <= height, width <= 4096; 0 <= block <= 30; exactly one of face_windows and frames; n_boxes 1 or n + 4; no NULL pointer but
+ * the three outputs of n3dt_syncnet_fwd; cos 8-byte, frames and boxes 4-byte, packed and workspace 256-byte, the rest 16-byte aligned; workspace_bytes at
+ * least the query's. */
+#define N3DT_SYNCNET_BLOCKS 31
+typedef struct N3dtSyncnetParams {
+    const float* weight[N3DT_SYNCNET_BLOCKS];
+    const float* bias[N3DT_SYNCNET_BLOCKS];
+    const float* bn_weight[N3DT_SYNCNET_BLOCKS];
+    const float* bn_bias[N3DT_SYNCNET_BLOCKS];
+    const float* bn_mean[N3DT_SYNCNET_BLOCKS];
+    const float* bn_var[N3DT_SYNCNET_BLOCKS];
+} N3dtSyncnetParams;
+size_t n3dt_syncnet_packed_bytes(void);
+int n3dt_syncnet_pack(const N3dtSyncnetParams* p, void* packed, void* stream);
+size_t n3dt_syncnet_workspace_bytes(int n);
+int n3dt_syncnet_face_windows(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes, float* face_windows,
+                              void* stream);
+int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_windows, const float* face_windows, const float* frames,
+                     const int32_t* boxes, int n_boxes, int height, int width, float* audio_emb, float* face_emb, double* cos,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int n3dt_syncnet_block(int block, int n, const void* packed, const float* in, float* out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

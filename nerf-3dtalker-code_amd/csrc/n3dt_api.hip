@@ -14,6 +14,7 @@
 #include "eval_metrics_core.h"
 #include "lpips_core.h"
 #include "mel_core.h"
+#include "syncnet_core.h"
 
 extern "C" {
 void n3dt_launch_pack(const N3dtGeom*, int, const N3dtMlpParams*, void*, hipStream_t);
@@ -98,6 +99,13 @@ void n3dt_launch_lpips(int, int, int, int, const void*, const float*, const floa
 size_t n3dt_mel_ws_bytes(void);
 void n3dt_launch_mel_spectrogram(const MelSignal*, long long, int, const float*, const double*, void*, long long, int, void*, hipStream_t);
 void n3dt_launch_mel_windows(const void*, long long, long long, int, const int*, int, float*, hipStream_t);
+size_t n3dt_syncnet_packed_layout_bytes(void);
+size_t n3dt_syncnet_ws_bytes(int);
+float* n3dt_syncnet_ws_faces(int, void*);
+void n3dt_launch_syncnet_pack(const N3dtSyncnetParams*, void*, hipStream_t);
+void n3dt_launch_syncnet_faces(int, int, int, const float*, const int*, int, float*, hipStream_t);
+void n3dt_launch_syncnet_fwd(int, const void*, const float*, const float*, float*, float*, double*, void*, hipStream_t);
+void n3dt_launch_syncnet_block(int, int, const void*, const float*, float*, void*, hipStream_t);
 }
 
 static thread_local char g_err[256] = "";
@@ -804,6 +812,106 @@ extern "C" int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int 
         return fail(N3DT_EINVAL, msg);
     }
     n3dt_launch_mel_windows(mel, T, mel_ld, mel_is_f64, start, n_windows, out, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// lip-sync expert (csrc/syncnet.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* syncnet_windows(int n) { return (n < 1 || n > SN_MAX_WINDOWS) ? "n outside 1..1024" : nullptr; }
+static const char* syncnet_frames(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes) {
+    if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 2..4096";
+    if (!frames || !boxes) return "NULL pointer";
+    if (n_boxes != 1 && n_boxes != n + SN_FACE_FRAMES - 1) return "n_boxes must be 1 or n + 4 (one box per frame)";
+    if ((((size_t)frames) | ((size_t)boxes)) & 3) return "frames and boxes must be 4-byte aligned";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_syncnet_packed_bytes(void) { return n3dt_syncnet_packed_layout_bytes(); }
+
+extern "C" int n3dt_syncnet_pack(const N3dtSyncnetParams* p, void* packed, void* stream) {
+    if (!p || !packed) return fail(N3DT_EINVAL, "n3dt_syncnet_pack: NULL argument");
+    if (((size_t)packed) & 255) return fail(N3DT_EINVAL, "n3dt_syncnet_pack: packed must be 256-byte aligned");
+    for (int b = 0; b < N3DT_SYNCNET_BLOCKS; ++b)
+        if (!p->weight[b] || !p->bias[b] || !p->bn_weight[b] || !p->bn_bias[b] || !p->bn_mean[b] || !p->bn_var[b])
+            return fail(N3DT_EINVAL, "n3dt_syncnet_pack: NULL parameter pointer");
+    n3dt_launch_syncnet_pack(p, packed, (hipStream_t)stream);
+    return check_hip("n3dt_syncnet_pack");
+}
+
+extern "C" size_t n3dt_syncnet_workspace_bytes(int n) {
+    const char* what = syncnet_windows(n);
+    if (what) {
+        snprintf(g_err, sizeof(g_err), "n3dt_syncnet_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_syncnet_ws_bytes(n);
+}
+
+extern "C" int n3dt_syncnet_face_windows(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes,
+                                         float* face_windows, void* stream) {
+    static const char* who = "n3dt_syncnet_face_windows";
+    char msg[160];
+    const char* what = syncnet_windows(n);
+    if (!what) what = syncnet_frames(n, height, width, frames, boxes, n_boxes);
+    if (!what) {
+        if (!face_windows) what = "NULL pointer";
+        else if (((size_t)face_windows) & 15) what = "face_windows must be 16-byte aligned";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_syncnet_faces(n, height, width, frames, boxes, n_boxes == 1 ? 0 : 4, face_windows, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_windows, const float* face_windows, const float* frames,
+                                const int32_t* boxes, int n_boxes, int height, int width, float* audio_emb, float* face_emb, double* cosv,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_syncnet_fwd";
+    char msg[160];
+    const char* what = syncnet_windows(n);
+    if (!what) {
+        if ((face_windows != nullptr) == (frames != nullptr)) what = "give exactly one of face_windows and frames";
+        else if (frames) what = syncnet_frames(n, height, width, frames, boxes, n_boxes);
+    }
+    if (!what) {
+        if (!packed || !mel_windows || !workspace) what = "NULL pointer";
+        else if (((size_t)cosv) & 7) what = "cos must be 8-byte aligned";
+        else if ((((size_t)mel_windows) | ((size_t)face_windows) | ((size_t)audio_emb) | ((size_t)face_emb)) & 15)
+            what = "mel_windows, face_windows, audio_emb and face_emb must be 16-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_syncnet_ws_bytes(n)) what = "workspace too small";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    if (frames) {
+        float* faces = n3dt_syncnet_ws_faces(n, workspace);
+        n3dt_launch_syncnet_faces(n, height, width, frames, boxes, n_boxes == 1 ? 0 : 4, faces, (hipStream_t)stream);
+        face_windows = faces;
+    }
+    n3dt_launch_syncnet_fwd(n, packed, mel_windows, face_windows, audio_emb, face_emb, cosv, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_syncnet_block(int block, int n, const void* packed, const float* in, float* out, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    static const char* who = "n3dt_syncnet_block";
+    char msg[160];
+    const char* what = syncnet_windows(n);
+    if (!what) {
+        if (block < 0 || block >= SN_BLOCKS) what = "block outside 0..30";
+        else if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)in) | ((size_t)out)) & 15) what = "in and out must be 16-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_syncnet_ws_bytes(n)) what = "workspace too small";
+    }
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_syncnet_block(block, n, packed, in, out, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
 

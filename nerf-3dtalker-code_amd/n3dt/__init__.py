@@ -4,6 +4,6 @@ from .headnerf import HeadNeRFNet, NeuralRenderer, MLPforNeRF  # noqa: F401
 from .audio import Audio2style  # noqa: F401
 from .mel import MelFrontend, MelStream, mel_basis  # noqa: F401
 from .optim import FlatAdam  # noqa: F401
-from .eval_utils import image_metrics, calc_eval_metrics, LPIPS  # noqa: F401
+from .eval_utils import image_metrics, calc_eval_metrics, LPIPS, SyncNet, SyncMeter  # noqa: F401
 from .train import validate  # noqa: F401
-from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel  # noqa: F401,E402
+from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet  # noqa: F401,E402

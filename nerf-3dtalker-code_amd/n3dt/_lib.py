@@ -44,6 +44,13 @@ class LpipsParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * LPIPS_LAYERS), ("bias", ctypes.c_void_p * LPIPS_LAYERS), ("lin", ctypes.c_void_p * LPIPS_LAYERS)]
 
 
+SYNCNET_BLOCKS = 31
+
+
+class SyncnetParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p * SYNCNET_BLOCKS) for name in ("weight", "bias", "bn_weight", "bn_bias", "bn_mean", "bn_var")]
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -110,6 +117,8 @@ EXPORTS = [
     "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
     "n3dt_lpips_packed_bytes", "n3dt_lpips_pack", "n3dt_lpips_workspace_bytes", "n3dt_lpips",
     "n3dt_mel_workspace_bytes", "n3dt_mel_spectrogram", "n3dt_mel_windows",
+    "n3dt_syncnet_packed_bytes", "n3dt_syncnet_pack", "n3dt_syncnet_workspace_bytes", "n3dt_syncnet_face_windows", "n3dt_syncnet_fwd",
+    "n3dt_syncnet_block",
 ]
 
 # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
@@ -267,6 +276,18 @@ def lib():
     L.n3dt_mel_spectrogram.argtypes = [i64, vp, i64, vp, i64, i64, ci, vp, vp, vp, i64, ci, vp, sz, vp]
     L.n3dt_mel_windows.restype = ci
     L.n3dt_mel_windows.argtypes = [i64, vp, i64, ci, ci, vp, vp, vp]
+    L.n3dt_syncnet_packed_bytes.restype = sz
+    L.n3dt_syncnet_packed_bytes.argtypes = []
+    L.n3dt_syncnet_pack.restype = ci
+    L.n3dt_syncnet_pack.argtypes = [ctypes.POINTER(SyncnetParams), vp, vp]
+    L.n3dt_syncnet_workspace_bytes.restype = sz
+    L.n3dt_syncnet_workspace_bytes.argtypes = [ci]
+    L.n3dt_syncnet_face_windows.restype = ci
+    L.n3dt_syncnet_face_windows.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp]
+    L.n3dt_syncnet_fwd.restype = ci
+    L.n3dt_syncnet_fwd.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.n3dt_syncnet_block.restype = ci
+    L.n3dt_syncnet_block.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp]
     L.n3dt_flat_adam_guard_bytes.restype = sz
     L.n3dt_flat_adam_guard_bytes.argtypes = []
     L.n3dt_flat_adam_guarded_step.restype = ci

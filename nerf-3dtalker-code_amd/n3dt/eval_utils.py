@@ -12,6 +12,8 @@ LPIPS (`LPIPS`, n3dt_lpips, csrc/lpips.hip) is lpips.LPIPS(
 five convolutions and the metric's five linear layers, from a torchvision / lpips state dict.  Nothing is downloaded, the `lpips`
 package is not a dependency and its pretrained weights have never been run through this code: parity is unpinned to the
 dependency.  Pass the object as `lpips=`; the older host callback `lpips_fn=` keeps working.
+The lip-sync score (`SyncNet`, `SyncMeter`, n3dt_syncnet_*, csrc/syncnet.hip) lives in n3dt/syncnet.py and is
+re-exported here: what single-frame metrics cannot see -- whether the rendered lips follow the audio.
 There is no CPU path.
 """
 import ctypes
@@ -20,6 +22,7 @@ import torch
 
 from . import ops
 from ._lib import LPIPS_INPUT_MODES, LpipsParams, check, lib
+from .syncnet import SyncMeter, SyncNet  # noqa: F401
 
 
 def _metrics(pred, gt):

@@ -358,6 +358,27 @@ def lpips_alex_state_dict(seed=0):
     return sd
 
 
+def syncnet_state_dict(seed=0):
+    """Seeded stand-in for the weights of Wav2Lip's lip-sync expert (`lipsync_expert.pth` cannot be fetched offline), under the
+    reference's keys for `SyncNet_color` (n3dt.syncnet.load_syncnet): every convolution with torch's default initialisation
+    (kaiming_uniform_(a = sqrt(5)) weights and the matching uniform bias, i.e. both U(-1 / sqrt(fan_in), 1 / sqrt(fan_in))), and
+    non-trivial batch-norm tensors: running_mean ~ N(0, 0.1), running_var ~ U(0.5, 1.5), weight ~ U(0.5, 1.5), bias ~ N(0, 0.1).
+    With these the class keeps O(1) activations through all its blocks."""
+    from .syncnet import BLOCKS, block_names
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, (cin, cout, (kh, kw), _, _, _) in zip(block_names(), BLOCKS):
+        bound = 1.0 / math.sqrt(cin * kh * kw)
+        sd[name + ".conv_block.0.weight"] = (torch.rand(cout, cin, kh, kw, generator=gen) * 2.0 - 1.0) * bound
+        sd[name + ".conv_block.0.bias"] = (torch.rand(cout, generator=gen) * 2.0 - 1.0) * bound
+        sd[name + ".conv_block.1.weight"] = torch.rand(cout, generator=gen) + 0.5
+        sd[name + ".conv_block.1.bias"] = torch.randn(cout, generator=gen) * 0.1
+        sd[name + ".conv_block.1.running_mean"] = torch.randn(cout, generator=gen) * 0.1
+        sd[name + ".conv_block.1.running_var"] = torch.rand(cout, generator=gen) + 0.5
+        sd[name + ".conv_block.1.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    return sd
+
+
 def mel_batch(B, seed=0):
     """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
     range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""

@@ -227,7 +227,7 @@ class GraphedTrainStep:
 _RENDER_KEYS = ("shape_code", "appea_code", "batch_Rmats", "batch_Tvecs", "batch_inv_inmats")
 
 
-def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lpips=None):
+def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lpips=None, sync=None):
     """The reference's validation pass (talker_trainer.py:1087-1150): render every held-out batch with net("test", ...) and score
     it with n3dt.eval_utils (SSIM and PSNR on the device; LPIPS only with `lpips` or `lpips_fn`, see calc_eval_metrics).
     `batches`: an iterable of dicts with the keys of synthetic.frame_inputs plus "gt_rgb" [B,3,P,P], "mask" (accepted and ignored,
@@ -238,6 +238,10 @@ def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lp
     also "LPIPS": its mean over the SAME images (one call per scored image, on [P,P,3] uint8 arrays), at the cost of one copy to
     the host and one synchronisation per batch.  With `lpips`, an eval_utils.LPIPS object, "LPIPS" is computed on the device
     and accumulated there with the other two: still one synchronisation.  Giving both raises.
+    With `sync`, an eval_utils.SyncMeter over the sequence's mel spectrogram, every rendered batch's merge_img is pushed to it in
+    order -- ALL images of the batch, whatever `all_images` says; the batches must then be consecutive frames -- and the result
+    gains "SYNC_conf", "SYNC_loss" and "SYNC_windows" (the meter's sync_conf, sync_loss and n_windows, over everything pushed to
+    it so far; the meter is the caller's and is not reset).  Still one synchronisation.
     net.invalidate_packed() runs first, so weights written through `.data` or by a replayed training graph since the last
     render are the ones rendered; the metrics accumulate on the device and the host synchronises once, at the end.
     The reference calls model.eval() first and never switches back; the "test" forward does not read net.training, so this
@@ -252,6 +256,8 @@ def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lp
             audiostyle = b["audiostyle"] if audio2style is None else audio2style(b["mel"])
             pred = net("test", b["batch_xy"], b["batch_uv"], audiostyle, bg_code=None, **{k: b[k] for k in _RENDER_KEYS})
             merge, gt = pred["coarse_dict"]["merge_img"], b["gt_rgb"]
+            if sync is not None:
+                sync.push(merge)
             if not all_images:
                 merge, gt = merge[:1], gt[:1]
             m = eval_utils._metrics(merge, gt).sum(dim=1)  # [2]: this batch's sums of SSIM and PSNR
@@ -265,8 +271,15 @@ def validate(net, batches, audio2style=None, all_images=False, lpips_fn=None, lp
                 lpips_sum += sum(float(lpips_fn(u8[i], u8[n + i])) for i in range(n))
     if count == 0:
         raise ValueError("validate: no batches")
-    means = (total / count).tolist()
+    if sync is not None:
+        n_img = total.shape[0]
+        means = torch.cat([total / count, sync._device_result()]).tolist()  # the one synchronisation
+        means, synced = means[:n_img], sync._finish(means[n_img:])
+    else:
+        means = (total / count).tolist()
     res = {"SSIM": means[0], "PSNR": means[1], "count": count}
+    if sync is not None:
+        res["SYNC_conf"], res["SYNC_loss"], res["SYNC_windows"] = synced["sync_conf"], synced["sync_loss"], synced["n_windows"]
     if lpips is not None:
         res["LPIPS"] = means[2]
     if lpips_fn is not None:
