@@ -488,7 +488,17 @@ int n3dt_loss_bwd(int batch, int pixels, const float* merge_img, const float* bg
  *   n3dt_vgg_loss_bwd  g_total [1] (device) = dL/d(sum) -> d_merge [B,3,P,P] (overwritten; 0 where merge_img is not finite);
  *                      `saved` from the forward with the same batch, img_size, precision and packed weights
  * precision N3DT_F32 (split-bf16 operands, three products: ~16 mantissa bits) or N3DT_BF16; 1 <= batch <= 64,
- * 16 <= img_size <= 2048. */
+ * 16 <= img_size <= 2048.
+ * n3dt_vgg_conv_stage runs ONE conv of the table (layer 0..9) on the caller's buffers at the geometry the caller names, through the
+ * launch path of the two calls above and the pack of n3dt_vgg_pack (a debugging aid: the tests judge the conv kernel one layer at
+ * a time with it).  All maps are NHWC fp32.
+ *   dgrad 0  in [n_img, H+2, W+2, C_in] with a zero halo -- for the layers that follow a 2x2 max-pool (2, 4, 7) the UN-pooled
+ *            [n_img, 2H+2, 2W+2, C_in] -- -> out = ReLU(conv + bias) [n_img, H, W, C_out]; gate must be NULL
+ *   dgrad 1  in [n_img, H+2, W+2, C_out] with a zero halo (the gradient of the layer's output) -> out [n_img, H, W, C_in], the
+ *            gradient of its input; gate (or NULL) has out's layout, out is kept where gate > 0 and is 0 elsewhere
+ *   out_pad 1: out is [n_img, H+2, W+2, C] and only its interior is written (the caller owns the halo); 0: no halo.
+ * Image i's result depends on image i and the pack alone, not on n_img; bit-reproducible.  1 <= n_img <= 128, 1 <= H, W <= 224; in,
+ * gate and out 16-byte, packed 256-byte aligned. */
 #define N3DT_VGG_CONVS 10   /* torchvision vgg16().features indices 0,2,5,7,10,12,14,17,19,21 */
 typedef struct N3dtVggParams {
     const float* weight[N3DT_VGG_CONVS];
@@ -503,6 +513,8 @@ int n3dt_vgg_loss_fwd(int batch, int img_size, int precision, const void* packed
                       void* stream);
 int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const void* packed, const float* merge_img, const float* g_total,
                       const void* saved, size_t saved_bytes, float* d_merge, void* ws, size_t ws_bytes, void* stream);
+int n3dt_vgg_conv_stage(int precision, const void* packed, int layer, int dgrad, int n_img, int H, int W, const float* in,
+                        const float* gate, float* out, int out_pad, void* stream);
 
 /* ---- Audio2style encoder (talker_trainer.py:407-461) ------------------------------------------------------------------
  * mel [T, 1280] (each frame's 80x16 window, row-major) is ONE sequence of T frames through

@@ -84,6 +84,7 @@ size_t n3dt_vgg_ws_floats(int);
 void n3dt_launch_vgg_pack(int, const N3dtVggParams*, void*, hipStream_t);
 void n3dt_launch_vgg_fwd(int, int, int, const void*, const float*, const float*, const float*, float, float*, void*, void*, hipStream_t);
 void n3dt_launch_vgg_bwd(int, int, int, const void*, const float*, const float*, const void*, float*, void*, hipStream_t);
+void n3dt_launch_vgg_conv_stage(int, const void*, int, int, int, int, int, const float*, const float*, float*, int, hipStream_t);
 size_t n3dt_a2s_saved_floats(int);
 size_t n3dt_a2s_ws_floats(int);
 void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* const[3], float*, void*, void*, hipStream_t);
@@ -540,6 +541,30 @@ extern "C" int n3dt_vgg_loss_bwd(int batch, int img_size, int precision, const v
     if (ws_bytes < n3dt_vgg_ws_floats(batch) * sizeof(float)) return fail(N3DT_EWORKSPACE, "n3dt_vgg_loss_bwd: workspace too small");
     n3dt_launch_vgg_bwd(batch, img_size, precision, packed, merge_img, g_total, saved, d_merge, ws, (hipStream_t)stream);
     return check_hip("n3dt_vgg_loss_bwd");
+}
+
+extern "C" int n3dt_vgg_conv_stage(int precision, const void* packed, int layer, int dgrad, int n_img, int H, int W, const float* in,
+                                   const float* gate, float* out, int out_pad, void* stream) {
+    static const char* who = "n3dt_vgg_conv_stage";
+    int rc = check_vgg(who, 1, 224, precision);
+    if (rc) return rc;
+    char msg[160];
+    const char* what = nullptr;
+    if (layer < 0 || layer >= N3DT_VGG_CONVS) what = "layer outside 0..9";
+    else if (dgrad != 0 && dgrad != 1) what = "direction must be 0 (forward) or 1 (dgrad)";
+    else if (n_img < 1 || n_img > 128) what = "n_img outside 1..128";
+    else if (H < 1 || H > 224 || W < 1 || W > 224) what = "H, W outside 1..224";
+    else if (out_pad != 0 && out_pad != 1) what = "out_pad must be 0 or 1";
+    else if (!packed || !in || !out) what = "NULL pointer";
+    else if (gate && !dgrad) what = "a gate goes with dgrad only";
+    else if ((((size_t)in) | ((size_t)out) | ((size_t)gate)) & 15) what = "in, gate and out must be 16-byte aligned";
+    else if (((size_t)packed) & 255) what = "packed must be 256-byte aligned";
+    if (what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(N3DT_EINVAL, msg);
+    }
+    n3dt_launch_vgg_conv_stage(precision, packed, layer, dgrad, n_img, H, W, in, gate, out, out_pad, (hipStream_t)stream);
+    return check_hip(who);
 }
 
 // ---- Audio2style encoder (csrc/audio_lstm.hip) ----

@@ -590,6 +590,31 @@ extern "C" void n3dt_launch_vgg_fwd(int batch, int P, int precision, const void*
     vgg_l1_finish_kernel<<<1, 256, 0, st>>>(partial, cnt, terms);
 }
 
+// ONE conv of the table at a geometry the caller names, on the caller's buffers (n3dt_vgg_conv_stage): the arguments the two loops
+// above and below form for layer l, with n_img, H, W from the caller instead of 2 batch, kH[l], kH[l].
+extern "C" void n3dt_launch_vgg_conv_stage(int precision, const void* packed, int l, int dgrad, int n_img, int H, int W, const float* in,
+                                           const float* gate, float* out, int out_pad, hipStream_t st) {
+    VggConvArgs a = weights_of(precision, packed, l, dgrad ? 1 : 0);
+    a.in = in;
+    a.out = out;
+    a.n_img = n_img;
+    a.H = H;
+    a.W = W;
+    a.out_pad = out_pad;
+    if (!dgrad) {
+        a.bias = (const float*)((const char*)packed + vgg_layout(precision).bias[l]);
+        a.cin = kCin[l];
+        a.cout = kCout[l];
+        a.relu = 1;
+        conv(precision, a, l == 0 ? 2 : (kPoolIn[l] ? 1 : 0), st);
+    } else {
+        a.gate = gate;
+        a.cin = kCout[l];
+        a.cout = kCin[l];
+        conv(precision, a, 0, st);
+    }
+}
+
 extern "C" void n3dt_launch_vgg_bwd(int batch, int P, int precision, const void* packed, const float* merge, const float* g_total,
                                     const void* saved, float* d_merge, void* ws, hipStream_t st) {
     float* buf[2] = {(float*)ws, (float*)ws + bwd_buf_floats(batch)};

@@ -109,7 +109,7 @@ EXPORTS = [
     "n3dt_img_to_uint8", "n3dt_sample_points", "n3dt_embed", "n3dt_mlp_points_workspace_bytes", "n3dt_mlp_points", "n3dt_composite",
     "n3dt_ray_vd_bias", "n3dt_embed_freqs",
     "n3dt_neural_render_pack", "n3dt_neural_render_fwd_reuse", "n3dt_stage_inputs", "n3dt_graph_begin", "n3dt_graph_end", "n3dt_graph_launch", "n3dt_graph_destroy",
-    "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd",
+    "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd", "n3dt_vgg_conv_stage",
     "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
     "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
     "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
@@ -245,6 +245,8 @@ def lib():
     L.n3dt_vgg_loss_fwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, sz, vp, sz, vp]
     L.n3dt_vgg_loss_bwd.restype = ci
     L.n3dt_vgg_loss_bwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.n3dt_vgg_conv_stage.restype = ci
+    L.n3dt_vgg_conv_stage.argtypes = [ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp]
     L.n3dt_a2s_saved_bytes.restype = sz
     L.n3dt_a2s_saved_bytes.argtypes = [ci]
     L.n3dt_a2s_workspace_bytes.restype = sz

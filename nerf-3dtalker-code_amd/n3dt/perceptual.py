@@ -124,6 +124,31 @@ class VGGPerceptualLoss(object):
             self._packed[key] = packed
         return self._packed[key]
 
+    def conv_stage(self, layer, x, dgrad=False, gate=None, out=None, out_pad=False):
+        """n3dt_vgg_conv_stage: ONE conv of the table on NHWC fp32 device maps (the tests judge the kernel a layer at a time with it).
+        x [n, H+2, W+2, C] with a zero halo (forward of layers 2, 4, 7: the un-pooled [n, 2H+2, 2W+2, C]).  forward: ReLU(conv + bias)
+        [n, H, W, C_out]; dgrad: the gradient of the layer's input [n, H, W, C_in], kept where gate > 0 (gate: out's layout).
+        out_pad: out is [n, H+2, W+2, C], interior written only; pass `out` to choose what the halo holds."""
+        from . import ops
+        from ._lib import lib, check
+        cin, cout = VGG_CONV_CHANNELS[layer]
+        pooled = (not dgrad) and layer in (2, 4, 7)
+        n, hp, wp, c = x.shape
+        if c != (cout if dgrad else cin) or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("VGGPerceptualLoss.conv_stage: layer %d %s takes contiguous fp32 [n, H+2, W+2, %d], got %s %s"
+                             % (layer, "dgrad" if dgrad else "forward", cout if dgrad else cin, x.dtype, tuple(x.shape)))
+        H, W = ((hp - 2) // 2, (wp - 2) // 2) if pooled else (hp - 2, wp - 2)
+        shape = (n, H + 2, W + 2, cin if dgrad else cout) if out_pad else (n, H, W, cin if dgrad else cout)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=x.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("VGGPerceptualLoss.conv_stage: out must be contiguous fp32 %s, got %s" % (shape, tuple(out.shape)))
+        if gate is not None and (tuple(gate.shape) != shape or gate.dtype != torch.float32 or not gate.is_contiguous()):
+            raise ValueError("VGGPerceptualLoss.conv_stage: gate must be contiguous fp32 %s, got %s" % (shape, tuple(gate.shape)))
+        check(lib().n3dt_vgg_conv_stage(self.prec, ops._ptr(self._packed_for(x.device)), layer, int(bool(dgrad)), n, H, W, ops._ptr(x),
+                                        ops._ptr(gate), ops._ptr(out), int(bool(out_pad)), ops._stream()), "n3dt_vgg_conv_stage")
+        return out
+
     def _check(self, merge_img, gt, mask):
         if merge_img.dim() != 4 or merge_img.shape[1] != 3 or merge_img.shape[2] != merge_img.shape[3]:
             raise ValueError("VGGPerceptualLoss: images must be [B,3,P,P], got %s" % (tuple(merge_img.shape),))
