@@ -395,14 +395,15 @@ def render_train_fwd(geom, packed, params, xy, R, T, Kinv, shape, appea, audio, 
 
 
 def render_bwd(geom, params, grads, shape, appea, audio, bg_featmap, d_merge, saved, cam=None, precision=0, d_bg=None, frozen=False,
-               cam_grads=None):
+               cam_grads=None, d_fg=None, d_ba=None):
     """Backward of render_train_fwd.  `grads` (MlpParams struct of zeroed tensors) is accumulated into.
     cam = (xy, R, T, Kinv, t_rand) requests camera gradients.
     Returns (d_bg_featmap [C,Nr], d_shape, d_appea, d_audio, d_R, d_T) -- and, with geom.vd_dim > 0 (include_vd), a seventh
     entry d_ray_bias [B, N_r, 192].
     cam_grads: None -- d_R and d_T, through n3dt_render_bwd (the call as it always was).  Else the names among "R", "T", "Kinv",
     "xy" whose gradient is wanted, through n3dt_render_bwd_cam: the others come back as None, and the tuple ends in two more
-    entries, d_Kinv [B,3,3] and d_xy [B,2,N_r] (contiguous whatever the strides of xy)."""
+    entries, d_Kinv [B,3,3] and d_xy [B,2,N_r] (contiguous whatever the strides of xy).
+    d_fg [B, N_r, C], d_ba [B, N_r]: cotangents of fg_feat and bg_alpha beside d_merge (fp32, contiguous)."""
     dev = d_merge.device
     B, Nr, C = geom.batch, geom.n_rays, geom.feat_nc
     if frozen:  # grads is None: no parameter gradient, no d_bg_featmap
@@ -435,7 +436,7 @@ def render_bwd(geom, params, grads, shape, appea, audio, bg_featmap, d_merge, sa
     ws = WORKSPACE.get("train", wbytes, dev)
     head = (ctypes.byref(geom), precision, ctypes.byref(params), None if grads is None else ctypes.byref(grads), _ptr(shape), _ptr(appea),
             _ptr(audio), _ptr(bg_featmap),
-            _ptr(d_merge), None, None, _ptr(saved), saved.numel(), _ptr(d_bg), _ptr(d_shape), _ptr(d_appea), _ptr(d_audio), _ptr(d_ray),
+            _ptr(d_merge), _ptr(d_fg), _ptr(d_ba), _ptr(saved), saved.numel(), _ptr(d_bg), _ptr(d_shape), _ptr(d_appea), _ptr(d_audio), _ptr(d_ray),
             *cam_ptrs, _ptr(d_R), _ptr(d_T))
     if cam_grads is None:
         check(lib().n3dt_render_bwd(*head, _ptr(ws), wbytes, _stream()), "n3dt_render_bwd")
