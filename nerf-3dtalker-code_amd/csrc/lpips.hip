@@ -2,16 +2,19 @@
 // (talker_trainer.py:1087-1150 -> Utils/Eval_utils.py:43-47,108-115).  The addresses that can go wrong at
 // an edge -- the reinterpretation, the convolutions' rows, taps and stores, the pool windows, the halo cells -- come from
 // lpips_core.h, which tests/lpips_core_host.cpp also compiles and walks over the same grids.  That program re-types the loop
-// nests of the convolution, pool and halo kernels below (block / wave / lane / K step, the epilogue's register -> row map, the
-// element decodes): a change to one of those loops here must be made there too.  The flat element decodes of the prologue, the
-// distance kernel and the pack kernel are written inline and are not walked.
+// nests of the convolution, pool and halo kernels below (block / wave / lane / K step, the pool's and the halo kernel's element
+// decodes): a change to one of those loops here must be made there too.  The epilogue's register -> row map, the pack kernel's
+// element decode and the address the MFMA step reads its weights at are not re-typed: they are conv_frag.h's functions, which
+// that program calls too, walking the pack of every layer.  The flat element decodes of the prologue and the distance kernel
+// are written inline and are not walked.
 //
 //   prologue   pred, gt [B,3,H,W] fp32 -> in0: one batch of 2B images (predictions first, then targets), NHWC with a 2-pixel zero
 //              halo.  reference mode: quantise to bytes (evm_quantise), read them as the reference's reshape(-1,3,h,w) of the HWC
 //              image does, values 0..255; standard mode: 2 clamp(x,0,1) - 1, channels as given.  Then (v - shift) / scale in fp32.
 //   conv x5    torchvision alexnet().features convolutions + bias + ReLU as implicit GEMMs on v_mfma_f32_32x32x16_bf16
 //              (M = output pixels, N = C_out, k = tap * C_in + c_in), every operand split x = hi + lo into two bf16s and three
-//              products hi*hi + hi*lo + lo*hi accumulated in fp32 (vgg_loss.hip's N3DT_F32 mode; there is no other mode here).
+//              products hi*hi + hi*lo + lo*hi accumulated in fp32: conv_mfma.h's step, which vgg_loss.hip and syncnet.hip share,
+//              in its split form (there is no other mode here).
 //              conv1 (C_in = 3, 11x11, stride 4) gathers its operand element by element; the others read 8 channels at a time.
 //   pool x2    3x3 / stride 2 max-pool of relu1 and relu2 into a halo-padded map of their own (relu1 and relu2 stay: they are
 //              LPIPS features).
@@ -27,17 +30,13 @@
 
 #include "../../include/n3dt.h"
 #include "eval_metrics_core.h"
+#include "conv_mfma.h"
 #include "lpips_core.h"
 
-typedef __bf16 lp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
-
-static inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // ---- packed weights ------------------------------------------------------------------------------------------------------------
-// Per conv one B matrix in vgg_pack_kernel's fragment order, [Kp/16][Np/32] fragments of 64 lanes x 8 bf16: lane (r = l & 31,
-// h = l >> 5) element j holds B[k = 16 s + 8 h + j][n = 32 t + r] = W[n][ci][ky][kx], k = (ky * ksize + kx) * C_in + ci; rows
-// k >= K are zero.  The lo matrix lies right behind the hi matrix.  Then the fp32 biases, then the fp32 lin weights.
+// Per conv one B matrix in conv_frag.h's fragment order, [Kp/16][Np/32] fragments of 64 lanes x 8 bf16: element e holds
+// B[k][n] = W[n][ci][ky][kx] with (k, n) = cf_pack_decode(e), k = (ky * ksize + kx) * C_in + ci; rows k >= K are zero.  The lo
+// matrix lies right behind the hi matrix.  Then the fp32 biases, then the fp32 lin weights.
 struct LpPackLayout {
     size_t w[LP_LAYERS], elems[LP_LAYERS], bias[LP_LAYERS], lin[LP_LAYERS], total;
 };
@@ -66,10 +65,8 @@ __global__ __launch_bounds__(256) void lpips_pack_kernel(const float* __restrict
                                                          __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)kp * cout) return;
-    const int frag = (int)(e / 512), within = (int)(e % 512);
-    const int lane = within >> 3, j = within & 7;
-    const int s = frag / (cout / 32), t = frag % (cout / 32);
-    const int k = 16 * s + 8 * (lane >> 5) + j, n = 32 * t + (lane & 31);
+    int k, n;
+    cf_pack_decode(e, cout / 32, &k, &n);
     float w = 0.0f;
     if (k < ksize * ksize * cin) {
         const int tap = k / cin, ci = k - tap * cin;
@@ -77,7 +74,7 @@ __global__ __launch_bounds__(256) void lpips_pack_kernel(const float* __restrict
     }
     const __bf16 h = (__bf16)w;
     hi[e] = h;
-    lo[e] = (__bf16)(w - (float)h);
+    lo[e] = conv_lo(w, h);
 }
 
 __global__ __launch_bounds__(256) void lpips_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
@@ -134,41 +131,6 @@ struct LpConvArgs {
     int n_img, Ho, Wo, Hp, Wp, cin, ksize, stride, K, kp, cout, out_pad;
 };
 
-// the MFMA step of vgg_loss.hip's split mode: two 32-row A tiles against two 32-column B tiles, three products each
-__device__ __forceinline__ void lp_mma_step(const LpConvArgs& a, int s, int nt0, int lane, const float (&av)[2][8], lp_f32x16 (&acc)[2][2]) {
-    lp_bf16x8 ahi[2], alo[2], bhi[2], blo[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const __bf16 h = (__bf16)av[mt][j];
-            ahi[mt][j] = h;
-            alo[mt][j] = (__bf16)(av[mt][j] - (float)h);
-        }
-    const int ntiles = a.cout >> 5;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const size_t f = ((size_t)s * ntiles + nt0 + nt) * 64 + lane;
-        bhi[nt] = reinterpret_cast<const lp_bf16x8*>(a.whi)[f];
-        blo[nt] = reinterpret_cast<const lp_bf16x8*>(a.wlo)[f];
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], blo[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-        }
-}
-
-__device__ __forceinline__ void lp_load8(const float* p, float* v) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    const float4 y = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-}
-
 // 256 threads = 4 waves; a wave computes LP_TILE_M output pixels x LP_TILE_N output channels (2 x 2 tiles of 32 x 32).
 // GATHER false: cin % 16 == 0, a k-step is 16 channels of one tap;  GATHER true: conv1 (C_in = 3, 11x11), k decoded per element
 // with the layer's constants folded in.
@@ -187,13 +149,8 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(LpConvArgs a) {
         lp_row_pixel(m0 + mt * 32 + r, M, a.Ho, a.Wo, &img, &y, &x);  // rows past M compute a clamped pixel and are never stored
         base[mt] = a.in + lp_field_base(img, y, x, a.stride, a.Hp, a.Wp, a.cin);
     }
-    lp_f32x16 acc[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.0f;
+    conv_f32x16 acc[2][2];
+    CONV_ZERO_ACC(acc, 2);
     float av[2][8];
 
     if constexpr (!GATHER) {
@@ -202,8 +159,8 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(LpConvArgs a) {
             const size_t toff = lp_tap_offset(tap, a.ksize, a.Wp, a.cin) + 8 * h;
             for (int c0 = 0; c0 < a.cin; c0 += 16, ++s) {
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) lp_load8(base[mt] + toff + c0, av[mt]);
-                lp_mma_step(a, s, nt0, lane, av, acc);
+                for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
+                conv_mma_step<true, 2>(a.whi, a.wlo, a.cout, s, nt0, lane, av, acc);
             }
         }
     } else {
@@ -216,16 +173,16 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(LpConvArgs a) {
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) av[mt][j] = ok ? base[mt][off] : 0.0f;
             }
-            lp_mma_step(a, s, nt0, lane, av, acc);
+            conv_mma_step<true, 2>(a.whi, a.wlo, a.cout, s, nt0, lane, av, acc);
         }
     }
 
-    // epilogue: accumulator register i of lane (r, h) is output row (i & 3) + 8 (i >> 2) + 4 h, column r
+    // epilogue: accumulator register i of lane (r, h) is output row cf_acc_row(i, h), column r
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const long long m = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const long long m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= M) continue;
             int img, y, x;
             lp_row_pixel(m, M, a.Ho, a.Wo, &img, &y, &x);
@@ -287,12 +244,6 @@ __global__ __launch_bounds__(256) void lpips_halo_kernel(LpHaloList L, int n_img
 }
 
 // ---- distance --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lp_wave_sum(double v) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w, 64);  // a butterfly: every lane ends with the same bits
-    return v;
-}
-
 // grid (LP_PARTS, B): workgroup (p, b) owns pixels i = 4 p + wave, stepping 4 LP_PARTS, of pair b (images b and B + b) -- pair-local
 // indices only.  feat [2B, H + 2 pad, W + 2 pad, C], C a multiple of 64.  partial[b * LP_PARTS + p] = the workgroup's sum of d.
 __global__ __launch_bounds__(256) void lpips_dist_kernel(const float* __restrict__ feat, int B, int H, int W, int C, int pad,
@@ -312,13 +263,13 @@ __global__ __launch_bounds__(256) void lpips_dist_kernel(const float* __restrict
             s0 += u * u;
             s1 += v * v;
         }
-        const double n0 = sqrt(lp_wave_sum(s0)) + 1e-10, n1 = sqrt(lp_wave_sum(s1)) + 1e-10;
+        const double n0 = sqrt(conv_wave_sum(s0)) + 1e-10, n1 = sqrt(conv_wave_sum(s1)) + 1e-10;
         double d = 0.0;
         for (int c = lane; c < C; c += 64) {
             const double t = (double)f0[c] / n0 - (double)f1[c] / n1;
             d += (double)lin[c] * (t * t);
         }
-        acc += lp_wave_sum(d);
+        acc += conv_wave_sum(d);
     }
     if (lane == 0) s_w[wave] = acc;
     __syncthreads();
@@ -387,11 +338,6 @@ extern "C" void n3dt_launch_lpips_pack(const N3dtLpipsParams* p, void* packed, h
     }
 }
 
-static unsigned lp_grid(size_t work) {
-    const size_t blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
-}
-
 extern "C" void n3dt_launch_lpips(int batch, int height, int width, int input_mode, const void* packed, const float* pred, const float* gt,
                                   double* out, double* layers, void* workspace, hipStream_t st) {
     const LpPackLayout L = lp_layout();
@@ -406,13 +352,13 @@ extern "C" void n3dt_launch_lpips(int batch, int height, int width, int input_mo
     float* pool[2] = {(float*)(ws + w.pool[0]), (float*)(ws + w.pool[1])};
     double* partial = (double*)(ws + w.partial);
 
-    lpips_prologue_kernel<<<lp_grid(g.in0 / 3), 256, 0, st>>>(batch, height, width, input_mode == N3DT_LPIPS_STANDARD, pred, gt, in0);
+    lpips_prologue_kernel<<<conv_grid(g.in0 / 3), 256, 0, st>>>(batch, height, width, input_mode == N3DT_LPIPS_STANDARD, pred, gt, in0);
     const float* in = in0;
     int Hp = height + 4, Wp = width + 4;
     for (int l = 0; l < LP_LAYERS; ++l) {
         if (l == 1 || l == 2) {  // the pool in front of conv2 and conv3, padded for that convolution
             const int pad = lp_pad(l);
-            lpips_pool_kernel<<<lp_grid(g.pool[l - 1] / 4), 256, 0, st>>>(relu[l - 1], n_img, g.fh[l - 1], g.fw[l - 1], lp_cout(l - 1), g.fh[l], g.fw[l],
+            lpips_pool_kernel<<<conv_grid(g.pool[l - 1] / 4), 256, 0, st>>>(relu[l - 1], n_img, g.fh[l - 1], g.fw[l - 1], lp_cout(l - 1), g.fh[l], g.fw[l],
                                                                           pad, pool[l - 1]);
             in = pool[l - 1];
             Hp = g.fh[l] + 2 * pad;

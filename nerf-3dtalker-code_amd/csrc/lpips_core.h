@@ -5,8 +5,10 @@
  * Included by csrc/lpips.hip, whose convolution, pool and halo kernels and whose prologue's gather take their addresses from the
  * functions below, and by tests/lpips_core_host.cpp, which walks the very same functions over those kernels' grids on the CPU
  * (under the address and undefined-behaviour sanitizers), so the reinterpretation, the tap and halo addressing, the pool
- * windows and the rows past M are checked without a GPU.  The flat element decodes of the prologue's output, the distance kernel
- * and the pack kernel stay in lpips.hip.  Compiles as host C++ on its own; the __host__ __device__ qualifiers exist only under hipcc.
+ * windows and the rows past M are checked without a GPU.  The weight pack's fragment arithmetic and the epilogue's register ->
+ * row map are conv_frag.h's, shared with the other convolutions and walked by the same program; the flat element decodes of the
+ * prologue's output and the distance kernel stay in lpips.hip.  Compiles as host C++ on its own; the __host__ __device__
+ * qualifiers exist only under hipcc.
  *
  * Maps.  Every activation is NHWC fp32; `pad` is the zero halo the NEXT convolution needs.
  *   in0    [n, H + 4, W + 4, 3]       the scaled input, pad 2

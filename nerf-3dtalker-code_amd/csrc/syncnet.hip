@@ -2,15 +2,18 @@
 // wav_models/syncnet.py over wav_models/conv.py).  The geometry table and every address that can go wrong at
 // an edge -- the rows of the GEMM, the halo cells, taps, residual reads and stores -- come from syncnet_core.h, which
 // tests/syncnet_core_host.cpp also compiles and walks over the same grid for all 31 blocks.  That program re-types the loop nest of
-// the convolution kernel below (block / wave / lane / K step, the epilogue's register -> row map): a change to that loop here
-// must be made there too.  The flat element decodes of the layout, prologue, pack and tail kernels are written inline.
+// the convolution kernel below (block / wave / lane / K step): a change to that loop here must be made there too.  The epilogue's
+// register -> row map, the pack kernel's element decode and the address the MFMA step reads its weights at are not re-typed:
+// they are conv_frag.h's functions, which that program calls too, walking the pack of every block.  The flat element decodes of
+// the layout, prologue and tail kernels are written inline.
 //
 //   faces      frames [F,3,H,W] fp32 RGB + crop boxes -> face windows [n,15,48,96]: crop, bilinear resample to 96 x 96 with
 //              half-pixel centres in float64, rows 48..95, BGR, channel 3 t + c for frame t of the window
 //   layout     [n,C,H,W] -> NHWC with C padded to 16 and the first block's zero halo
 //   conv x31   Conv2d + folded BatchNorm2d (+ the block's own input) + ReLU as an implicit GEMM on v_mfma_f32_32x32x16_bf16
 //              (M = cells of the padded output map, N = C_out, k = tap * C_in + c_in), every operand split x = hi + lo into two
-//              bf16s and three products hi*hi + hi*lo + lo*hi accumulated in fp32.  There is no other mode.
+//              bf16s and three products hi*hi + hi*lo + lo*hi accumulated in fp32: conv_mfma.h's step, which vgg_loss.hip and
+//              lpips.hip share, in its split form.  There is no other mode.
 //   tail       per window x / max(||x||_2, 1e-12) of both 512-vectors and their dot product, in float64, in a fixed order
 //
 // Every window goes through identical code with the same K order, no split-K and no atomics: a window's embeddings depend
@@ -19,17 +22,13 @@
 #include <stdint.h>
 
 #include "../../include/n3dt.h"
+#include "conv_mfma.h"
 #include "syncnet_core.h"
 
-typedef __bf16 sn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float sn_f32x16 __attribute__((ext_vector_type(16)));
-
-static inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // ---- packed weights ------------------------------------------------------------------------------------------------------------
-// Per block one B matrix in fragment order, [K/16][C_out/32] fragments of 64 lanes x 8 bf16: lane (r = l & 31, h = l >> 5)
-// element j holds B[k = 16 s + 8 h + j][n = 32 t + r] = w'[n][ci][ky][kx], k = (ky kw + kx) cinp + ci; rows of the padded
-// channels are zero.  The lo matrix lies right behind the hi matrix.  Then the folded fp32 biases.
+// Per block one B matrix in conv_frag.h's fragment order, [K/16][C_out/32] fragments of 64 lanes x 8 bf16: element e holds
+// B[k][n] = w'[n][ci][ky][kx] with (k, n) = cf_pack_decode(e), k = (ky kw + kx) cinp + ci; rows of the padded channels are
+// zero.  The lo matrix lies right behind the hi matrix.  Then the folded fp32 biases.
 struct SnPackLayout {
     size_t w[SN_BLOCKS], elems[SN_BLOCKS], bias[SN_BLOCKS], total;
 };
@@ -61,16 +60,14 @@ __global__ __launch_bounds__(256) void syncnet_pack_kernel(const float* __restri
                                                            __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)K * cout) return;
-    const int frag = (int)(e / 512), within = (int)(e % 512);
-    const int lane = within >> 3, j = within & 7;
-    const int s = frag / (cout / 32), t = frag % (cout / 32);
-    const int k = 16 * s + 8 * (lane >> 5) + j, n = 32 * t + (lane & 31);
+    int k, n;
+    cf_pack_decode(e, cout / 32, &k, &n);
     const int tap = k / cinp, ci = k - tap * cinp;
     float w = 0.0f;
     if (ci < cin) w = (float)((double)W[((size_t)n * cin + ci) * taps + tap] * sn_bn_scale(gamma, var, n));
     const __bf16 h = (__bf16)w;
     hi[e] = h;
-    lo[e] = (__bf16)(w - (float)h);
+    lo[e] = conv_lo(w, h);
 }
 
 __global__ __launch_bounds__(256) void syncnet_bias_kernel(const float* __restrict__ bias, const float* __restrict__ gamma,
@@ -159,42 +156,6 @@ struct SnConvArgs {
     int n, Ho, Wo, Hp, Wp, Hq, Wq, cinp, cout, kh, kw, sh, sw, ipad, opad, residual;
 };
 
-__device__ __forceinline__ void sn_load8(const float* p, float* v) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    const float4 y = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-}
-
-// one K step of 16: two 32-row A tiles against NT 32-column B tiles, three products each
-template <int NT>
-__device__ __forceinline__ void sn_mma_step(const SnConvArgs& a, int s, int nt0, int lane, const float (&av)[2][8], sn_f32x16 (&acc)[2][NT]) {
-    sn_bf16x8 ahi[2], alo[2], bhi[NT], blo[NT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const __bf16 h = (__bf16)av[mt][j];
-            ahi[mt][j] = h;
-            alo[mt][j] = (__bf16)(av[mt][j] - (float)h);
-        }
-    const int ntiles = a.cout >> 5;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const size_t f = ((size_t)s * ntiles + nt0 + nt) * 64 + lane;
-        bhi[nt] = reinterpret_cast<const sn_bf16x8*>(a.whi)[f];
-        blo[nt] = reinterpret_cast<const sn_bf16x8*>(a.wlo)[f];
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], blo[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-        }
-}
-
 // 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M cells x 32 NT channels: the tiles are numbered with
 // the channel tile fastest, so the waves of a workgroup share their rows where C_out has several tiles, and a map of a few cells
 // still spreads over C_out / (32 NT) waves.  A k-step is 16 channels of one tap (cinp % 16 == 0).
@@ -216,13 +177,8 @@ __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
         const int y = sn_clampi(yq - a.opad, 0, a.Ho - 1), x = sn_clampi(xq - a.opad, 0, a.Wo - 1);
         base[mt] = a.in + sn_field_base(img, y, x, a.sh, a.sw, a.Hp, a.Wp, a.cinp);
     }
-    sn_f32x16 acc[2][NT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.0f;
+    conv_f32x16 acc[2][NT];
+    CONV_ZERO_ACC(acc, NT);
     float av[2][8];
 
     int s = 0;
@@ -230,18 +186,18 @@ __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
         const size_t toff = sn_tap_offset(tap, a.kw, a.Wp, a.cinp) + 8 * h;
         for (int c0 = 0; c0 < a.cinp; c0 += 16, ++s) {
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) sn_load8(base[mt] + toff + c0, av[mt]);
-            sn_mma_step<NT>(a, s, nt0, lane, av, acc);
+            for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
+            conv_mma_step<true, NT>(a.whi, a.wlo, a.cout, s, nt0, lane, av, acc);
         }
     }
 
-    // epilogue: accumulator register i of lane (r, h) is output row (i & 3) + 8 (i >> 2) + 4 h, column r.
+    // epilogue: accumulator register i of lane (r, h) is output row cf_acc_row(i, h), column r.
     // conv + folded bias, then the block's own input, then ReLU (wav_models/conv.py:15-19); 0 in the halo.
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const long long m = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const long long m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= Mq) continue;
             int img, yq, xq;
             sn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
@@ -264,12 +220,6 @@ __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
 }
 
 // ---- tail ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sn_wave_sum(double v) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w, 64);  // a butterfly: every lane ends with the same bits
-    return v;
-}
-
 // one wave per window: lane l owns entries l, l + 64, ... of both vectors
 __global__ __launch_bounds__(64) void syncnet_tail_kernel(const float* __restrict__ audio, const float* __restrict__ face,
                                                           float* __restrict__ audio_emb, float* __restrict__ face_emb, double* __restrict__ cosv) {
@@ -281,7 +231,7 @@ __global__ __launch_bounds__(64) void syncnet_tail_kernel(const float* __restric
         sa += u * u;
         sf += v * v;
     }
-    const double na = fmax(sqrt(sn_wave_sum(sa)), 1e-12), nf = fmax(sqrt(sn_wave_sum(sf)), 1e-12);
+    const double na = fmax(sqrt(conv_wave_sum(sa)), 1e-12), nf = fmax(sqrt(conv_wave_sum(sf)), 1e-12);
     double d = 0.0;
     for (int c = lane; c < SN_EMB; c += 64) {
         const double u = (double)audio[w + c] / na, v = (double)face[w + c] / nf;
@@ -289,7 +239,7 @@ __global__ __launch_bounds__(64) void syncnet_tail_kernel(const float* __restric
         if (face_emb) face_emb[w + c] = (float)v;
         d += u * v;
     }
-    d = sn_wave_sum(d);
+    d = conv_wave_sum(d);
     if (cosv && lane == 0) cosv[blockIdx.x] = d;
 }
 
@@ -333,14 +283,9 @@ extern "C" void n3dt_launch_syncnet_pack(const N3dtSyncnetParams* p, void* packe
     }
 }
 
-static unsigned sn_grid(size_t work) {
-    const size_t blocks = (work + 255) / 256;
-    return (unsigned)(blocks < 65536 ? (blocks ? blocks : 1) : 65536);
-}
-
 extern "C" void n3dt_launch_syncnet_faces(int n, int height, int width, const float* frames, const int* boxes, int box_stride, float* faces,
                                           hipStream_t st) {
-    syncnet_faces_kernel<<<sn_grid((size_t)n * SN_FACE_C * SN_FACE_H * SN_FACE_W), 256, 0, st>>>(n, height, width, frames, boxes, box_stride, faces);
+    syncnet_faces_kernel<<<conv_grid((size_t)n * SN_FACE_C * SN_FACE_H * SN_FACE_W), 256, 0, st>>>(n, height, width, frames, boxes, box_stride, faces);
 }
 
 static void sn_conv(int block, int n, const void* packed, const float* in, float* out, hipStream_t st) {
@@ -369,7 +314,7 @@ static void sn_conv(int block, int n, const void* packed, const float* in, float
 // blocks first .. last on `src` [n, C, H, W]; the last block's output (halo 0) goes to `final`
 static void sn_encoder(int first, int last, int n, const void* packed, const float* src, float* map0, float* map1, float* final, hipStream_t st) {
     const SnGeom g0 = sn_geom(first);
-    syncnet_to_nhwc_kernel<<<sn_grid(sn_in_elems(&g0, n)), 256, 0, st>>>(src, n, SN_TABLE[first].cin, g0.Hi, g0.Wi, g0.ipad, g0.cinp, map0);
+    syncnet_to_nhwc_kernel<<<conv_grid(sn_in_elems(&g0, n)), 256, 0, st>>>(src, n, SN_TABLE[first].cin, g0.Hi, g0.Wi, g0.ipad, g0.cinp, map0);
     float* in = map0;
     float* out = map1;
     for (int b = first; b <= last; ++b) {
@@ -402,7 +347,7 @@ extern "C" void n3dt_launch_syncnet_block(int block, int n, const void* packed, 
     char* ws = (char*)workspace;
     float* map0 = (float*)(ws + w.map[0]);
     float* map1 = (float*)(ws + w.map[1]);
-    syncnet_to_nhwc_kernel<<<sn_grid(sn_in_elems(&g, n)), 256, 0, st>>>(in, n, SN_TABLE[block].cin, g.Hi, g.Wi, g.ipad, g.cinp, map0);
+    syncnet_to_nhwc_kernel<<<conv_grid(sn_in_elems(&g, n)), 256, 0, st>>>(in, n, SN_TABLE[block].cin, g.Hi, g.Wi, g.ipad, g.cinp, map0);
     sn_conv(block, n, packed, map0, map1, st);
-    syncnet_to_nchw_kernel<<<sn_grid((size_t)n * g.cout * g.Ho * g.Wo), 256, 0, st>>>(map1, n, g.cout, g.Ho, g.Wo, g.opad, out);
+    syncnet_to_nchw_kernel<<<conv_grid((size_t)n * g.cout * g.Ho * g.Wo), 256, 0, st>>>(map1, n, g.cout, g.Ho, g.Wo, g.opad, out);
 }

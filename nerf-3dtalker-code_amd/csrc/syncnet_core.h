@@ -4,7 +4,9 @@
  *
  * Included by csrc/syncnet.hip, whose convolution, layout and prologue kernels take their addresses from the functions below, and
  * by tests/syncnet_core_host.cpp, which walks the very same functions over the convolution kernel's grid on the CPU (under the
- * address and undefined-behaviour sanitizers) for all 31 blocks.  Compiles as host C++ on its own; the __host__ __device__
+ * address and undefined-behaviour sanitizers) for all 31 blocks.  The weight pack's fragment arithmetic and the epilogue's
+ * register -> row map are conv_frag.h's, shared with the other convolutions and walked by the same program; the block / wave /
+ * lane / K-step nest of the convolution kernel is re-typed there.  Compiles as host C++ on its own; the __host__ __device__
  * qualifiers exist only under hipcc.
  *
  * Maps.  Every activation is NHWC fp32 with C a multiple of 16 (the two first blocks' 15 and 1 input channels are padded with

@@ -13,7 +13,9 @@
 //
 // Precision.  N3DT_BF16: activations and weights rounded to bf16 at the MFMA operands, fp32 accumulate.  N3DT_F32: every operand
 // split x = hi + lo (two bf16s), three products hi*hi + hi*lo + lo*hi per product (~16 mantissa bits, as nerf_fwd_x16s.hip).
-// Activations are stored fp32 in both modes; the conversion happens while the operand is loaded.
+// Activations are stored fp32 in both modes; the conversion happens while the operand is loaded.  The K step of both modes, the
+// split and the order of its products are conv_mfma.h's, which lpips.hip and syncnet.hip share; the fragment order of the weight
+// pack and the accumulators' rows are conv_frag.h's.
 //
 // Every image of the 2B batch goes through identical code with the same K order and no split-K, so a prediction equal to its
 // target gives bit-identical activations, a loss of exactly 0 and a gradient of exactly 0.
@@ -22,9 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/n3dt.h"
-
-typedef __bf16 vgg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float vgg_f32x16 __attribute__((ext_vector_type(16)));
+#include "conv_mfma.h"
 
 #define VGG_L1_BLOCKS 256
 #define VGG_S 224
@@ -36,11 +36,9 @@ static constexpr int kH[N3DT_VGG_CONVS] = {224, 224, 112, 112, 56, 56, 56, 28, 2
 static constexpr bool kPoolIn[N3DT_VGG_CONVS] = {false, false, true, false, true, false, false, true, false, false};
 static constexpr int kBlockEnd[4] = {1, 3, 6, 9};  // the convs whose ReLU output ends blocks [:4], [4:9], [9:16], [16:23]
 
-static inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // ---- weight pack --------------------------------------------------------------------------------------------------------------
-// One matrix per conv and direction, [Kp/16][Np/32] fragments of 64 lanes x 8 bf16: lane (r = l & 31, h = l >> 5) element j holds
-// B[k = 16 s + 8 h + j][n = 32 t + r], so a wave reads one fragment as one contiguous KiB.
+// One matrix per conv and direction in conv_frag.h's fragment order, [Kp/16][Np/32] fragments of 64 lanes x 8 bf16: element e holds
+// B[k][n] with (k, n) = cf_pack_decode(e), so a wave reads one fragment as one contiguous KiB.
 //   forward: B[tap * C_in + ci][co]  = W[co][ci][ky][kx]                      Kp = rup(9 C_in, 16), Np = C_out
 //   dgrad:   B[tap * C_out + co][ci] = W[co][ci][2 - ky][2 - kx]              Kp = 9 C_out,         Np = rup(C_in, 64)
 // N3DT_F32 stores a lo matrix right behind each hi matrix.  The fp32 biases follow the matrices.
@@ -79,10 +77,8 @@ __global__ __launch_bounds__(256) void vgg_pack_kernel(const float* __restrict__
                                                        __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)kp * np_) return;
-    const int frag = (int)(e / 512), within = (int)(e % 512);
-    const int lane = within >> 3, j = within & 7;
-    const int s = frag / (np_ / 32), t = frag % (np_ / 32);
-    const int k = 16 * s + 8 * (lane >> 5) + j, n = 32 * t + (lane & 31);
+    int k, n;
+    cf_pack_decode(e, np_ / 32, &k, &n);
     float w = 0.0f;
     if (!dgrad) {
         if (k < 9 * cin && n < cout) {
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256) void vgg_pack_kernel(const float* __restrict__
     }
     const __bf16 h = (__bf16)w;
     hi[e] = h;
-    if (split) lo[e] = (__bf16)(w - (float)h);
+    if (split) lo[e] = conv_lo(w, h);
 }
 
 __global__ __launch_bounds__(256) void vgg_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
@@ -115,43 +111,6 @@ struct VggConvArgs {
 };
 
 // MODE 0: C_in % 16 == 0, halo-padded input;  MODE 1: same with the 2x2 max-pool fused into the load;  MODE 2: any C_in (conv1_1)
-template <bool SPLIT>
-__device__ __forceinline__ void vgg_mma_step(const VggConvArgs& a, int s, int nt0, int lane, const float (&av)[2][8], vgg_f32x16 (&acc)[2][2]) {
-    vgg_bf16x8 ahi[2], alo[2], bhi[2], blo[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const __bf16 h = (__bf16)av[mt][j];
-            ahi[mt][j] = h;
-            if (SPLIT) alo[mt][j] = (__bf16)(av[mt][j] - (float)h);
-        }
-    const int ntiles = a.np_ >> 5;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const size_t f = ((size_t)s * ntiles + nt0 + nt) * 64 + lane;
-        bhi[nt] = reinterpret_cast<const vgg_bf16x8*>(a.whi)[f];
-        if (SPLIT) blo[nt] = reinterpret_cast<const vgg_bf16x8*>(a.wlo)[f];
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            if (SPLIT) {
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], blo[nt], acc[mt][nt], 0, 0, 0);
-            }
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[mt], bhi[nt], acc[mt][nt], 0, 0, 0);
-        }
-}
-
-__device__ __forceinline__ void vgg_load8(const float* p, float* v) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    const float4 y = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-}
-
 // 256 threads = 4 waves; a wave computes 64 output pixels x 64 output channels (2 x 2 tiles of 32 x 32), the workgroup 256 pixels
 template <bool SPLIT, int MODE>
 __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
@@ -171,13 +130,8 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
         py[mt] = rem / a.W;
         px[mt] = rem - py[mt] * a.W;
     }
-    vgg_f32x16 acc[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.0f;
+    conv_f32x16 acc[2][2];
+    CONV_ZERO_ACC(acc, 2);
     float av[2][8];
 
     if constexpr (MODE == 0) {
@@ -189,8 +143,8 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
             const int toff = ((tap / 3) * Wp + tap % 3) * a.cin;
             for (int c0 = 0; c0 < a.cin; c0 += 16, ++s) {
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) vgg_load8(base[mt] + toff + c0, av[mt]);
-                vgg_mma_step<SPLIT>(a, s, nt0, lane, av, acc);
+                for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
+                conv_mma_step<SPLIT, 2>(a.whi, a.wlo, a.np_, s, nt0, lane, av, acc);
             }
         }
     } else if constexpr (MODE == 1) {
@@ -211,14 +165,14 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
                     if (ok[mt]) {
                         float q[8];
                         const float* p = src[mt] + c0;
-                        vgg_load8(p, av[mt]);
-                        vgg_load8(p + a.cin, q);
+                        conv_load8(p, av[mt]);
+                        conv_load8(p + a.cin, q);
 #pragma unroll
                         for (int j = 0; j < 8; ++j) av[mt][j] = fmaxf(av[mt][j], q[j]);
-                        vgg_load8(p + (size_t)Wu * a.cin, q);
+                        conv_load8(p + (size_t)Wu * a.cin, q);
 #pragma unroll
                         for (int j = 0; j < 8; ++j) av[mt][j] = fmaxf(av[mt][j], q[j]);
-                        vgg_load8(p + (size_t)Wu * a.cin + a.cin, q);
+                        conv_load8(p + (size_t)Wu * a.cin + a.cin, q);
 #pragma unroll
                         for (int j = 0; j < 8; ++j) av[mt][j] = fmaxf(av[mt][j], q[j]);
                     } else {
@@ -226,7 +180,7 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
                         for (int j = 0; j < 8; ++j) av[mt][j] = 0.0f;
                     }
                 }
-                vgg_mma_step<SPLIT>(a, s, nt0, lane, av, acc);
+                conv_mma_step<SPLIT, 2>(a.whi, a.wlo, a.np_, s, nt0, lane, av, acc);
             }
         }
     } else {
@@ -246,16 +200,16 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VggConvArgs a) {
                     av[mt][j] = v;
                 }
             }
-            vgg_mma_step<SPLIT>(a, s, nt0, lane, av, acc);
+            conv_mma_step<SPLIT, 2>(a.whi, a.wlo, a.np_, s, nt0, lane, av, acc);
         }
     }
 
-    // epilogue: accumulator register i of lane (r, h) is output row (i & 3) + 8 (i >> 2) + 4 h, column r
+    // epilogue: accumulator register i of lane (r, h) is output row cf_acc_row(i, h), column r
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int m = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= M) continue;
             const int n = m / HW, rem = m - n * HW, y = rem / a.W, x = rem - y * a.W;
             const size_t pix = a.out_pad ? (size_t)(n * (a.H + 2) + y + 1) * Wp + x + 1 : (size_t)(n * a.H + y) * a.W + x;

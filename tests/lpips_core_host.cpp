@@ -1,20 +1,25 @@
 // csrc/lpips_core.h -- the index arithmetic the LPIPS kernels (csrc/lpips.hip) are compiled from -- walked on the CPU over the
 // kernels' full grids: every workgroup, wave, lane and K step of the five implicit-GEMM convolutions (rows past M included), the
-// epilogue's stores, both pools, the halo kernel's cells and the prologue's reinterpretation.  Every buffer is a std::vector of
+// epilogue's stores, both pools, the halo kernel's cells, the prologue's reinterpretation and the weight pack of every layer
+// against the addresses the MFMA step reads it at.  Every buffer is a std::vector of
 // exactly the size the workspace gives it and holds, per element, the LOGICAL coordinate it stands for, so an index that leaves
 // its buffer ends the program through the address sanitizer and an index that stays inside but names the wrong element fails a
 // check.
 //
-// The loop nests below (block / wave / lane / K step, the epilogue's register -> row map, the pool's and the halo kernel's element
-// decodes) are RE-TYPED from lpips_conv_kernel, lpips_pool_kernel and lpips_halo_kernel in csrc/lpips.hip; only the lp_* functions
-// are shared.  A change to one of those loops there must be made here too, or this program checks a kernel that no longer exists.
-// Not walked: the flat element decodes of the prologue's output, the distance kernel and the pack kernel.
+// The loop nests below (block / wave / lane / K step, the pool's and the halo kernel's element decodes, the pack kernel's weight
+// lookup) are RE-TYPED from lpips_conv_kernel, lpips_pool_kernel, lpips_halo_kernel and lpips_pack_kernel in csrc/lpips.hip.  A
+// change to one of those loops there must be made here too, or this program checks a kernel that no longer exists.  NOT re-typed,
+// but the very functions the kernels are compiled from: the lp_* functions of lpips_core.h, and from csrc/conv_frag.h the
+// epilogue's register -> row map (cf_acc_row), the pack kernel's element decode (cf_pack_decode) and the address the MFMA step
+// reads its weight fragments at (cf_frag_group / cf_frag_elem).
+// Not walked: the flat element decodes of the prologue's output and of the distance kernel.
 //
 // usage: lpips_core_host B H W [B H W ...]; prints one line per shape: B H W fh1 fw1 ... fh5 fw5 reads
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
+#include "../nerf-3dtalker-code_amd/csrc/conv_frag.h"
 #include "../nerf-3dtalker-code_amd/csrc/lpips_core.h"
 
 struct Cell {
@@ -102,10 +107,10 @@ static void walk_conv(int l, int n, int Hi, int Wi, const std::vector<Cell>& in,
                         CHECK(s * 16 == kp, "layer %d: %d K steps, the pack has %d", l, s, kp / 16);
                     }
                 }
-                // epilogue: register i of lane (r, h) is row (i & 3) + 8 (i >> 2) + 4 h
+                // epilogue: register i of lane (r, h) is row cf_acc_row(i, h)
                 for (int mt = 0; mt < 2; ++mt)
                     for (int i = 0; i < 16; ++i) {
-                        const long long m = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                        const long long m = m0 + mt * 32 + cf_acc_row(i, h);
                         if (m >= M) continue;
                         int img, y, x;
                         lp_row_pixel(m, M, Ho, Wo, &img, &y, &x);
@@ -118,6 +123,53 @@ static void walk_conv(int l, int n, int Hi, int Wi, const std::vector<Cell>& in,
     const std::vector<Cell> lab = labelled(n, Ho, Wo, out_pad, cout);
     CHECK(lab.size() == out.size(), "layer %d: output size", l);
     for (size_t e = 0; e < out.size(); ++e) CHECK(out[e] == (lab[e].y >= 0 ? 1 : 0), "layer %d: element %zu stored %d times", l, e, out[e]);
+}
+
+// lpips_pack_kernel for layer l -- one thread per element e of the packed matrix -- and then every weight read of the MFMA step
+// over the convolution's grid.y.  packed[e] stands for what the kernel stores at e: 1 + the index of W[n][ci][ky][kx], or 0 where
+// it stores zero.  The decode must hit every (k, n) once and use every weight once; the reader must stay inside the matrix, take
+// every element once, and find at the address of (K step s, tile, lane, j) the weight of the k its A operand holds there and of
+// the column the epilogue stores that tile's lane to: zero for the rows k >= K, which conv1's gather feeds 0.
+static void walk_pack(int l) {
+    const int cin = lp_cin(l), cout = lp_cout(l), ks = lp_ksize(l), K = lp_k(l), kp = lp_kp(l), ntiles = cout / 32;
+    CHECK(kp % 16 == 0 && cout % LP_TILE_N == 0 && kp >= K, "layer %d: pack divisibility", l);
+    const size_t elems = (size_t)kp * cout, weights = (size_t)cout * K;
+    std::vector<size_t> packed(elems, 0);
+    std::vector<int> decoded(elems, 0), used(weights, 0), read(elems, 0);
+    for (size_t e = 0; e < elems; ++e) {
+        int k, n;
+        cf_pack_decode(e, ntiles, &k, &n);
+        CHECK(k >= 0 && k < kp && n >= 0 && n < cout, "layer %d: element %zu decodes to (%d, %d)", l, e, k, n);
+        ++decoded[(size_t)k * cout + n];
+        if (k < ks * ks * cin) {
+            const int tap = k / cin, ci = k - tap * cin;
+            const size_t w = ((size_t)n * cin + ci) * (ks * ks) + tap;
+            CHECK(w < weights, "layer %d: element %zu reads weight %zu of %zu", l, e, w, weights);
+            ++used[w];
+            packed[e] = 1 + w;
+        }
+    }
+    for (size_t i = 0; i < elems; ++i) CHECK(decoded[i] == 1, "layer %d: (k, n) = (%zu, %zu) packed %d times", l, i / cout, i % cout, decoded[i]);
+    for (size_t w = 0; w < weights; ++w) CHECK(used[w] == 1, "layer %d: weight %zu packed %d times", l, w, used[w]);
+    for (int by = 0; by < cout / LP_TILE_N; ++by)  // grid.y of the convolution; nt0 = 2 blockIdx.y
+        for (int s = 0; s < kp / 16; ++s)
+            for (int nt = 0; nt < 2; ++nt)
+                for (int lane = 0; lane < 64; ++lane) {
+                    CHECK(cf_frag_elem(s, ntiles, by * 2, nt, lane, 0) == 8 * cf_frag_group(s, ntiles, by * 2, nt, lane), "layer %d: group", l);
+                    for (int j = 0; j < 8; ++j) {  // one 16-byte load of 8 bf16
+                        const size_t e = cf_frag_elem(s, ntiles, by * 2, nt, lane, j);
+                        CHECK(e < elems, "layer %d: the step reads element %zu of %zu", l, e, elems);
+                        ++read[e];
+                        const int k = 16 * s + 8 * (lane >> 5) + j;           // what the A operand holds in this position
+                        const int n = (by * 2 + nt) * 32 + (lane & 31);       // the epilogue's co
+                        int dk, dn;
+                        cf_pack_decode(e, ntiles, &dk, &dn);
+                        CHECK(dk == k && dn == n, "layer %d: the step reads (%d, %d) where the pack put (%d, %d)", l, k, n, dk, dn);
+                        const size_t want = k < K ? 1 + ((size_t)n * cin + k % cin) * (ks * ks) + k / cin : 0;
+                        CHECK(packed[e] == want, "layer %d: (k, n) = (%d, %d) holds %zu, expected %zu", l, k, n, packed[e], want);
+                    }
+                }
+    for (size_t e = 0; e < elems; ++e) CHECK(read[e] == 1, "layer %d: element %zu read %d times", l, e, read[e]);
 }
 
 static void walk_pool(int n, int Hi, int Wi, int C, int Ho, int Wo, size_t in_elems, size_t out_elems, int pad) {
@@ -186,6 +238,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "usage: %s B H W [B H W ...]\n", argv[0]);
         return 1;
     }
+    for (int l = 0; l < LP_LAYERS; ++l) walk_pack(l);
     for (int a = 1; a + 2 < argc; a += 3) {
         const int B = atoi(argv[a]), H = atoi(argv[a + 1]), W = atoi(argv[a + 2]);
         CHECK(B >= 1 && B <= LP_MAX_BATCH && H >= LP_MIN_HW && W >= LP_MIN_HW && H <= LP_MAX_HW && W <= LP_MAX_HW, "shape outside the limits");

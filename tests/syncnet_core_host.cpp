@@ -1,6 +1,9 @@
 // The index arithmetic of csrc/syncnet_core.h walked on the CPU over the grid of csrc/syncnet.hip's convolution kernel, for all 31
-// blocks and the window counts given on the command line (default 1 2 3).  The loop nest below is RE-TYPED from
-// syncnet_conv_kernel (block / wave / lane / K step, the epilogue's register -> row map): a change there must be made here too.
+// blocks and the window counts given on the command line (default 1 2 3), and the weight pack of every block against the addresses
+// the MFMA step reads it at.  The loop nest below is RE-TYPED from syncnet_conv_kernel (block / wave / lane / K step), and so is
+// syncnet_pack_kernel's weight lookup: a change there must be made here too.  NOT re-typed, but the very functions the kernels are
+// compiled from: syncnet_core.h's, and from csrc/conv_frag.h the epilogue's register -> row map (cf_acc_row), the pack kernel's
+// element decode (cf_pack_decode) and the address of the step's weight fragments (cf_frag_group / cf_frag_elem).
 // Built by tests/test_syncnet_cpu.py with the host compiler under -fsanitize=address,undefined: the maps are heap blocks of exactly
 // the size the library allocates, so a read or a store outside one ends the program through the sanitizer; a read of the wrong
 // element, a cell stored twice or never, a K step too many or too few fails the program's own check (exit code 1).
@@ -10,6 +13,7 @@
 
 #include <vector>
 
+#include "../nerf-3dtalker-code_amd/csrc/conv_frag.h"
 #include "../nerf-3dtalker-code_amd/csrc/syncnet_core.h"
 
 static int g_fail = 0;
@@ -73,7 +77,7 @@ static void walk_conv(int b, int n, int NT, bool print) {
                             reads += 8;
                         }
                         for (int nt = 0; nt < NT; ++nt) {
-                            const size_t f = ((size_t)s * (g.cout >> 5) + nt0 + nt) * 64 + lane;
+                            const size_t f = cf_frag_group(s, g.cout >> 5, nt0, nt, lane);
                             CHECK(f < frags, "block %d: weight fragment %zu of %zu", b, f, frags);
                         }
                     }
@@ -81,7 +85,7 @@ static void walk_conv(int b, int n, int NT, bool print) {
                 CHECK(s == g.K / 16, "block %d: %d K steps, expected %d", b, s, g.K / 16);
                 for (int mt = 0; mt < 2; ++mt)
                     for (int i = 0; i < 16; ++i) {
-                        const long long m = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                        const long long m = m0 + mt * 32 + cf_acc_row(i, h);
                         if (m >= Mq) continue;
                         int img, yq, xq;
                         sn_row_cell(m, Mq, g.Hq, g.Wq, &img, &yq, &xq);
@@ -118,6 +122,64 @@ static void walk_conv(int b, int n, int NT, bool print) {
     delete[] stored;
 }
 
+// syncnet_pack_kernel for block b -- one thread per element e of the packed matrix -- and then every weight read of the MFMA step
+// over the column tiles of syncnet_conv_kernel<NT>.  packed[e] stands for what the kernel stores at e: 1 + the index of
+// w[n][ci][ky][kx], or 0 where it stores zero.  The decode must hit every (k, n) once and use every weight once; the reader must
+// stay inside the matrix, take every element once, and find at the address of (K step s, tile, lane, j) the weight of the k its A
+// operand holds there and of the column the epilogue stores that tile's lane to: zero for the padded channels ci >= C_in, where
+// the layout kernel wrote zero activations.
+static void walk_pack(int b, int NT) {
+    const SnGeom g = sn_geom(b);
+    const int cin = SN_TABLE[b].cin, taps = g.kh * g.kw, ntiles = g.cout / 32, ntn = g.cout / (32 * NT);
+    const size_t elems = (size_t)g.K * g.cout, weights = (size_t)g.cout * cin * taps;
+    std::vector<size_t> packed(elems, 0);
+    std::vector<int> decoded(elems, 0), used(weights, 0), read(elems, 0);
+    for (size_t e = 0; e < elems; ++e) {
+        int k, n;
+        cf_pack_decode(e, ntiles, &k, &n);
+        CHECK(k >= 0 && k < g.K && n >= 0 && n < g.cout, "block %d: element %zu decodes to (%d, %d)", b, e, k, n);
+        if (k < 0 || k >= g.K || n < 0 || n >= g.cout) continue;
+        ++decoded[(size_t)k * g.cout + n];
+        const int tap = k / g.cinp, ci = k - tap * g.cinp;
+        if (ci < cin) {
+            const size_t w = ((size_t)n * cin + ci) * taps + tap;
+            CHECK(w < weights, "block %d: element %zu reads weight %zu of %zu", b, e, w, weights);
+            if (w >= weights) continue;
+            ++used[w];
+            packed[e] = 1 + w;
+        }
+    }
+    size_t bad = 0;
+    for (size_t i = 0; i < elems; ++i) bad += decoded[i] != 1;
+    CHECK(bad == 0, "block %d: %zu of %zu (k, n) not packed exactly once", b, bad, elems);
+    bad = 0;
+    for (size_t w = 0; w < weights; ++w) bad += used[w] != 1;
+    CHECK(bad == 0, "block %d: %zu of %zu weights not packed exactly once", b, bad, weights);
+    for (int tn = 0; tn < ntn; ++tn)  // nt0 = (tile % ntn) * NT
+        for (int s = 0; s < g.K / 16; ++s)
+            for (int nt = 0; nt < NT; ++nt)
+                for (int lane = 0; lane < 64; ++lane) {
+                    CHECK(cf_frag_elem(s, ntiles, tn * NT, nt, lane, 0) == 8 * cf_frag_group(s, ntiles, tn * NT, nt, lane), "block %d: group", b);
+                    for (int j = 0; j < 8; ++j) {  // one 16-byte load of 8 bf16
+                        const size_t e = cf_frag_elem(s, ntiles, tn * NT, nt, lane, j);
+                        CHECK(e < elems, "block %d: the step reads element %zu of %zu", b, e, elems);
+                        if (e >= elems) continue;
+                        ++read[e];
+                        const int k = 16 * s + 8 * (lane >> 5) + j;           // what the A operand holds in this position
+                        const int n = (tn * NT + nt) * 32 + (lane & 31);      // the epilogue's co
+                        int dk, dn;
+                        cf_pack_decode(e, ntiles, &dk, &dn);
+                        CHECK(dk == k && dn == n, "block %d: the step reads (%d, %d) where the pack put (%d, %d)", b, k, n, dk, dn);
+                        const int tap = k / g.cinp, ci = k % g.cinp;
+                        const size_t want = ci < cin ? 1 + ((size_t)n * cin + ci) * taps + tap : 0;
+                        CHECK(packed[e] == want, "block %d: (k, n) = (%d, %d) holds %zu, expected %zu", b, k, n, packed[e], want);
+                    }
+                }
+    bad = 0;
+    for (size_t e = 0; e < elems; ++e) bad += read[e] != 1;
+    CHECK(bad == 0, "block %d, NT %d: %zu of %zu packed elements not read exactly once", b, NT, bad, elems);
+}
+
 // the prologue's addresses: every element of one face window of an H x W frame under `box`
 static void walk_faces(int H, int W, int b0, int b1, int b2, int b3) {
     float* frame = new float[(size_t)H * W];
@@ -150,6 +212,8 @@ int main(int argc, char** argv) {
         const SnGeom g = sn_geom(b);
         CHECK(g.K % 16 == 0 && g.cinp % 16 == 0 && g.cout % 32 == 0, "block %d: K %d, cinp %d, cout %d", b, g.K, g.cinp, g.cout);
         CHECK(sn_in_elems(&g, 1) <= sn_max_map_elems() && sn_out_elems(&g, 1) <= sn_max_map_elems(), "block %d exceeds the largest map", b);
+        walk_pack(b, 1);
+        if (g.cout % 64 == 0) walk_pack(b, 2);
         if (b == SN_FACE_BLOCKS - 1 || b == SN_BLOCKS - 1) {
             CHECK(g.Ho == 1 && g.Wo == 1 && g.opad == 0 && g.cout == SN_EMB, "block %d does not end in a 512-vector", b);
         } else {

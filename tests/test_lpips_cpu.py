@@ -255,8 +255,10 @@ def test_index_walk_on_the_host_under_sanitizers(tmp_path):
     """csrc/lpips_core.h -- the functions the convolution, pool and halo kernels and the prologue's gather take their addresses
     from -- over those kernels' full grids on the CPU, for every shape and batch size of the GPU test: the smallest legal input
     (every late map 1x1, M < 64), non-square sizes whose conv1 and pool floors drop rows, B = 1 and 3, and 256^2 and 512^2.  The
-    program re-types the kernels' loop nests (its header says so); the prologue's output decode, the distance kernel and the
-    pack kernel are not walked.  A read outside a buffer ends the program through the sanitizer; a read of the wrong
+    program re-types the kernels' loop nests (its header says so) but takes the epilogue's row map, the pack kernel's decode and
+    the MFMA step's weight address from csrc/conv_frag.h as the kernels do, and walks the pack of every layer: every (k, n) packed
+    once, the decode the inverse of the address read, the rows k >= K zero.  The prologue's output decode and the distance
+    kernel are not walked.  A read outside a buffer ends the program through the sanitizer; a read of the wrong
     element fails the program's own check.  Where the compiler has no sanitizer runtimes the indices are still checked, on an
     unsanitised build, and only the sanitizer claim is skipped."""
     found = _host_compiler(tmp_path)

@@ -310,9 +310,11 @@ def test_index_walk_on_the_host_under_sanitizers(tmp_path):
     """csrc/syncnet_core.h -- the functions the convolution kernel takes its rows, halo cells, taps, residual reads and stores from,
     and the prologue its source pixels -- over the kernel's full grid on the CPU, all 31 blocks, n = 1, 2, 3 (n = 1: M = 1 in the
     1x1 blocks and 9 in the 3x3 ones), both instantiations of the kernel.  The program re-types the kernel's loop nest (its header
-    says so).  A read outside a buffer ends the program through the sanitizer; a read of the wrong element, or an output element
-    stored twice or never, fails the program's own check.  Where the compiler has no sanitizer runtimes the indices are still
-    checked, on an unsanitised build, and only the sanitizer claim is skipped."""
+    says so) but takes the epilogue's row map, the pack kernel's decode and the MFMA step's weight address from csrc/conv_frag.h
+    as the kernels do, and walks the pack of every block: every (k, n) packed once, the decode the inverse of the address read,
+    the padded channels' rows zero.  A read outside a buffer ends the program through the sanitizer; a read of the wrong
+    element, or an output element stored twice or never, fails the program's own check.  Where the compiler has no sanitizer
+    runtimes the indices are still checked, on an unsanitised build, and only the sanitizer claim is skipped."""
     from n3dt.syncnet import block_shapes
     found = _host_compiler(tmp_path)
     if found is None:
