@@ -1,6 +1,8 @@
 """Stage-by-stage float64 restatement of the 2-D neural renderer's training step, for the tests that pin
 csrc/train_nr.hip, the save epilogue of neural_render_x16.inc / nr_fused_x16.inc and nr_train16.h
 (test_nr_restatement_cpu.py, test_gpu_nr_stagewise.py).  A helper module, not a test file: CPU only, numpy.
+The last section restates the 16-bit INFERENCE renderer (run_x16), forward only, in bf16 and IEEE half, for
+test_gpu_nr_infer_stagewise.py.
 
 What is restated (reference: NetWorks/neural_renderer.py:72-91, PixelShuffleUpsample.py:36-45, Blur with the filter2d
 semantics of DESIGN section 4: cross-correlation with [1 2 1]^2 / 16 on a reflect border):
@@ -94,6 +96,12 @@ NR_F32_FLOOR = {
 }
 NR_F32_IMAGE_FLOOR = 1.3e-7      # |img32 - img64| of the free float32 forward (absolute: a sigmoid output)
 NR_F32_STAGE_FLOOR = 3.1e-7      # lrelu stages of the free float32 forward: |a32 - a64| / (|b| + sum |w x|), every stage of every case
+# the fp32 stages of the 16-bit INFERENCE renderer (the last section of this module): the float32 emulation in two accumulation
+# orders (16-wide k-steps in sequence, rows of the stencils first; torch.matmul, columns first) against float64 over every INFER_CASES entry in both formats.  The CPU test
+# re-measures them and fails unless measured <= floor < 2 x measured.  GPU bounds are MARGIN x the floor.
+NR_X16_RGB0_FLOOR = 3.7e-7          # |rgb0_32 - rgb0_64| / (|b| + sum |w x|); measured 2.67e-7
+NR_X16_RGB_FLOOR = 3.1e-7           # pre-sigmoid pyramid value of a level from FIXED 16-bit activations: / (|b| + sum |w net| + up |lo|); measured 2.22e-7
+NR_X16_SIGMOID_FLOOR = 1.3e-7       # |sigmoid32(z) - sigmoid64(z)| at the same float32 z (absolute: a value in (0, 1)); measured 9.43e-8
 BF16_FLOOR_ORDERS, BF16_FLOOR_SEEDS = 3, 4   # the bf16 floor of a geometry is the maximum over 3 float32 orders x 4 seeds (the case's and
 #                               the next three): the figure is the size of the few rounding flips an order causes, a handful of events whose
 #                               largest varies several-fold from one draw of the inputs to the next (and hardly between orders on one draw)
@@ -258,8 +266,17 @@ def sep(A, x, rows_first=True):
     return np.einsum("ih,nhjc->nijc", A, np.einsum("jw,nhwc->nhjc", A, x))
 
 
+def blur_taps(x):
+    """the blur by its three taps per axis on a reflect border: the same operator without the dense matrices, for large maps"""
+    def along(a, axis):
+        a = np.moveaxis(a, axis, 0)
+        p = np.concatenate([a[1:2], a, a[-2:-1]])
+        return np.moveaxis(0.25 * p[:-2] + 0.5 * p[1:-1] + 0.25 * p[2:], 0, axis)
+    return along(along(x, 1), 2)
+
+
 def blur(x):
-    return sep(blur_matrix(x.shape[1]), x)
+    return blur_taps(x) if x.shape[1] > 64 else sep(blur_matrix(x.shape[1]), x)
 
 
 def blur_adj(d, fault=None, rows_first=True):
@@ -791,3 +808,375 @@ def emulate_fused(x, P, mm=mm32_seq16):
         xin = net
     sm.img = image_from_nets(np.asarray(x, dtype=np.float64), sm.net, P).astype(np.float32).astype(np.float64)
     return sm
+
+
+# =============================================================================================
+# The 16-bit INFERENCE renderer (run_x16, neural_render_x16.inc:562-670), forward only, in both map types ("bf16", "fp16" = IEEE
+# half): test_gpu_nr_infer_stagewise.py pins it stage by stage from what a call leaves in a caller-owned workspace, the CPU
+# test holds the rules to a float32-ordered emulation and to five deliberate faults.
+#
+# A call over the first k blocks (geometry (fs, C, k, nb)) leaves, in the workspace: hid of block k - 1 as four sub-pixel planes,
+# the stored input map of block k - 1 (net[k - 2]; the caller's feature map for k = 1), net[k - 3] in the other ping-pong
+# buffer, the fp32 pyramid planes levels k - 1 and k - 2 read, and returns img.  The last level's net is never stored
+# (launch_blur_q gets net == nullptr, :650); t1 and y never leave registers (nr_fused_x16.inc:10-11).  So block k - 1 is pinned
+# from the k-block run; net[i] (stored by the (i + 2)-block run) is checked from hid[i] as read after the (i + 1)-block run.
+#
+#   rgb0          fp32, to_rgb16_kernel on the fp32 map with the fp32 weights (neural_render.hip:146-181): per entry within
+#                 MARGIN x NR_X16_RGB0_FLOOR x (|b| + sum |w x|)
+#   hid[k - 1]    a chain of three roundings from the block's stored input (x16_hid_chain): the interval rule of check16 with
+#                 delta_hid, a per-entry tolerance; the median of delta_hid / magnitude over a stage must stay <= HID_MEDIAN_CAP
+#   net[i]        one stage from the stored hid[i]: the bit rule (check16, delta = U (Blur |hid| + |b|), the LeakyReLU) with the
+#                 caps of the format (xs.CAPS)
+#   pyramid plane / img   fp32, from the stored hid, the stored plane the level read, feat_b and to_rgb_{i + 1} (x16_rgb_stage)
+# =============================================================================================
+INFER_CASES = dict(GPU_CASES)       # every entry runs the latency form of the block kernel (M <= 768 pixels, nr_fused_x16.inc:397)
+INFER_CASES.update({
+    (64, 256, 1, 5): 0,             # M = 20 480: the throughput kernel at C = 256 with fp32 input; last level K = 128: blur_mfma_q_kernel<., false>
+    (48, 256, 3, 2): 0,             # M = 4 608 (latency form), 18 432, 73 728: the throughput kernel at C = 128 and 64 on 16-bit input;
+    #                                 blur_mfma_last_kernel at H = 192; blur_mfma_q_kernel<., true> at K = 128 and 64
+    (65, 256, 1, 4): 0,             # M = 16 900 = 528 x 32 + 4: a ragged last tile and a partial workgroup; the odd side: blur_act_rgb_q_kernel
+})
+LARGE_INFER_CASES = ((64, 256, 1, 5), (48, 256, 3, 2), (65, 256, 1, 4))
+TRAIN_TWIN_CASES = ((64, 256, 1, 5), (48, 256, 3, 2))      # the SAVE throughput kernels: the training forward's one-stage bit rule
+FORM_CASES = ((4, 256, 4, 1), (48, 256, 3, 2))             # the last level (K = 32, H = 32 / 192) in all three blur forms
+IN16_CASE = (64, 256, 1, 5)
+FORMATS16 = ("bf16", "fp16")
+HID_MEDIAN_CAP = 5e-4               # median of delta_hid / magnitude over a stage, either format (measured on the CPU emulation: <= 2.2e-4
+#                                     in bf16, <= 1.8e-4 in IEEE half)
+# (the floors of this section's fp32 stages -- NR_X16_RGB0_FLOOR, NR_X16_RGB_FLOOR, NR_X16_SIGMOID_FLOOR -- stand with the other floors at the top)
+
+
+def al128(n):  # neural_render_x16.inc:576
+    return (n + 127) & ~127
+
+
+def nrf_packed_bytes(C, CO):
+    """nrf_dims / nrf_packed_bytes (nr_fused_x16.inc:31-49): the piece stream of a block padded to whole chunks of 24 pieces of
+    1 KiB (x16_core.h:19-20), then its 6 C fp32 biases"""
+    kxq = C // 64 if C >= 128 else C // 16
+    s1, s2, s3 = (2 * C // 32) * (C // 16), (C // 32) * (C // 8), (CO // 32) * (C // 16 + kxq)
+    total = s1 + 4 * (s2 + s3)
+    return (total + 23) // 24 * 24 * 1024 + 6 * C * 4
+
+
+def infer_ws_layout(case):
+    """The workspace of a 16-bit render over case = (fs, C, blocks, maps), BYTE offsets.  run_x16 (neural_render_x16.inc:567-586)
+    carves t1 | ps | hid | netA | netB in 16-bit elements, each rounded up to 128 elements, then planar fp32 rgbA | rgbB; the packed
+    block weights sit at the tail of what n3dt_neural_render_workspace_bytes returns, which is the fp32 renderer's carve (nr_carve,
+    neural_render.hip:236-251: t1 + ps + bl + 2 net + 2 rgb FLOATS) plus nrf_pack_floats (neural_render_x16.inc:545-552: every
+    block's stream rounded up to 256 bytes).  "pack": (offset, bytes) of each block's stream."""
+    fs, C, n, nb = case
+    e_t1 = e_ps = e_hid = 0
+    for i in range(n):
+        h = fs << i
+        M, ci, co = nb * h * h, nr_ch(C, i), nr_ch(C, i + 1)
+        e_t1, e_ps, e_hid = max(e_t1, M * 2 * ci), max(e_ps, 4 * M * ci), max(e_hid, 4 * M * co)
+    L, o = {}, 0
+    for name, e in (("t1", e_t1), ("ps", e_ps), ("hid", e_hid), ("netA", e_hid), ("netB", e_hid)):
+        L[name] = 2 * o
+        o += al128(e)
+    P = fs << n
+    plane = nb * 3 * P * P
+    L["rgbA"], L["rgbB"], L["end"] = 2 * o, 2 * o + 4 * plane, 2 * o + 8 * plane
+    sizes = [nrf_packed_bytes(nr_ch(C, i), nr_ch(C, i + 1)) for i in range(n)]
+    pack = sum(al256(s) for s in sizes)
+    L["total"] = 4 * (e_t1 + 2 * e_ps + 2 * e_hid + 2 * plane) + pack
+    L["packw"] = L["total"] - pack
+    L["pack"], o = [], L["packw"]
+    for s in sizes:
+        L["pack"].append((o, s))
+        o += al256(s)
+    return L
+
+
+def infer_written(case, in16=False):
+    """[(offset, bytes)] of everything a call over case's blocks writes into its workspace (the fused path: every block of a
+    256-channel renderer is nrf_supported): hid by every block; net[i] of a non-last level into netA (i even) / netB (i odd) (:615-616,
+    :650, :664-668); the level-0 projection into rgbB unless the caller brings rgb0 (:598-607); level i < n - 1 writes its pyramid
+    plane into rgbA (i even) / rgbB (i odd) (:611-612, :651-654); the packed streams.  t1 and ps are the layered fallback's."""
+    fs, C, n, nb = case
+    L = infer_ws_layout(case)
+    size = {"hid": 0, "netA": 0, "netB": 0, "rgbA": 0, "rgbB": 0 if in16 else 4 * nb * 3 * fs * fs}
+    for i in range(n):
+        h = fs << i
+        M, co = nb * h * h, nr_ch(C, i + 1)
+        size["hid"] = max(size["hid"], 2 * 4 * M * co)
+        if i < n - 1:
+            k = "netA" if i % 2 == 0 else "netB"
+            size[k] = max(size[k], 2 * 4 * M * co)
+            k = "rgbA" if i % 2 == 0 else "rgbB"
+            size[k] = max(size[k], 4 * nb * 3 * 4 * h * h)
+    return [(L[k], s) for k, s in size.items() if s] + list(L["pack"])
+
+
+class InferWs:
+    """What a call over case = (fs, C, k, nb) left in its workspace (see the section header), decoded: hid_bits [nb, 2h, 2h, co]
+    (raster, h = fs << (k - 1)); lo [nb, h, h, 3] float64, the fp32 plane level k - 1 read; for k >= 2 net_bits (the stored input
+    of block k - 1, net[k - 2]) and lo_prev (the plane level k - 2 read); for k >= 3 net_prev_bits (net[k - 3]).
+    buf: the workspace as uint8; rgb0: the caller's plane [nb, 3, fs * fs] of the 16-bit-input form (it is never copied)."""
+
+    def __init__(self, buf, case, rgb0=None):
+        fs, C, k, nb = case
+        L = infer_ws_layout(case)
+        u16 = lambda off, cnt: buf[off:off + 2 * cnt].view(np.uint16)  # noqa: E731
+
+        def plane(level):   # the plane level `level` reads: rgbB / rgbA alternate (:611-612, :652-654); level 0 may read the caller's
+            h = fs << level
+            if level == 0 and rgb0 is not None:
+                a = np.asarray(rgb0, dtype=np.float32).reshape(-1)
+            else:
+                off = L["rgbB"] if level % 2 == 0 else L["rgbA"]
+                a = buf[off:off + 4 * nb * 3 * h * h].view(np.float32)
+            return np.ascontiguousarray(a.reshape(nb, 3, h, h).transpose(0, 2, 3, 1)).astype(np.float64)
+
+        def net(i):
+            h = fs << (i + 1)
+            return u16(L["netA"] if i % 2 == 0 else L["netB"], nb * h * h * nr_ch(C, i + 1)).reshape(nb, h, h, nr_ch(C, i + 1)).copy()
+        h, co = fs << (k - 1), nr_ch(C, k)
+        raw = u16(L["hid"], 4 * nb * h * h * co).reshape(2, 2, nb, h, h, co)
+        self.hid_bits = np.ascontiguousarray(raw.transpose(2, 3, 0, 4, 1, 5)).reshape(nb, 2 * h, 2 * h, co)   # planes -> raster
+        self.lo = plane(k - 1)
+        self.net_bits = net(k - 2) if k >= 2 else None
+        self.lo_prev = plane(k - 2) if k >= 2 else None
+        self.net_prev_bits = net(k - 3) if k >= 3 else None
+
+
+def rne(fmt):
+    return lambda a: xs.round16(a, fmt)
+
+
+def trunc16(z, fmt):
+    """round toward zero: the fault "net rounded by truncation" """
+    p, emin = xs.FORMATS[fmt]
+    z = np.asarray(z, dtype=np.float64)
+    _, e = np.frexp(np.abs(z))
+    ulp = np.ldexp(1.0, np.maximum(e, emin + 1) - p)
+    return np.copysign(np.floor(np.abs(z) / ulp) * ulp, z)
+
+
+def hi_lo16(b, fmt):
+    hi, lo = xs.split_hi_lo(b, fmt)
+    return hi + lo
+
+
+class X16Block:
+    """The parameters of block i as the fused block kernel sees them: the pack kernel rounds W1, W2, Wf and the fp32 sums R_q to the
+    map type, one conversion each (nr_fused_x16.inc:77-104); b1 and b2 enter through one MFMA as hi + lo halves (:203-206,
+    x16_core.h:67-69, :100-102)."""
+
+    def __init__(self, P, i, fmt):
+        r = rne(fmt)
+        self.W1, self.W2, self.Wf = r(P.w1[i]), r(P.w2[i]), r(P.wf[i])
+        self.R = [r(residual_matrix(P.wf[i], q, f32=True)) for q in range(4)]
+        self.b1, self.b2 = hi_lo16(P.b1[i], fmt), hi_lo16(P.b2[i], fmt)
+
+
+def lin(a, W):
+    return (a.reshape(-1, a.shape[-1]) @ np.ascontiguousarray(W.T)).reshape(a.shape[:-1] + (W.shape[0],))
+
+
+def round_slack(z, delta, nominal, fmt):
+    """per entry: the distance from `nominal` = rne16(lrelu(z)) to the farther of rne16(lrelu(z -+ delta))"""
+    r = rne(fmt)
+    return np.maximum(np.abs(r(lrelu64(z - delta)) - nominal), np.abs(r(lrelu64(z + delta)) - nominal))
+
+
+def x16_hid_chain(xin, P, i, fmt):
+    """hid of block i from the block's STORED input: t1 and y stay in registers, so this is a chain of three roundings.
+    Nominal t1 = rne16(lrelu(z1)); its per-entry slack s1 is the distance to the farther of rne16(lrelu(z1 -+ delta1)), delta1 = U mag1;
+    delta_y = U mag_y + s1 |W2q|^T; in the same way delta_hid = U mag_hid + shuffle(s_y) |Wfq|^T.  Returns (z_hid, mag_hid, delta_hid) in
+    raster order [nb, 2h, 2w, CO]."""
+    w, r, U = X16Block(P, i, fmt), rne(fmt), xs.U
+    xq = r(np.asarray(xin, dtype=np.float64))    # the fp32-input kernel rounds the map once (:307-314); a 16-bit map is unchanged
+    ax = np.abs(xq)
+    z1 = lin(xq, w.W1) + w.b1
+    d1 = U * (lin(ax, np.abs(w.W1)) + np.abs(w.b1))
+    t1 = r(lrelu64(z1))
+    s1 = round_slack(z1, d1, t1, fmt)
+    z2 = lin(t1, w.W2) + w.b2
+    d2 = lin(U * np.abs(t1) + s1, np.abs(w.W2)) + U * np.abs(w.b2)
+    y = r(lrelu64(z2))
+    sy = round_slack(z2, d2, y, fmt)
+    nb, h, wd, _ = xq.shape
+    ys = shuffle(y)
+    z3 = lin(ys, w.Wf) + unplanes([lin(xq, R) for R in w.R], nb, h, wd)
+    mag3 = lin(np.abs(ys), np.abs(w.Wf)) + unplanes([lin(ax, np.abs(R)) for R in w.R], nb, h, wd)
+    return z3, mag3, U * mag3 + lin(shuffle(sy), np.abs(w.Wf))
+
+
+def x16_check_hid(hid_bits, xin, P, i, fmt):
+    """the interval rule with delta_hid; "median" / "max": delta_hid / magnitude over the stage"""
+    z, mag, d = x16_hid_chain(xin, P, i, fmt)
+    st = xs.check16(hid_bits, z, d, fmt)
+    ratio = d[mag > 0] / mag[mag > 0]
+    st["median"], st["max"] = float(np.median(ratio)), float(ratio.max())
+    return st
+
+
+def x16_check_net(net_bits, hid, P, i, fmt):
+    """net[i] = rne16(lrelu(Blur(hid) / 16 + bf)) with the fp32 bias (nr_blur_mfma.inc:289-292, neural_render_x16.inc:492-494): one stage"""
+    z, mag = fused_stage_net(hid, P, i)
+    return xs.check16(net_bits, z, xs.U * mag, fmt, act=lrelu64)
+
+
+def blur_form(nb, H, W, K, env=None):
+    """which kernel launch_blur_q picks for a level of INPUT resolution H x W (nr_blur_mfma.inc:654-711): "mfma" (blur_mfma_q_kernel,
+    blur_mfma_last_kernel: feat_2_rgb's weights enter as hi + lo halves, :12-14, :64-76, :388-401) or "scalar" (blur_act_rgb_q_kernel:
+    the fp32 weights themselves, neural_render_x16.inc:496-498)"""
+    env = env or {}
+    if env.get("N3DT_NR_BLUR_MFMA") == "0" or H < 2 or W < 4 or (H & 1) or (W & 3) or (K & 31) or K > 256:
+        return "scalar"
+    return "mfma" if 4 * nb * H * W * K * 2 < (1 << 31) else "scalar"
+
+
+def up_matrix(n, fault=None):
+    """rgb_upsample along one axis: the blur of the bilinear x2.  fault "bilinear_swap": the two outer taps (0.3125 / 0.0625) of every
+    interior output swapped between even and odd outputs."""
+    U = blur_matrix(2 * n) @ bilinear_matrix(n)
+    if fault == "bilinear_swap":
+        for o in range(2, 2 * n - 2):
+            b = o >> 1
+            U[o, b - 1], U[o, b + 1] = U[o, b + 1], U[o, b - 1]
+    return U
+
+
+def x16_rgb_stage(hid, net, lo, P, i, fmt, form):
+    """The fp32 output of level i before the sigmoid, from the STORED hid [nb, 2h, 2h, CO], the stored plane `lo` [nb, h, h, 3] the level
+    read, feat_b and to_rgb_{i + 1}: pre = Wrgb' net + brgb + rgb_upsample(lo), net the 16-bit activation (the kernels round it before
+    feat_2_rgb, nr_blur_mfma.inc:25-27, :292, neural_render_x16.inc:494-495) and Wrgb' = hi + lo in the matrix-pipe forms.  net: the
+    stored map of a non-last level; None on the last level, whose net is never stored: the nominal rne16(lrelu(z)) then, and its
+    rounding slack s_net (round_slack under delta = U mag) enters the bound as sum |Wrgb| s_net.
+    Returns (pre, S = |brgb| + sum |w net| + rgb_upsample |lo|, slack)."""
+    W = hi_lo16(P.rgb_w[i + 1], fmt) if form == "mfma" else np.asarray(P.rgb_w[i + 1], dtype=np.float64)
+    slack = 0.0
+    if net is None:
+        z, mag = fused_stage_net(hid, P, i)
+        net = rne(fmt)(lrelu64(z))
+        slack = lin(round_slack(z, xs.U * mag, net, fmt), np.abs(W))
+    pre = lin(net, W) + P.rgb_b[i + 1] + rgb_upsample(lo)
+    S = lin(np.abs(net), np.abs(W)) + np.abs(P.rgb_b[i + 1]) + rgb_upsample(np.abs(lo))
+    return pre, S, slack
+
+
+def x16_rgb_bounds(pre, S, slack):
+    """(bound of the pre-sigmoid plane, bound of img): MARGIN x NR_X16_RGB_FLOOR x S + slack, and through the sigmoid
+    sigma'(pre) x that + MARGIN x NR_X16_SIGMOID_FLOOR"""
+    b = MARGIN * NR_X16_RGB_FLOOR * S + slack
+    s = sigmoid(pre)
+    return b, s * (1.0 - s) * b + MARGIN * NR_X16_SIGMOID_FLOOR
+
+
+def worst_ratio(got, want, bound):
+    """(largest |got - want| / bound, its index)"""
+    r = np.abs(np.asarray(got, dtype=np.float64) - want) / bound
+    j = int(np.argmax(r))
+    return float(r.reshape(-1)[j]), tuple(int(v) for v in np.unravel_index(j, r.shape))
+
+
+def rgb0_stage(x, P):
+    """(rgb0, S) of the level-0 projection of the fp32 map: fp32 weights, nothing is rounded"""
+    return conv(x, P.rgb_w[0], P.rgb_b[0], np.matmul), conv_mag(x, P.rgb_w[0], P.rgb_b[0])
+
+
+# ---- float32-ordered emulations -------------------------------------------------------------
+RGB_ORDERS = (("16-wide sequential, rows first", mm32_seq16, True), ("torch.matmul, columns first", mm32_torch, False))
+
+
+def sep32(A, x, rows_first):
+    return sep(A.astype(np.float32), np.asarray(x, dtype=np.float32), rows_first)
+
+
+def rgb_pre32(net, lo, W, b, mm, rows_first, fault=None):
+    """the pre-sigmoid value of a level in float32 from fixed activations"""
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    z = mm(f32(net).reshape(-1, net.shape[-1]), np.ascontiguousarray(f32(W).T)).reshape(net.shape[:-1] + (3,))
+    return z + f32(b) + sep32(up_matrix(lo.shape[1], fault), lo, rows_first)
+
+
+def sigmoid32(z, use_torch=False):
+    z = np.asarray(z, dtype=np.float32)
+    if use_torch:
+        return torch.sigmoid(torch.from_numpy(np.ascontiguousarray(z))).numpy()
+    return (np.float32(1) / (np.float32(1) + np.exp(-z))).astype(np.float32)
+
+
+INFER_FAULTS = ("k_block", "residual_plane", "reflect", "bilinear_swap", "net_trunc")
+
+
+def emulate_infer(x, P, fmt, mm=mm32_seq16, fault=None):
+    """Free-running float32-ordered CPU emulation of the 16-bit inference renderer in map type fmt: every stage rounds where the kernels
+    do, so workspace-format data of realistic values exists without a GPU.  Per block i: the 16-bit patterns t1_bits, y_bits (in
+    registers on the GPU), hid_bits, net_bits (the last level's too; emu_map decodes one); lo[i] the fp32 plane level i reads
+    (lo[0] = rgb0), pre[i] what it writes (= lo[i + 1]), img[i] = the image of the call over the first i + 1 blocks.
+    fault: one of INFER_FAULTS --
+      k_block         one 32-wide k-block (32 .. 63) of the layer_2 product dropped in the first 32-pixel tile of block 0
+      residual_plane  R_q taken from the next sub-pixel plane
+      reflect         the blur's reflected row above the first row read off by one (row 0 instead of row 1)
+      bilinear_swap   rgb_upsample's two outer taps swapped (up_matrix)
+      net_trunc       net rounded toward zero"""
+    assert fault is None or fault in INFER_FAULTS
+    r = rne(fmt)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    rnd = lambda z32: r(f32(z32).astype(np.float64))  # noqa: E731
+    lin32 = lambda a, W: mm(f32(a).reshape(-1, a.shape[-1]), np.ascontiguousarray(f32(W).T)).reshape(a.shape[:-1] + (W.shape[0],))  # noqa: E731
+    x = np.asarray(x, dtype=np.float64)
+    e = {k: [] for k in ("t1_bits", "y_bits", "hid_bits", "net_bits", "pre", "img")}
+    e["fmt"] = fmt
+    e["lo"] = [(lin32(x, P.rgb_w[0]) + f32(P.rgb_b[0])).astype(np.float64)]
+    xin = x
+    for i in range(P.n):
+        w = X16Block(P, i, fmt)
+        nb, h, wd, _ = xin.shape
+        xq = r(xin)
+        t1 = rnd(lrelu(lin32(xq, w.W1) + f32(w.b1)))
+        z2 = lin32(t1, w.W2) + f32(w.b2)
+        if fault == "k_block" and i == 0:
+            cut = t1.copy().reshape(-1, t1.shape[-1])
+            cut[:, 32:64] = 0.0
+            rows = min(32, cut.shape[0])
+            z2.reshape(-1, z2.shape[-1])[:rows] = (lin32(cut[:rows], w.W2) + f32(w.b2))
+        y = rnd(lrelu(z2))
+        Rs = w.R[1:] + w.R[:1] if fault == "residual_plane" else w.R
+        hid = rnd(lin32(shuffle(y), w.Wf) + unplanes([lin32(xq, R) for R in Rs], nb, h, wd))
+        bl = blur(f32(hid))
+        if fault == "reflect":
+            B = blur_matrix(2 * h)
+            Bc = B.copy()
+            B[0] = 0.0
+            B[0, 0], B[0, 1] = 0.75, 0.25
+            bl = np.einsum("jw,niwc->nijc", Bc.astype(np.float32), np.einsum("ih,nhwc->niwc", B.astype(np.float32), f32(hid)))
+        zn = lrelu(bl + f32(P.bf[i])).astype(np.float64)
+        net = trunc16(zn, fmt) if fault == "net_trunc" else r(zn)
+        pre = rgb_pre32(net, e["lo"][i], hi_lo16(P.rgb_w[i + 1], fmt), P.rgb_b[i + 1], mm, True, fault)
+        for k, a in (("t1", t1), ("y", y), ("hid", hid), ("net", net)):
+            e[k + "_bits"].append(xs.bits16(a, fmt))      # (only the patterns are kept: the large cases' maps are hundreds of MB in float64)
+        e["pre"].append(pre.astype(np.float64))
+        e["lo"].append(pre.astype(np.float64))
+        e["img"].append(sigmoid32(pre).astype(np.float64))
+        xin = net
+    return e
+
+
+def emu_map(e, k, i):
+    """map k ("t1", "y", "hid", "net") of block i of an emulation as float64"""
+    return xs.bits16_to_f64(e[k + "_bits"][i], e["fmt"])
+
+
+def x16_one_stage(e, x, P, fmt):
+    """(tag, z64, magnitude, lrelu?, bits) of the ONE-stage rule on every rounding of an emulation, each from the stage's own stored
+    input (t1 and y are observable on the CPU only; on the GPU the training twin stores them)"""
+    xin = np.asarray(x, dtype=np.float64)
+    for i in range(P.n):
+        w = X16Block(P, i, fmt)
+        nb, h, wd, _ = xin.shape
+        xq = rne(fmt)(xin)
+        yield "t1[%d]" % i, lin(xq, w.W1) + w.b1, lin(np.abs(xq), np.abs(w.W1)) + np.abs(w.b1), True, e["t1_bits"][i]
+        t1 = emu_map(e, "t1", i)
+        yield "y[%d]" % i, lin(t1, w.W2) + w.b2, lin(np.abs(t1), np.abs(w.W2)) + np.abs(w.b2), True, e["y_bits"][i]
+        ys = shuffle(emu_map(e, "y", i))
+        z = lin(ys, w.Wf) + unplanes([lin(xq, R) for R in w.R], nb, h, wd)
+        mag = lin(np.abs(ys), np.abs(w.Wf)) + unplanes([lin(np.abs(xq), np.abs(R)) for R in w.R], nb, h, wd)
+        yield "hid[%d]" % i, z, mag, False, e["hid_bits"][i]
+        z, mag = fused_stage_net(emu_map(e, "hid", i), P, i)
+        yield "net[%d]" % i, z, mag, True, e["net_bits"][i]
+        xin = emu_map(e, "net", i)

@@ -271,3 +271,160 @@ def test_a_deliberate_fault_is_reported_at_the_gpu_bound(fault):
         assert lines16, "%s passes the bf16 bound in case %s" % (fault, case)
         print(fault, case, "exact: %d entries reported, largest %.3g of S; bf16: largest %.3g of S" %
               (len(lines), max(maxima.values()), max(maxima16.values())))
+
+
+# ---------------------------------------------------------------------------------------------
+# the 16-bit INFERENCE renderer, forward only, bf16 and IEEE half (the last section of nr_restatement.py; the GPU side is
+# test_gpu_nr_infer_stagewise.py): layout, floors, caps on the CPU emulation, and the five faults the rules must report
+# ---------------------------------------------------------------------------------------------
+def infer_mm(case):
+    """the large cases' emulation takes torch.matmul (their maps are 16-wide-sequential minutes); any float32 order is a legal one"""
+    return nr.mm32_torch if case in nr.LARGE_INFER_CASES else nr.mm32_seq16
+
+
+@functools.lru_cache(maxsize=None)
+def infer_inputs(case):
+    P, x, _ = nr.case_inputs(case, nr.INFER_CASES[case])
+    return P, x
+
+
+@functools.lru_cache(maxsize=None)
+def infer_emulated(case, fmt):
+    P, x = infer_inputs(case)
+    return nr.emulate_infer(x, P, fmt, mm=infer_mm(case))
+
+
+def test_16_bit_formats_round_like_the_hardware_types():
+    """round16 / bits16 against numpy's IEEE half (subnormals, ties, overflow) and torch's bfloat16 conversion of float32 values; the
+    bf16 names are wrappers"""
+    rng = np.random.RandomState(3)
+    z = np.concatenate([rng.randn(200000) * 10.0 ** rng.uniform(-9, 5, 200000),
+                        [0.0, -0.0, 65504.0, 65519.9, 65520.0, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * 1.0001, 3 * 2.0 ** -25, 2.0 ** -14, 1.0 + 2.0 ** -11]])
+    z = z.astype(np.float32).astype(np.float64)
+    with np.errstate(over="ignore"):
+        half = z.astype(np.float16)
+    assert np.array_equal(xs.bits16(z, "fp16"), half.view(np.uint16))
+    assert np.array_equal(xs.bits16_to_f64(half.view(np.uint16), "fp16"), half.astype(np.float64))
+    bf = torch.from_numpy(z.astype(np.float32)).to(torch.bfloat16)
+    assert np.array_equal(xs.bf16_bits(z), bf.view(torch.int16).numpy().view(np.uint16))
+    assert np.array_equal(xs.bits16(z, "bf16"), xs.bf16_bits(z)) and np.array_equal(xs.round16(z, "bf16"), xs.bf16_round(z))
+    fin = np.abs(z) < 6e4
+    assert np.all(np.abs(nr.trunc16(z[fin], "fp16")) <= np.abs(z[fin])) and np.array_equal(nr.trunc16(half.astype(np.float64)[fin], "fp16"), half.astype(np.float64)[fin])
+
+
+@pytest.mark.parametrize("case", list(nr.INFER_CASES), ids=str)
+def test_infer_workspace_layout_is_consistent(case):
+    """for every k: the regions a call writes lie inside their carve regions, in order and without overlap, and the 16-bit carve ends
+    before the packed tail"""
+    fs, C, n, nb = case
+    for k in range(1, n + 1):
+        ck = (fs, C, k, nb)
+        L = nr.infer_ws_layout(ck)
+        assert L["t1"] == 0 and L["end"] <= L["packw"] and L["total"] % 4 == 0
+        order = ["t1", "ps", "hid", "netA", "netB", "rgbA", "rgbB", "end"]
+        assert all(L[a] <= L[b] for a, b in zip(order, order[1:]))
+        o = 0
+        for off, size in sorted(nr.infer_written(ck)):
+            assert off >= o and off % 4 == 0
+            o = off + size
+        assert o <= L["total"]
+        for name, nxt in (("hid", "netA"), ("netA", "netB"), ("netB", "rgbA"), ("rgbA", "rgbB"), ("rgbB", "end")):
+            for off, size in nr.infer_written(ck):
+                if off == L[name]:
+                    assert off + size <= L[nxt], (name, k)
+
+
+def test_infer_floors_are_in_range():
+    """NR_X16_RGB0_FLOOR, NR_X16_RGB_FLOOR, NR_X16_SIGMOID_FLOOR re-measured over every inference case in both formats and both
+    float32 orders: measured <= floor < 2 x measured"""
+    m = {"rgb0": 0.0, "rgb": 0.0, "sigmoid": 0.0}
+    for case in nr.INFER_CASES:
+        P, x = infer_inputs(case)
+        z64, S = nr.rgb0_stage(x, P)
+        for tag, mm, rows_first in nr.RGB_ORDERS:
+            z32 = nr.conv(x.astype(np.float32), P.rgb_w[0].astype(np.float32), P.rgb_b[0].astype(np.float32), mm)
+            m["rgb0"] = max(m["rgb0"], float((np.abs(z32 - z64) / S).max()))
+        for fmt in nr.FORMATS16:
+            e = infer_emulated(case, fmt)
+            for i in range(P.n):
+                net = nr.emu_map(e, "net", i)
+                pre, S, _ = nr.x16_rgb_stage(None, net, e["lo"][i], P, i, fmt, "mfma")
+                for tag, mm, rows_first in nr.RGB_ORDERS:
+                    p32 = nr.rgb_pre32(net, e["lo"][i], nr.hi_lo16(P.rgb_w[i + 1], fmt), P.rgb_b[i + 1], mm, rows_first)
+                    m["rgb"] = max(m["rgb"], float((np.abs(p32 - pre) / S).max()))
+                    for use_torch in (False, True):
+                        err = np.abs(nr.sigmoid32(p32, use_torch).astype(np.float64) - nr.sigmoid(p32.astype(np.float64)))
+                        m["sigmoid"] = max(m["sigmoid"], float(err.max()))
+        print(case, {k: "%.3g" % v for k, v in m.items()})
+    for k, floor in (("rgb0", nr.NR_X16_RGB0_FLOOR), ("rgb", nr.NR_X16_RGB_FLOOR), ("sigmoid", nr.NR_X16_SIGMOID_FLOOR)):
+        print("%s: measured %.3g, floor %.3g" % (k, m[k], floor))
+        assert m[k] <= floor < 2.0 * m[k], (k, m[k], floor)
+
+
+@pytest.mark.parametrize("fmt", nr.FORMATS16)
+@pytest.mark.parametrize("case", list(nr.INFER_CASES), ids=str)
+def test_infer_emulation_passes_every_rule(case, fmt):
+    """The CPU emulation (one legal float32 order) of the case in the format: every rounding under the ONE-stage rule with no mismatch
+    and inside the caps of the format (bf16: AMBIGUOUS_CAP 5 %, WIDE_CAP 0.5 %; IEEE half: 25 %, 4 %); hid under the chain rule with the
+    median of delta_hid / magnitude <= HID_MEDIAN_CAP; the pyramid plane from the stored net and the image from the stored hid inside
+    their bounds"""
+    P, x = infer_inputs(case)
+    e = infer_emulated(case, fmt)
+    amb_cap, wide_cap = xs.CAPS[fmt]
+    for tag, z, mag, act, bits in nr.x16_one_stage(e, x, P, fmt):
+        st = xs.check16(bits, z, xs.U * mag, fmt, act=nr.lrelu64 if act else None)
+        xs.report("%s %s %s" % (case, fmt, tag), st)
+        assert st["mismatches"] == 0 and st["max_ulp"] <= 1, tag
+        assert st["ambiguous"] <= amb_cap * st["n"] and st["wide"] <= wide_cap * st["n"], tag
+    xin = x
+    for i in range(P.n):
+        st = nr.x16_check_hid(e["hid_bits"][i], xin, P, i, fmt)
+        print("%s %s hid[%d] chain rule: ambiguous %.1f %%, mismatches %d, delta_hid / magnitude median %.3g maximum %.3g" %
+              (case, fmt, i, 100.0 * st["ambiguous"] / st["n"], st["mismatches"], st["median"], st["max"]))
+        assert st["mismatches"] == 0 and st["max_ulp"] <= 1 and st["median"] <= nr.HID_MEDIAN_CAP
+        hid, net = nr.emu_map(e, "hid", i), nr.emu_map(e, "net", i)
+        pre, S, _ = nr.x16_rgb_stage(None, net, e["lo"][i], P, i, fmt, "mfma")
+        bound, _ = nr.x16_rgb_bounds(pre, S, 0.0)
+        assert nr.worst_ratio(e["pre"][i], pre, bound)[0] <= 1.0
+        pre, S, slack = nr.x16_rgb_stage(hid, None, e["lo"][i], P, i, fmt, "mfma")
+        _, bound = nr.x16_rgb_bounds(pre, S, slack)
+        worst, at = nr.worst_ratio(e["img"][i], nr.sigmoid(pre), bound)
+        print("%s %s img after %d blocks: largest error / bound %.3g" % (case, fmt, i + 1, worst))
+        assert worst <= 1.0
+        xin = net
+
+
+def infer_verdicts(e, x, P, fmt):
+    """which rules report something on an emulation: {"hid", "net", "img", "plane"} -> bool, over all blocks, exactly as the GPU test
+    applies them (hid: chain rule; net: bit rule; img: from the stored hid with the slack; plane: from the stored net)"""
+    out = {"hid": False, "net": False, "img": False, "plane": False}
+    xin = x
+    for i in range(P.n):
+        st = nr.x16_check_hid(e["hid_bits"][i], xin, P, i, fmt)
+        out["hid"] |= st["mismatches"] > 0 or st["max_ulp"] > 1
+        hid, net = nr.emu_map(e, "hid", i), nr.emu_map(e, "net", i)
+        st = nr.x16_check_net(e["net_bits"][i], hid, P, i, fmt)
+        out["net"] |= st["mismatches"] > 0 or st["max_ulp"] > 1
+        pre, S, _ = nr.x16_rgb_stage(None, net, e["lo"][i], P, i, fmt, "mfma")
+        out["plane"] |= nr.worst_ratio(e["pre"][i], pre, nr.x16_rgb_bounds(pre, S, 0.0)[0])[0] > 1.0
+        pre, S, slack = nr.x16_rgb_stage(hid, None, e["lo"][i], P, i, fmt, "mfma")
+        out["img"] |= nr.worst_ratio(e["img"][i], nr.sigmoid(pre), nr.x16_rgb_bounds(pre, S, slack)[1])[0] > 1.0
+        xin = net
+    return out
+
+
+EXPECTED_REPORTS = {"k_block": ("hid",), "residual_plane": ("hid",), "reflect": ("img",), "bilinear_swap": ("img", "plane"), "net_trunc": ("net",)}
+
+
+@pytest.mark.parametrize("fmt", nr.FORMATS16)
+@pytest.mark.parametrize("fault", nr.INFER_FAULTS)
+def test_a_deliberate_inference_fault_is_reported(fault, fmt):
+    """The CPU emulation with one deliberate fault, at the bounds the GPU test uses, in every case of GPU_CASES (every fault can show
+    in each: the smallest has one 16-pixel tile, 4 x 4 maps are all border, every plane has interior outputs): the rule named for
+    the fault reports it; the emulation without a fault reports nothing (test_infer_emulation_passes_every_rule)."""
+    for case in nr.GPU_CASES:
+        P, x = infer_inputs(case)
+        got = infer_verdicts(nr.emulate_infer(x, P, fmt, fault=fault), x, P, fmt)
+        print(fault, fmt, case, got)
+        for rule in EXPECTED_REPORTS[fault]:
+            assert got[rule], "%s passes the %s rule in case %s (%s)" % (fault, rule, case, fmt)

@@ -30,6 +30,10 @@ torch.matmul), against float64, over every forward and dX stage of the five case
                                                                       it covers the MFMA's unspecified internal order)
     ambiguous share under U: at most 5 % of any stage of any case (asserted on the CPU emulation; measured <= 1.3 %)
 
+The rule is written once for both 16-bit map types (`check16`, `ambiguous_share16`, `bits16`, `round16`: "bf16", or "fp16" = IEEE
+half with its subnormals); `check_bf16`, `ambiguous_share`, `bf16_bits`, `bf16_round` are the bf16 wrappers.  IEEE half has 8 x finer
+spacing under the same U, so its caps are wider (CAPS; used by the 2-D renderer's inference pin, nr_restatement.py).
+
 The weight-gradient products (fp32 sums of exact bf16 x bf16 products over blocks, slices, XCD partials and atomics) are
 bounded per entry relative to sum_points |dz| |x| of that entry, one bound per product family (DW_FLOOR), 4 x the largest
 error of the fp32-ordered CPU sums.  Per-sample weights: W_FLOOR in the measure of `weight_tolerance`.
@@ -55,6 +59,11 @@ U_FLOOR = 3.0e-7
 U = 4.0 * U_FLOOR
 AMBIGUOUS_CAP = 0.05
 WIDE_CAP = 5e-3           # share of a stage's entries whose delta exceeds the spacing of the result (see the docstring)
+# IEEE half has 8 x finer spacing under the same U: the float64 reference alone (nr_restatement's inference stages, cases (4, 256, 1, 1)
+# and (4, 256, 3, 2)) shows ambiguous <= 15.4 % (y of block 0) and wide <= 2.4 % (t1 of block 0)
+AMBIGUOUS_CAP_FP16 = 0.25
+WIDE_CAP_FP16 = 0.04
+CAPS = {"bf16": (AMBIGUOUS_CAP, WIDE_CAP), "fp16": (AMBIGUOUS_CAP_FP16, WIDE_CAP_FP16)}
 # weight-gradient families: largest |sum32 - sum64| / sum |dz| |x| of the fp32-ordered CPU sums
 DW_FLOOR = {
     "hidden": 4.5e-7,    # dW_1..7 (module 5: its H4 columns), 384 x 384
@@ -151,38 +160,62 @@ def dw_slices(bpf, B, n_products=None, gy=1):
 # bf16 <-> float64.  Round to nearest even straight from float64 (no double rounding through float32), which is what
 # the kernels' (__bf16)v does to an fp32 value (v_cvt_pk_bf16_f32) and what torch.bfloat16 conversion does.
 # ---------------------------------------------------------------------------------------------
-def bf16_round(z):
+FORMATS = {"bf16": (8, -126), "fp16": (11, -14)}   # significant bits (the hidden one included), exponent of the smallest normal number
+
+
+def round16(z, fmt):
+    """float64 -> the nearest value of the 16-bit format (ties to even, subnormals included, overflow to infinity), as float64"""
+    p, emin = FORMATS[fmt]
     z = np.asarray(z, dtype=np.float64)
     a = np.abs(z)
     _, e = np.frexp(a)                      # a = m 2^e, m in [0.5, 1)
-    e = np.maximum(e, -125)                 # below 2^-126 the spacing stays 2^-133 (subnormals)
-    ulp = np.ldexp(1.0, e - 8)              # 8 significant bits
+    e = np.maximum(e, emin + 1)             # below the smallest normal number the spacing stays 2^(emin + 1 - p) (subnormals)
+    ulp = np.ldexp(1.0, e - p)
     with np.errstate(over="ignore", invalid="ignore"):
-        return np.copysign(np.rint(a / ulp) * ulp, z)
+        r = np.rint(a / ulp) * ulp
+        if fmt == "fp16":
+            r = np.where(r > 65504.0, np.inf, r)
+        return np.copysign(r, z)
 
 
-def bf16_bits(z):
+def bits16(z, fmt):
     with np.errstate(over="ignore"):
-        r = np.ascontiguousarray(bf16_round(z).astype(np.float32))
+        if fmt == "fp16":
+            return np.ascontiguousarray(round16(z, fmt).astype(np.float16)).view(np.uint16)
+        r = np.ascontiguousarray(round16(z, fmt).astype(np.float32))
     return (r.view(np.uint32) >> 16).astype(np.uint16)
 
 
-def bf16_to_f64(bits):
+def bits16_to_f64(bits, fmt):
+    if fmt == "fp16":
+        return np.ascontiguousarray(np.asarray(bits, dtype=np.uint16)).view(np.float16).astype(np.float64)
     b = np.ascontiguousarray(np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16)
     return b.view(np.float32).astype(np.float64)
 
 
+def bf16_round(z):
+    return round16(z, "bf16")
+
+
+def bf16_bits(z):
+    return bits16(z, "bf16")
+
+
+def bf16_to_f64(bits):
+    return bits16_to_f64(bits, "bf16")
+
+
 def ordinal(bits):
-    """bf16 bit patterns on a line: neighbours differ by 1, -0 = +0 = 0."""
+    """16-bit patterns (bf16 or IEEE half: sign and magnitude both) on a line: neighbours differ by 1, -0 = +0 = 0."""
     m = (np.asarray(bits).astype(np.int32)) & 0x7FFF
     return np.where((np.asarray(bits).astype(np.int32) & 0x8000) != 0, -m, m)
 
 
-def split_hi_lo(b32):
-    """X16::bias_frag (x16_core.h:45-47): hi = bf16(b), lo = bf16(b - hi); returned as float64 (hi, lo)."""
+def split_hi_lo(b32, fmt="bf16"):
+    """X16::bias_frag (x16_core.h:67-69 bf16, :100-102 IEEE half): hi = rne16(b), lo = rne16(b - hi); returned as float64 (hi, lo)."""
     b = np.asarray(b32, dtype=np.float32).astype(np.float64)
-    hi = bf16_round(b)
-    lo = bf16_round((b - hi).astype(np.float32).astype(np.float64))
+    hi = round16(b, fmt)
+    lo = round16((b - hi).astype(np.float32).astype(np.float64), fmt)
     return hi, lo
 
 
@@ -338,15 +371,16 @@ class Workspace:
 # ---------------------------------------------------------------------------------------------
 # the comparison rule
 # ---------------------------------------------------------------------------------------------
-def check_bf16(stored_bits, z64, delta, relu=False, gate=None, act=None):
-    """See the module docstring.  gate (bool, or None): entries whose gate is closed must be stored as zero.
+def check16(stored_bits, z64, delta, fmt, relu=False, gate=None, act=None):
+    """The comparison rule of the module docstring in the 16-bit format `fmt` ("bf16" or "fp16").  gate (bool, or None): entries
+    whose gate is closed must be stored as zero.
     act: a monotone activation in place of the ReLU (the 2-D renderer's LeakyReLU, nr_restatement.py); the rule is unchanged.
     Returns dict(n, ambiguous, mismatches, max_ulp, worst): `worst` lists (flat index, stored, expected, z64, delta) of up to eight
     failing entries."""
     z64 = np.asarray(z64, dtype=np.float64)
     delta = np.broadcast_to(np.asarray(delta, dtype=np.float64), z64.shape)
     act = act or ((lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v))
-    e, a, b = bf16_bits(act(z64)), bf16_bits(act(z64 - delta)), bf16_bits(act(z64 + delta))
+    e, a, b = bits16(act(z64), fmt), bits16(act(z64 - delta), fmt), bits16(act(z64 + delta), fmt)
     if gate is not None:
         closed = ~np.asarray(gate, dtype=bool)
         e, a, b = (np.where(closed, np.uint16(0), v) for v in (e, a, b))
@@ -356,21 +390,30 @@ def check_bf16(stored_bits, z64, delta, relu=False, gate=None, act=None):
     wide = (ob - oa) > 1          # delta is wider than the spacing of the result: more than two values are possible
     dist = np.abs(os_ - oe)       # the true distance, never clamped
     bad = np.flatnonzero(~ok)
-    worst = [(int(i), float(bf16_to_f64(np.asarray(stored_bits).reshape(-1)[i:i + 1])[0]), float(bf16_to_f64(e.reshape(-1)[i:i + 1])[0]),
+    worst = [(int(i), float(bits16_to_f64(np.asarray(stored_bits).reshape(-1)[i:i + 1], fmt)[0]), float(bits16_to_f64(e.reshape(-1)[i:i + 1], fmt)[0]),
               float(z64.reshape(-1)[i]), float(delta.reshape(-1)[i])) for i in bad[:8]]
     narrow = dist[~wide]
     return {"n": int(z64.size), "ambiguous": int(amb.sum()), "mismatches": int(bad.size), "max_ulp": int(narrow.max()) if narrow.size else 0,
             "wide": int(wide.sum()), "max_ulp_wide": int(dist[wide].max()) if wide.any() else 0, "worst": worst}
 
 
-def ambiguous_share(z64, delta, relu=False, gate=None, act=None):
+def check_bf16(stored_bits, z64, delta, relu=False, gate=None, act=None):
+    """check16 in bf16: see the module docstring."""
+    return check16(stored_bits, z64, delta, "bf16", relu=relu, gate=gate, act=act)
+
+
+def ambiguous_share16(z64, delta, fmt, relu=False, gate=None, act=None):
     """(share of ambiguous entries, share of wide-delta entries) of a stage"""
     z64 = np.asarray(z64, dtype=np.float64)
     act = act or ((lambda v: np.maximum(v, 0.0)) if relu else (lambda v: v))
-    span = ordinal(bf16_bits(act(z64 + delta))) - ordinal(bf16_bits(act(z64 - delta)))
+    span = ordinal(bits16(act(z64 + delta), fmt)) - ordinal(bits16(act(z64 - delta), fmt))
     if gate is not None:
         span = np.where(np.asarray(gate, dtype=bool), span, 0)
     return float((span != 0).mean()), float((span > 1).mean())
+
+
+def ambiguous_share(z64, delta, relu=False, gate=None, act=None):
+    return ambiguous_share16(z64, delta, "bf16", relu=relu, gate=gate, act=act)
 
 
 def report(tag, st):
