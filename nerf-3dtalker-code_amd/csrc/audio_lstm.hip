@@ -21,6 +21,7 @@
 #include "../../include/n3dt.h"
 #include "gemm32.h"
 #include "n3dt_device.h"
+#include "n3dt_launch.h"
 
 #define A2S_IN 1280
 #define A2S_H 640

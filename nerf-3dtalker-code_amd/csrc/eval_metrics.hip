@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "eval_metrics_core.h"
+#include "n3dt_launch.h"
 
 #define EVM_MAX_GRID (1 << 20)
 

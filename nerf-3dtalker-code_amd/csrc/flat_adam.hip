@@ -46,6 +46,7 @@
 //       before adam_elem; a coefficient of 1 leaves the arithmetic bit-identical to flat_adam_kernel<false>, which is the
 //       unguarded step as it always was.
 #include "n3dt_device.h"
+#include "n3dt_launch.h"
 
 #define ADAM_THREADS 256
 #define ADAM_UNROLL 4

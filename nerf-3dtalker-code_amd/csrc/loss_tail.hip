@@ -9,6 +9,7 @@
 // acc[8] = { sum_bg, sum_head, n_head, sum_nonhead, n_nonhead, n_bg, -, - } (element counts, i.e. 3 per pixel).
 // terms[4] = { bg_loss, head_loss, nonhead_loss, total = (bg + head) + nonhead } (the reference sums in that order, :228-231).
 #include "n3dt_device.h"
+#include "n3dt_launch.h"
 
 __device__ __forceinline__ float loss_clean(float r) {
     if (r != r) return 0.0f;  // nan_to_num(nan=0.0); +-inf map to +-FLT_MAX like torch

@@ -32,6 +32,7 @@
 #include "eval_metrics_core.h"
 #include "conv_mfma.h"
 #include "lpips_core.h"
+#include "n3dt_launch.h"
 
 // ---- packed weights ------------------------------------------------------------------------------------------------------------
 // Per conv one B matrix in conv_frag.h's fragment order, [Kp/16][Np/32] fragments of 64 lanes x 8 bf16: element e holds

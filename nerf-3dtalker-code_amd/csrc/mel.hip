@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mel_core.h"
+#include "n3dt_launch.h"
 
 #define MEL_MAX_GRID 65536
 

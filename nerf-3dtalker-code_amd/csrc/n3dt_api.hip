@@ -3,6 +3,7 @@
 // caller's stream.  No allocation, no synchronisation; the only mutable global state is the opt-in
 // measurement hook (n3dt_prof_*, mutex-guarded).
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,118 +12,27 @@
 
 #include "../../include/n3dt.h"
 #include "n3dt_layout.h"
+#include "n3dt_launch.h"
 #include "eval_metrics_core.h"
 #include "lpips_core.h"
 #include "mel_core.h"
 #include "syncnet_core.h"
 
-extern "C" {
-void n3dt_launch_pack(const N3dtGeom*, int, const N3dtMlpParams*, void*, hipStream_t);
-void n3dt_launch_fold(const N3dtGeom*, const N3dtMlpParams*, const float*, const float*, const float*, float*, int, hipStream_t);
-void n3dt_launch_ray_head(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*, float*,
-                          float*, float*, float*, hipStream_t);
-void n3dt_launch_ray_head_mfma(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*, float*,
-                               float*, float*, float*, float*, hipStream_t);
-void n3dt_launch_ray_head_mfma16(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*, float*,
-                                 float*, float*, float*, void*, int, float*, const float*, const float*, hipStream_t);
-void n3dt_launch_chw_to_hwc(int, int, const float*, float*, hipStream_t);
-void n3dt_launch_rayfold(const N3dtGeom*, const float*, const float*, hipStream_t);
-void n3dt_launch_ray_vd_bias(const N3dtGeom*, const float*, long, const float*, const float*, const float*, float*, hipStream_t);
-void n3dt_launch_embed_freqs(int, size_t, int, const float*, float*, hipStream_t);
-void n3dt_launch_sample_points(const N3dtGeom*, const float*, const float*, const float*, const float*, const float*, float*, float*,
-                               float*, float*, float*, hipStream_t);
-void n3dt_launch_embed(int, size_t, const float*, float*, hipStream_t);
-size_t n3dt_seam_mlp_ws_floats(const N3dtGeom*, size_t);
-void n3dt_launch_mlp_points(const N3dtGeom*, size_t, const N3dtMlpParams*, const float*, const float*, const float*, float*, float*, float*,
-                            hipStream_t);
-void n3dt_launch_composite(int, int, int, int, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
-                           hipStream_t);
-void n3dt_launch_x16_pack_probe(int, int, size_t, const float*, unsigned short*, hipStream_t);
-void n3dt_launch_x16_pe_probe(int, int, size_t, const float*, unsigned short*, hipStream_t);
-void n3dt_launch_fine_sample(const N3dtGeom*, int, const float*, const float*, const float*, const float*, float*, hipStream_t);
-void n3dt_launch_nerf_fwd_f32(const N3dtGeom*, const N3dtMlpParams*, const void*, const float*, const float*, const float*,
-                              const float*, const float*, const float*, float*, float*, hipStream_t);
-void n3dt_launch_nerf_fwd_x16(const N3dtGeom*, int, const void*, const float*, const float*, const float*, const float*,
-                              const float*, const float*, float*, float*, hipStream_t);
-void n3dt_launch_nerf_fwd_x16s(const N3dtGeom*, const void*, const float*, const float*, const float*, const float*, const float*,
-                               const float*, float*, float*, hipStream_t);
-size_t n3dt_nr_workspace_floats(const N3dtGeom*, int);
-size_t n3dt_train_saved_floats(const N3dtGeom*);
-size_t n3dt_train_ws_floats(const N3dtGeom*);
-void n3dt_launch_train_fwd(const N3dtGeom*, const N3dtMlpParams*, const float*, const float*, const float*, const float*, const float*,
-                           const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*, float*,
-                           float*, const float* /*ray_bias*/, hipStream_t);
-void n3dt_launch_train_bwd(const N3dtGeom*, const N3dtMlpParams*, const N3dtMlpGrads*, const float*, const float*, const float*,
-                           const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
-                           const float*, const float*, const float*, const float*, const float*, float*, float*, float* /*d_Kinv*/,
-                           float* /*d_xy*/, float*, float* /*d_ray_bias*/, hipStream_t);
-size_t n3dt_train16_saved_bytes(const N3dtGeom*);
-size_t n3dt_train16_ws_bytes(const N3dtGeom*);
-void n3dt_launch_train16_fwd(const N3dtGeom*, const N3dtMlpParams*, const void*, const float*, const float*, const float*, const float*,
-                             const float*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
-                             float*, void*, void*, const float* /*ray_bias*/, hipStream_t);
-void n3dt_launch_train16_bwd(const N3dtGeom*, const N3dtMlpParams*, const N3dtMlpGrads*, const float*, const float*, const float*,
-                             const float*, const float*, const float*, const float*, const void*, float*, float*, float*, float*,
-                             const float*, const float*, const float*, const float*, const float*, float*, float*, float* /*d_Kinv*/,
-                             float* /*d_xy*/, void*, float* /*d_ray_bias*/, hipStream_t);
-void n3dt_launch_img_to_uint8(int, int, const float*, unsigned char*, hipStream_t);
-void n3dt_launch_loss_fwd(int, int, const float*, const float*, const float*, const float*, float, float*, float*, hipStream_t);
-void n3dt_launch_loss_bwd(int, int, const float*, const float*, const float*, const float*, float, const float*, const float*, const float*, float*,
-                          float*, hipStream_t);
-size_t n3dt_nr_train_saved_floats(const N3dtGeom*, int);
-size_t n3dt_nr_train_ws_floats(const N3dtGeom*, int);
-void n3dt_launch_nr_train_fwd(const N3dtGeom*, int, const N3dtRenderParams*, const float*, float*, float*, float*, int, hipStream_t);
-void n3dt_launch_nr_bwd(const N3dtGeom*, int, const N3dtRenderParams*, const N3dtRenderGrads*, const float*, const float*, const float*,
-                        float*, float*, int, hipStream_t);
-void n3dt_launch_neural_render(const N3dtGeom*, int, int, const N3dtRenderParams*, const float*, float*, float*, int, hipStream_t);
-void n3dt_launch_feat_to_rgb0(int, int, const float*, const float*, const float*, float*, hipStream_t);
-void n3dt_launch_neural_render16(const N3dtGeom*, int, int, const N3dtRenderParams*, const void*, const float*, float*, float*, hipStream_t);
-void n3dt_launch_stage(const N3dtStageCopy*, hipStream_t);
-size_t n3dt_vgg_packed_layout_bytes(int);
-size_t n3dt_vgg_saved_floats(int);
-size_t n3dt_vgg_ws_floats(int);
-void n3dt_launch_vgg_pack(int, const N3dtVggParams*, void*, hipStream_t);
-void n3dt_launch_vgg_fwd(int, int, int, const void*, const float*, const float*, const float*, float, float*, void*, void*, hipStream_t);
-void n3dt_launch_vgg_bwd(int, int, int, const void*, const float*, const float*, const void*, float*, void*, hipStream_t);
-void n3dt_launch_vgg_conv_stage(int, const void*, int, int, int, int, int, const float*, const float*, float*, int, hipStream_t);
-size_t n3dt_a2s_saved_floats(int);
-size_t n3dt_a2s_ws_floats(int);
-void n3dt_launch_a2s_fwd(int, const N3dtA2sParams*, const float*, const float* const[3], float*, void*, void*, hipStream_t);
-void n3dt_launch_a2s_bwd(int, const N3dtA2sParams*, const float*, const void*, float*, void*, hipStream_t);
-void n3dt_launch_flat_adam(const void*, const void*, int, const void*, int, void*, hipStream_t);
-void n3dt_launch_flat_adam_guarded(const void*, const void*, int, const void*, int, void*, void*, void*, hipStream_t);
-size_t n3dt_eval_metrics_ws_bytes(int, int, int);
-void n3dt_launch_eval_metrics(int, int, int, const float*, const float*, double*, double*, void*, hipStream_t);
-size_t n3dt_lpips_packed_layout_bytes(void);
-size_t n3dt_lpips_ws_bytes(int, int, int);
-void n3dt_launch_lpips_pack(const N3dtLpipsParams*, void*, hipStream_t);
-void n3dt_launch_lpips(int, int, int, int, const void*, const float*, const float*, double*, double*, void*, hipStream_t);
-size_t n3dt_mel_ws_bytes(void);
-void n3dt_launch_mel_spectrogram(const MelSignal*, long long, int, const float*, const double*, void*, long long, int, void*, hipStream_t);
-void n3dt_launch_mel_windows(const void*, long long, long long, int, const int*, int, float*, hipStream_t);
-size_t n3dt_syncnet_packed_layout_bytes(void);
-size_t n3dt_syncnet_ws_bytes(int);
-float* n3dt_syncnet_ws_faces(int, void*);
-void n3dt_launch_syncnet_pack(const N3dtSyncnetParams*, void*, hipStream_t);
-void n3dt_launch_syncnet_faces(int, int, int, const float*, const int*, int, float*, hipStream_t);
-void n3dt_launch_syncnet_fwd(int, const void*, const float*, const float*, float*, float*, double*, void*, hipStream_t);
-void n3dt_launch_syncnet_block(int, int, const void*, const float*, float*, void*, hipStream_t);
-}
-
 static thread_local char g_err[256] = "";
 
-static int fail(int code, const char* msg) {
-    snprintf(g_err, sizeof(g_err), "%s", msg);
+// the one place a refusal's text is formed: writes the calling thread's n3dt_last_error() string and returns `code`
+__attribute__((format(printf, 2, 3))) static int failf(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
     return code;
 }
+static int fail(int code, const char* msg) { return failf(code, "%s", msg); }
 
 static int check_hip(const char* where) {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
-        return N3DT_EHIP;
-    }
-    return N3DT_OK;
+    return e == hipSuccess ? N3DT_OK : failf(N3DT_EHIP, "%s: %s", where, hipGetErrorString(e));
 }
 
 static int check_geom(const N3dtGeom* g, int precision) {
@@ -140,10 +50,7 @@ static int check_geom(const N3dtGeom* g, int precision) {
 }
 // include_vd: the per-ray bias must come with the flag, and only with it
 static int check_ray_bias(const N3dtGeom* g, const void* ray_bias, const char* who) {
-    if ((g->vd_dim > 0) != (ray_bias != nullptr)) {
-        snprintf(g_err, sizeof(g_err), "%s: the per-ray bias must be given iff vd_dim > 0", who);
-        return N3DT_EINVAL;
-    }
+    if ((g->vd_dim > 0) != (ray_bias != nullptr)) return failf(N3DT_EINVAL, "%s: the per-ray bias must be given iff vd_dim > 0", who);
     return N3DT_OK;
 }
 
@@ -479,19 +386,10 @@ extern "C" int n3dt_neural_render_fwd16_reuse(const N3dtGeom* g, int nb, int pre
 
 // ---- VGG16 perceptual term (csrc/vgg_loss.hip) ----
 static int check_vgg(const char* who, int batch, int img_size, int precision) {
-    char m[160];
-    if (precision != N3DT_F32 && precision != N3DT_BF16) {
-        snprintf(m, sizeof(m), "%s: unsupported precision %d (N3DT_F32 or N3DT_BF16)", who, precision);
-        return fail(N3DT_EINVAL, m);
-    }
-    if (batch < 1 || batch > 64) {
-        snprintf(m, sizeof(m), "%s: batch %d outside 1..64", who, batch);
-        return fail(N3DT_EINVAL, m);
-    }
-    if (img_size < 16 || img_size > 2048) {
-        snprintf(m, sizeof(m), "%s: img_size %d outside 16..2048", who, img_size);
-        return fail(N3DT_EINVAL, m);
-    }
+    if (precision != N3DT_F32 && precision != N3DT_BF16)
+        return failf(N3DT_EINVAL, "%s: unsupported precision %d (N3DT_F32 or N3DT_BF16)", who, precision);
+    if (batch < 1 || batch > 64) return failf(N3DT_EINVAL, "%s: batch %d outside 1..64", who, batch);
+    if (img_size < 16 || img_size > 2048) return failf(N3DT_EINVAL, "%s: img_size %d outside 16..2048", who, img_size);
     return N3DT_OK;
 }
 
@@ -548,7 +446,6 @@ extern "C" int n3dt_vgg_conv_stage(int precision, const void* packed, int layer,
     static const char* who = "n3dt_vgg_conv_stage";
     int rc = check_vgg(who, 1, 224, precision);
     if (rc) return rc;
-    char msg[160];
     const char* what = nullptr;
     if (layer < 0 || layer >= N3DT_VGG_CONVS) what = "layer outside 0..9";
     else if (dgrad != 0 && dgrad != 1) what = "direction must be 0 (forward) or 1 (dgrad)";
@@ -559,27 +456,14 @@ extern "C" int n3dt_vgg_conv_stage(int precision, const void* packed, int layer,
     else if (gate && !dgrad) what = "a gate goes with dgrad only";
     else if ((((size_t)in) | ((size_t)out) | ((size_t)gate)) & 15) what = "in, gate and out must be 16-byte aligned";
     else if (((size_t)packed) & 255) what = "packed must be 256-byte aligned";
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_vgg_conv_stage(precision, packed, layer, dgrad, n_img, H, W, in, gate, out, out_pad, (hipStream_t)stream);
     return check_hip(who);
 }
 
 // ---- Audio2style encoder (csrc/audio_lstm.hip) ----
-static int a2s_fail(const char* who, const char* what) {
-    char m[200];
-    snprintf(m, sizeof(m), "%s: %s", who, what);
-    return fail(N3DT_EINVAL, m);
-}
-
 static int check_a2s_T(const char* who, int T) {
-    if (T < 1 || T > N3DT_A2S_MAX_T) {
-        char m[160];
-        snprintf(m, sizeof(m), "%s: T = %d outside 1..%d", who, T, N3DT_A2S_MAX_T);
-        return fail(N3DT_EINVAL, m);
-    }
+    if (T < 1 || T > N3DT_A2S_MAX_T) return failf(N3DT_EINVAL, "%s: T = %d outside 1..%d", who, T, N3DT_A2S_MAX_T);
     return N3DT_OK;
 }
 
@@ -587,40 +471,25 @@ static bool a2s_aligned(const void* q) { return (((size_t)q) & 15) == 0; }
 
 // every parameter pointer non-NULL and 16-byte aligned (the step kernels read W_hh with 16-byte loads)
 static int check_a2s_params(const char* who, const N3dtA2sParams* p) {
-    if (!p) return a2s_fail(who, "params is NULL");
+    if (!p) return failf(N3DT_EINVAL, "%s: params is NULL", who);
     static const char* names[4] = {"w_ih", "w_hh", "b_ih", "b_hh"};
     const float* const* lstm[4] = {p->w_ih, p->w_hh, p->b_ih, p->b_hh};
-    char m[96];
     for (int a = 0; a < 4; ++a)
-        for (int k = 0; k < 4; ++k) {
-            if (!lstm[a][k] || !a2s_aligned(lstm[a][k])) {
-                snprintf(m, sizeof(m), "params->%s[%d] is NULL or not 16-byte aligned", names[a], k);
-                return a2s_fail(who, m);
-            }
-        }
+        for (int k = 0; k < 4; ++k)
+            if (!lstm[a][k] || !a2s_aligned(lstm[a][k]))
+                return failf(N3DT_EINVAL, "%s: params->%s[%d] is NULL or not 16-byte aligned", who, names[a], k);
     for (int k = 0; k < 3; ++k) {
-        if (!p->lin_w[k] || !a2s_aligned(p->lin_w[k])) {
-            snprintf(m, sizeof(m), "params->lin_w[%d] is NULL or not 16-byte aligned", k);
-            return a2s_fail(who, m);
-        }
-        if (!p->lin_b[k] || !a2s_aligned(p->lin_b[k])) {
-            snprintf(m, sizeof(m), "params->lin_b[%d] is NULL or not 16-byte aligned", k);
-            return a2s_fail(who, m);
-        }
+        if (!p->lin_w[k] || !a2s_aligned(p->lin_w[k]))
+            return failf(N3DT_EINVAL, "%s: params->lin_w[%d] is NULL or not 16-byte aligned", who, k);
+        if (!p->lin_b[k] || !a2s_aligned(p->lin_b[k]))
+            return failf(N3DT_EINVAL, "%s: params->lin_b[%d] is NULL or not 16-byte aligned", who, k);
     }
     return N3DT_OK;
 }
 
 static int check_a2s_buf(const char* who, const char* name, const void* q, size_t have, size_t need) {
-    char m[160];
-    if (!q || !a2s_aligned(q)) {
-        snprintf(m, sizeof(m), "%s is NULL or not 16-byte aligned", name);
-        return a2s_fail(who, m);
-    }
-    if (have < need) {
-        snprintf(m, sizeof(m), "%s_bytes = %zu, %zu needed", name, have, need);
-        return a2s_fail(who, m);
-    }
+    if (!q || !a2s_aligned(q)) return failf(N3DT_EINVAL, "%s: %s is NULL or not 16-byte aligned", who, name);
+    if (have < need) return failf(N3DT_EINVAL, "%s: %s_bytes = %zu, %zu needed", who, name, have, need);
     return N3DT_OK;
 }
 
@@ -640,11 +509,11 @@ extern "C" int n3dt_a2s_fwd(int T, const N3dtA2sParams* p, const float* mel, con
     int rc = check_a2s_T(who, T);
     if (!rc) rc = check_a2s_params(who, p);
     if (rc) return rc;
-    if (!mel || !a2s_aligned(mel)) return a2s_fail(who, "mel is NULL or not 16-byte aligned");
-    if (!out) return a2s_fail(who, "out is NULL");
+    if (!mel || !a2s_aligned(mel)) return failf(N3DT_EINVAL, "%s: mel is NULL or not 16-byte aligned", who);
+    if (!out) return failf(N3DT_EINVAL, "%s: out is NULL", who);
     const float* masks[3] = {mask1, mask2, mask3};
     if ((mask1 != nullptr) != (mask2 != nullptr) || (mask1 != nullptr) != (mask3 != nullptr))
-        return a2s_fail(who, "mask1, mask2 and mask3 must be all given or all NULL");
+        return failf(N3DT_EINVAL, "%s: mask1, mask2 and mask3 must be all given or all NULL", who);
     if ((rc = check_a2s_buf(who, "saved", saved, saved_bytes, n3dt_a2s_saved_floats(T) * sizeof(float)))) return rc;
     if ((rc = check_a2s_buf(who, "ws", ws, ws_bytes, n3dt_a2s_ws_floats(T) * sizeof(float)))) return rc;
     n3dt_launch_a2s_fwd(T, p, mel, masks, out, saved, ws, (hipStream_t)stream);
@@ -657,8 +526,8 @@ extern "C" int n3dt_a2s_bwd(int T, const N3dtA2sParams* p, const float* g_out, c
     int rc = check_a2s_T(who, T);
     if (!rc) rc = check_a2s_params(who, p);
     if (rc) return rc;
-    if (!g_out) return a2s_fail(who, "g_out is NULL");
-    if (!grad_arena || !a2s_aligned(grad_arena)) return a2s_fail(who, "grad_arena is NULL or not 16-byte aligned");
+    if (!g_out) return failf(N3DT_EINVAL, "%s: g_out is NULL", who);
+    if (!grad_arena || !a2s_aligned(grad_arena)) return failf(N3DT_EINVAL, "%s: grad_arena is NULL or not 16-byte aligned", who);
     if ((rc = check_a2s_buf(who, "saved", saved, saved_bytes, n3dt_a2s_saved_floats(T) * sizeof(float)))) return rc;
     if ((rc = check_a2s_buf(who, "ws", ws, ws_bytes, n3dt_a2s_ws_floats(T) * sizeof(float)))) return rc;
     n3dt_launch_a2s_bwd(T, p, g_out, saved, grad_arena, ws, (hipStream_t)stream);
@@ -685,7 +554,6 @@ extern "C" size_t n3dt_flat_adam_guard_bytes(void) { return sizeof(N3dtAdamGuard
 extern "C" int n3dt_flat_adam_guarded_step(const void* tensor_table, const void* chunk_table, int n_chunks, const void* group_table,
                                            int n_groups, void* step_counter, void* partials, void* guard, void* stream) {
     static const char* who = "n3dt_flat_adam_guarded_step";
-    char msg[160];
     const char* what = nullptr;
     if (!tensor_table || !chunk_table || !group_table || !step_counter) what = "NULL table";
     else if (!partials || !guard) what = "NULL partials or guard record";
@@ -694,10 +562,7 @@ extern "C" int n3dt_flat_adam_guarded_step(const void* tensor_table, const void*
     else if ((((size_t)tensor_table) | ((size_t)chunk_table) | ((size_t)group_table)) & 7 || ((size_t)step_counter) & 3)
         what = "tables must be 8-byte aligned, the step counter 4-byte aligned";
     else if (((size_t)partials) & 7 || ((size_t)guard) & 3) what = "partials must be 8-byte aligned, the guard record 4-byte aligned";
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_flat_adam_guarded(tensor_table, chunk_table, n_chunks, group_table, n_groups, step_counter, partials, guard,
                                   (hipStream_t)stream);
     return check_hip(who);
@@ -714,7 +579,7 @@ static const char* eval_metrics_geometry(int n_images, int height, int width) {
 extern "C" size_t n3dt_eval_metrics_workspace_bytes(int n_images, int height, int width) {
     const char* what = eval_metrics_geometry(n_images, height, width);
     if (what) {
-        snprintf(g_err, sizeof(g_err), "n3dt_eval_metrics_workspace_bytes: %s", what);
+        (void)failf(N3DT_EINVAL, "n3dt_eval_metrics_workspace_bytes: %s", what);
         return 0;
     }
     return n3dt_eval_metrics_ws_bytes(n_images, height, width);
@@ -723,7 +588,6 @@ extern "C" size_t n3dt_eval_metrics_workspace_bytes(int n_images, int height, in
 extern "C" int n3dt_eval_metrics(int n_images, int height, int width, const float* pred, const float* gt, double* ssim, double* psnr,
                                  void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "n3dt_eval_metrics";
-    char msg[160];
     const char* what = eval_metrics_geometry(n_images, height, width);
     if (!what) {
         if (!pred || !gt || !ssim || !psnr || !workspace) what = "NULL pointer";
@@ -731,10 +595,7 @@ extern "C" int n3dt_eval_metrics(int n_images, int height, int width, const floa
         else if ((((size_t)pred) | ((size_t)gt)) & 3) what = "pred and gt must be 4-byte aligned";
         else if (workspace_bytes < n3dt_eval_metrics_ws_bytes(n_images, height, width)) what = "workspace too small";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_eval_metrics(n_images, height, width, pred, gt, ssim, psnr, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
@@ -761,7 +622,7 @@ extern "C" int n3dt_lpips_pack(const N3dtLpipsParams* p, void* packed, void* str
 extern "C" size_t n3dt_lpips_workspace_bytes(int batch, int height, int width) {
     const char* what = lpips_geometry(batch, height, width);
     if (what) {
-        snprintf(g_err, sizeof(g_err), "n3dt_lpips_workspace_bytes: %s", what);
+        (void)failf(N3DT_EINVAL, "n3dt_lpips_workspace_bytes: %s", what);
         return 0;
     }
     return n3dt_lpips_ws_bytes(batch, height, width);
@@ -770,7 +631,6 @@ extern "C" size_t n3dt_lpips_workspace_bytes(int batch, int height, int width) {
 extern "C" int n3dt_lpips(int batch, int height, int width, int input_mode, const void* packed, const float* pred, const float* gt,
                           double* out, double* layers, void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "n3dt_lpips";
-    char msg[160];
     const char* what = lpips_geometry(batch, height, width);
     if (!what) {
         if (input_mode != N3DT_LPIPS_REFERENCE && input_mode != N3DT_LPIPS_STANDARD) what = "input_mode must be N3DT_LPIPS_REFERENCE or N3DT_LPIPS_STANDARD";
@@ -780,10 +640,7 @@ extern "C" int n3dt_lpips(int batch, int height, int width, int input_mode, cons
         else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
         else if (workspace_bytes < n3dt_lpips_ws_bytes(batch, height, width)) what = "workspace too small";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_lpips(batch, height, width, input_mode, packed, pred, gt, out, layers, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
@@ -795,7 +652,6 @@ extern "C" int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t
                                     int64_t first_frame, int n_frames, const float* basis, const double* table, void* out, int64_t out_ld,
                                     int out_is_f64, void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "n3dt_mel_spectrogram";
-    char msg[200];
     const char* what = nullptr;
     if (n_samples < MEL_MIN_SAMPLES) what = "n_samples must be >= 401 (the reflect padding of 400 needs 401 samples)";
     else if (n_frames < 1 || n_frames > MEL_MAX_FRAMES) what = "n_frames outside 1..2^24";
@@ -809,10 +665,7 @@ extern "C" int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t
             what = "wav, prev_sample, basis, out and the workspace must be 4-byte aligned";
         else if (workspace_bytes < n3dt_mel_ws_bytes()) what = "workspace too small";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     MelSignal sig;
     sig.wav = wav;
     sig.prev = prev_sample;
@@ -826,16 +679,12 @@ extern "C" int n3dt_mel_spectrogram(int64_t n_samples, const float* wav, int64_t
 extern "C" int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int mel_is_f64, int n_windows, const int32_t* start, float* out,
                                 void* stream) {
     static const char* who = "n3dt_mel_windows";
-    char msg[160];
     const char* what = nullptr;
     if (T < 1 || mel_ld < T || mel_ld > ((int64_t)1 << 40)) what = "need 1 <= T <= mel_ld";
     else if (n_windows < 1) what = "n_windows must be >= 1";
     else if (!mel || !start || !out) what = "NULL pointer";
     else if ((((size_t)mel) & (mel_is_f64 ? 7 : 3)) || (((size_t)start) | ((size_t)out)) & 3) what = "mel, start or out misaligned";
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_mel_windows(mel, T, mel_ld, mel_is_f64, start, n_windows, out, (hipStream_t)stream);
     return check_hip(who);
 }
@@ -865,7 +714,7 @@ extern "C" int n3dt_syncnet_pack(const N3dtSyncnetParams* p, void* packed, void*
 extern "C" size_t n3dt_syncnet_workspace_bytes(int n) {
     const char* what = syncnet_windows(n);
     if (what) {
-        snprintf(g_err, sizeof(g_err), "n3dt_syncnet_workspace_bytes: %s", what);
+        (void)failf(N3DT_EINVAL, "n3dt_syncnet_workspace_bytes: %s", what);
         return 0;
     }
     return n3dt_syncnet_ws_bytes(n);
@@ -874,17 +723,13 @@ extern "C" size_t n3dt_syncnet_workspace_bytes(int n) {
 extern "C" int n3dt_syncnet_face_windows(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes,
                                          float* face_windows, void* stream) {
     static const char* who = "n3dt_syncnet_face_windows";
-    char msg[160];
     const char* what = syncnet_windows(n);
     if (!what) what = syncnet_frames(n, height, width, frames, boxes, n_boxes);
     if (!what) {
         if (!face_windows) what = "NULL pointer";
         else if (((size_t)face_windows) & 15) what = "face_windows must be 16-byte aligned";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_syncnet_faces(n, height, width, frames, boxes, n_boxes == 1 ? 0 : 4, face_windows, (hipStream_t)stream);
     return check_hip(who);
 }
@@ -893,7 +738,6 @@ extern "C" int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_wind
                                 const int32_t* boxes, int n_boxes, int height, int width, float* audio_emb, float* face_emb, double* cosv,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     static const char* who = "n3dt_syncnet_fwd";
-    char msg[160];
     const char* what = syncnet_windows(n);
     if (!what) {
         if ((face_windows != nullptr) == (frames != nullptr)) what = "give exactly one of face_windows and frames";
@@ -907,10 +751,7 @@ extern "C" int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_wind
         else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
         else if (workspace_bytes < n3dt_syncnet_ws_bytes(n)) what = "workspace too small";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     if (frames) {
         float* faces = n3dt_syncnet_ws_faces(n, workspace);
         n3dt_launch_syncnet_faces(n, height, width, frames, boxes, n_boxes == 1 ? 0 : 4, faces, (hipStream_t)stream);
@@ -923,7 +764,6 @@ extern "C" int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_wind
 extern "C" int n3dt_syncnet_block(int block, int n, const void* packed, const float* in, float* out, void* workspace, size_t workspace_bytes,
                                   void* stream) {
     static const char* who = "n3dt_syncnet_block";
-    char msg[160];
     const char* what = syncnet_windows(n);
     if (!what) {
         if (block < 0 || block >= SN_BLOCKS) what = "block outside 0..30";
@@ -932,10 +772,7 @@ extern "C" int n3dt_syncnet_block(int block, int n, const void* packed, const fl
         else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
         else if (workspace_bytes < n3dt_syncnet_ws_bytes(n)) what = "workspace too small";
     }
-    if (what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(N3DT_EINVAL, msg);
-    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_syncnet_block(block, n, packed, in, out, workspace, (hipStream_t)stream);
     return check_hip(who);
 }

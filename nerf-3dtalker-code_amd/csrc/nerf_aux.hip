@@ -2,6 +2,7 @@
 // the per-ray head (block combine + RGB_layer_2 + background merge).
 #include "n3dt_device.h"
 #include "n3dt_layout.h"
+#include "n3dt_launch.h"
 
 // ---------------------------------------------------------------------------------------------
 // Weight packing.  Logical matrices and their sources: n3dt_layout.h.

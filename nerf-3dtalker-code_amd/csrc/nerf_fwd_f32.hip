@@ -12,6 +12,7 @@
 // NetWorks/models.py:62-87 (MLP), NetWorks/utils.py:268-309 (compositing, per-block part).
 #include "n3dt_device.h"
 #include "n3dt_layout.h"
+#include "n3dt_launch.h"
 
 #define F32_BS 16                 // samples per wave
 #define F32_WAVES 4               // waves per workgroup

@@ -18,6 +18,7 @@
 // lanes -> weights; the RGB_layer_1 activations are weighted and reduced over the samples with a
 // 5-step butterfly, so the only HBM traffic per block is one 196-float partial.
 #include "x16_core.h"
+#include "n3dt_launch.h"
 
 
 #ifndef X16_SAVE_DEPTH

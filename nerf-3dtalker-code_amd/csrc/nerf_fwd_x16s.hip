@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "x16_core.h"
+#include "n3dt_launch.h"
 
 #define XS_WAVES 4
 typedef X16<N3DT_BF16> XsT;

@@ -9,6 +9,7 @@
 // v_mfma_f32_32x32x2_f32 (exact fp32); pixel-shuffle is a store-address permutation in the
 // second PSU GEMM's epilogue; the RGB skip pyramid stays planar [nb,3,h,w] like the output.
 #include "n3dt_device.h"
+#include "n3dt_launch.h"
 
 #define EPI_LRELU 0   // Y = lrelu(acc + b)
 #define EPI_PSU 1     // Y(pixel-shuffled) = lrelu(acc + b) + X.repeat(1,4,1,1)

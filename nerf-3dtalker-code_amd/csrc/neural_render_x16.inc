@@ -674,6 +674,7 @@ static void run_x16(const N3dtGeom* g, int nb, const N3dtRenderParams* p, const 
 // backward needs kept (nr_train16.h): t1 and the y planes from the block kernel's SAVE epilogue, every level's activation
 // map, the sigmoid image.  7 launches + 3 weight packs for three levels (the layered training forward it replaces: 24).
 #include "nr_train16.h"
+#include "n3dt_launch.h"
 size_t nrf_packed_bytes_for(int C, int CO) { return nrf_packed_bytes(C, CO); }
 bool nr16_supported(const N3dtGeom* g) {
     if (g->feat_nc != 256 || g->n_blocks < 1) return false;

@@ -9,6 +9,7 @@
 #include "gemm32.h"
 #include "n3dt_device.h"
 #include "x16_core.h"
+#include "n3dt_launch.h"
 
 // ---- GenSamplePoints ---------------------------------------------------------------------------
 // pts [B,3,Nr,Ns], zvals / z_dists [B,1,Nr,Ns], ray_d [B,3,Nr], ray_l [B,1,Nr]   (any output may be NULL)

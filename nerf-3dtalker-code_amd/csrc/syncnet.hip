@@ -24,6 +24,7 @@
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
 #include "syncnet_core.h"
+#include "n3dt_launch.h"
 
 // ---- packed weights ------------------------------------------------------------------------------------------------------------
 // Per block one B matrix in conv_frag.h's fragment order, [K/16][C_out/32] fragments of 64 lanes x 8 bf16: element e holds

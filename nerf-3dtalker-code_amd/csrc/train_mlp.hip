@@ -11,6 +11,7 @@
 #include "gemm32.h"
 #include "n3dt_device.h"
 #include "n3dt_layout.h"
+#include "n3dt_launch.h"
 
 // diagnostic: dst[r][c] = bf16(src[r][c]) as fp32, for n = rows * cols elements (cols per row, leading dimensions given)
 __global__ void train_round_bf16_kernel(size_t n, int cols, long ld_src, long ld_dst, const float* __restrict__ src, float* __restrict__ dst) {
@@ -627,11 +628,6 @@ __global__ void train_unpack_grads_kernel(N3dtMlpGrads gp, int S, const float* _
 // ---------------------------------------------------------------------------------------------
 // orchestration
 // ---------------------------------------------------------------------------------------------
-extern "C" void n3dt_launch_fold(const N3dtGeom*, const N3dtMlpParams*, const float*, const float*, const float*, float*, int, hipStream_t);
-extern "C" void n3dt_launch_rayfold(const N3dtGeom*, const float*, const float*, hipStream_t);
-extern "C" void n3dt_launch_ray_head(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, int, float*,
-                                     float*, float*, float*, float*, hipStream_t);
-
 static Gemm32 mk(int M, int N, int K, const float* A, long lda, int ak, const float* B, long ldb, int bk, float* C, long ldc) {
     Gemm32 g;
     g.M = M; g.N = N; g.K = K;

@@ -8,6 +8,7 @@
 // Blur :15-18 (kornia filter2d semantics).
 #include "gemm32.h"
 #include "n3dt_device.h"
+#include "n3dt_launch.h"
 
 static inline int nr_ch(int C, int i) {
     int v = C >> i;
@@ -62,8 +63,6 @@ static NrWs nr_ws_layout(const N3dtGeom* g, int nb) {
 
 // (the sizes cover both the layered layouts above and the fused mixed-precision path's, nr_train16.h: the size queries of the
 // C ABI do not take the precision)
-extern "C" size_t n3dt_nr_train16_saved_bytes(const N3dtGeom* g, int nb);
-extern "C" size_t n3dt_nr_train16_ws_bytes(const N3dtGeom* g, int nb);
 extern "C" size_t n3dt_nr_train_saved_floats(const N3dtGeom* g, int nb) {
     const size_t a = nr_saved_layout(g, nb).total, b = (n3dt_nr_train16_saved_bytes(g, nb) + 3) / 4;
     return a > b ? a : b;
@@ -549,10 +548,6 @@ static void set_grad_split(Gemm32& q, long K) {
     q.accumulate = q.split_k <= 1 ? 1 : 0;
 }
 
-extern "C" void n3dt_launch_conv1x1_bf16(int, int, int, const void*, int, const float*, const float*, float, void*, hipStream_t);
-extern "C" void n3dt_launch_conv1x1_bwd_bf16(int, int, int, const void*, const float*, int, const void*, void*, hipStream_t);
-extern "C" void n3dt_launch_chw_to_hwc(int, int, const float*, float*, hipStream_t);
-
 // input gradient of a 1x1 conv: dx[M][Nin] = dy[M][Kout] . W[Kout][Nin], then * lrelu'(gate) (mode 1) or += into dx (mode 2).
 // fp32: the generic GEMM with its k-major B operand; bf16 maps: W is transposed into `wt` ([Nin][Kout], a few hundred KB) and
 // the renderer's 16-bit GEMM runs with a gate / add epilogue.
@@ -884,10 +879,6 @@ static void nr_train_fwd(const N3dtGeom* g, int nb, const N3dtRenderParams* p, c
 // three weight transposes (one pack launch per block instead).
 #include "nr_train16.h"
 #include "dw_rowmajor.h"
-extern "C" void n3dt_launch_nr_train16_fwd(const N3dtGeom*, int, const N3dtRenderParams*, const float*, float*, unsigned char*, unsigned char*,
-                                           hipStream_t);
-extern "C" void n3dt_launch_gemm_regions_bf16(int, int, int, int, const void* const*, const int*, const int*, const float*, const void*, void*,
-                                              hipStream_t);
 
 // the three transposed / permuted fp32 matrices of every block (nr_train16.h: Nr16Wt); blockIdx.y = block
 struct Nr16PackArgs {

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "x16_core.h"
+#include "n3dt_launch.h"
 
 #define T16_DZ_TILES 103  // per block: [dG (6) | d sigma row (1)] | dZ0 .. dZ7 (12 each), tile offset of dZ_l = 7 + 12 l
 #define T16_BWD_PIECES (168 + 7 * 288)
@@ -27,12 +28,6 @@
 #define T16_BWD_PIECES_CAM (T16_BWD_PIECES + 2 * 48)
 #define T16_BWD_NCHUNK_CAM (T16_BWD_PIECES_CAM / X16_CH)
 #define T16_BWD_WAVES 4
-
-extern "C" void n3dt_launch_nerf_fwd_x16_train(const N3dtGeom*, const void*, const float*, const float*, const float*, const float*,
-                                               const float*, const float*, float*, float*, void*, void*, float*, void*, hipStream_t);
-extern "C" void n3dt_launch_small_gemm(int, int, int, const float*, long, long, const float*, long, long, float*, long, int, hipStream_t);
-extern "C" void n3dt_launch_ray_head_rec(const N3dtGeom*, int, int, const float*, const float*, const float*, const float*, float*,
-                                         float*, float*, float*, float*, float*, hipStream_t);
 
 #define DW_XCDS 8           // partial buffers per weight-gradient launch (indexed by the hardware XCC id, masked to 0..7)
 #define DW_PACE_SLOTS 4096  // per product: [slice][2], slices <= 2048
@@ -1123,8 +1118,7 @@ static void launch_dz_rowsum(const N3dtGeom* g, const unsigned char* dzT, size_t
 // ---------------------------------------------------------------------------------------------
 // orchestration
 // ---------------------------------------------------------------------------------------------
-extern "C" int n3dt_prof_span_begin(hipStream_t);   // bench.py's measurement hook (n3dt_api.hip)
-extern "C" void n3dt_prof_span_end(int, hipStream_t);
+// (n3dt_prof_span_begin / _end below: bench.py's measurement hook, n3dt_api.hip)
 extern "C" void n3dt_launch_train16_fwd(const N3dtGeom* g, const N3dtMlpParams* p, const void* packed_bf16, const float* tail,
                                         const float* xy, const float* R, const float* T, const float* Kinv, const float* shape,
                                         const float* appea, const float* audio, const float* t_rand, const float* bg_featmap,

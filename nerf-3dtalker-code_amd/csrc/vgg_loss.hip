@@ -25,6 +25,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "n3dt_launch.h"
 
 #define VGG_L1_BLOCKS 256
 #define VGG_S 224

@@ -98,38 +98,103 @@ class RenderParams(ctypes.Structure):
     ]
 
 
-EXPORTS = [
-    "n3dt_abi_version", "n3dt_last_error", "n3dt_mlp_packed_bytes", "n3dt_mlp_pack",
-    "n3dt_render_workspace_bytes", "n3dt_render_fwd", "n3dt_neural_render_workspace_bytes",
-    "n3dt_neural_render_fwd", "n3dt_chw_to_hwc", "n3dt_prof_enable", "n3dt_prof_collect",
-    "n3dt_render_train_saved_bytes", "n3dt_render_train_workspace_bytes", "n3dt_render_train_fwd", "n3dt_render_bwd",
-    "n3dt_render_bwd_cam",
-    "n3dt_neural_render_train_saved_bytes", "n3dt_neural_render_train_workspace_bytes",
-    "n3dt_neural_render_train_fwd", "n3dt_neural_render_bwd", "n3dt_loss_fwd", "n3dt_loss_bwd", "n3dt_fine_sample",
-    "n3dt_img_to_uint8", "n3dt_sample_points", "n3dt_embed", "n3dt_mlp_points_workspace_bytes", "n3dt_mlp_points", "n3dt_composite",
-    "n3dt_ray_vd_bias", "n3dt_embed_freqs",
-    "n3dt_neural_render_pack", "n3dt_neural_render_fwd_reuse", "n3dt_stage_inputs", "n3dt_graph_begin", "n3dt_graph_end", "n3dt_graph_launch", "n3dt_graph_destroy",
-    "n3dt_vgg_packed_bytes", "n3dt_vgg_pack", "n3dt_vgg_saved_bytes", "n3dt_vgg_workspace_bytes", "n3dt_vgg_loss_fwd", "n3dt_vgg_loss_bwd", "n3dt_vgg_conv_stage",
-    "n3dt_a2s_saved_bytes", "n3dt_a2s_workspace_bytes", "n3dt_a2s_fwd", "n3dt_a2s_bwd",
-    "n3dt_flat_adam_record_bytes", "n3dt_flat_adam_step",
-    "n3dt_render_fwd16", "n3dt_neural_render_fwd16_reuse", "n3dt_feat_to_rgb0",
-    "n3dt_x16_pack_probe", "n3dt_x16_pe_probe",
-    "n3dt_eval_metrics_workspace_bytes", "n3dt_eval_metrics",
-    "n3dt_lpips_packed_bytes", "n3dt_lpips_pack", "n3dt_lpips_workspace_bytes", "n3dt_lpips",
-    "n3dt_mel_workspace_bytes", "n3dt_mel_spectrogram", "n3dt_mel_windows",
-    "n3dt_syncnet_packed_bytes", "n3dt_syncnet_pack", "n3dt_syncnet_workspace_bytes", "n3dt_syncnet_face_windows", "n3dt_syncnet_fwd",
-    "n3dt_syncnet_block",
-]
-
-# the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
-GUARD_EXPORTS = ["n3dt_flat_adam_guard_bytes", "n3dt_flat_adam_guarded_step"]
-
 STAGE_MAX = 12
 
 
 class Stage(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p * STAGE_MAX), ("dst", ctypes.c_void_p * STAGE_MAX), ("count", ctypes.c_int64 * STAGE_MAX),
                 ("view_dims", ctypes.c_int64 * 3), ("view_strides", ctypes.c_int64 * 3), ("n", ctypes.c_int32)]
+
+
+def _signatures():
+    """name -> (restype, [argtypes]) of every entry point of include/n3dt.h and include/n3dt_flat_adam_guard.h: the one place
+    this package types the C ABI.  A new entry point is one row here (tests/test_host_cpu.py holds every row to the headers'
+    prototypes, argument by argument, so a count such as [vp] * 15 cannot drift)."""
+    vp, sz, ci, i64, f32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    gp, mp, rp = ctypes.POINTER(Geom), ctypes.POINTER(MlpParams), ctypes.POINTER(RenderParams)
+    a2p = ctypes.POINTER(A2sParams)
+    return {
+        "n3dt_abi_version": (ci, []),
+        "n3dt_last_error": (ctypes.c_char_p, []),
+        "n3dt_mlp_packed_bytes": (sz, [gp, ci]),
+        "n3dt_mlp_pack": (ci, [gp, ci, mp, vp, vp]),
+        "n3dt_render_workspace_bytes": (sz, [gp, ci]),
+        "n3dt_render_fwd": (ci, [gp, ci, vp, mp] + [vp] * 15 + [vp, sz, vp]),
+        "n3dt_neural_render_workspace_bytes": (sz, [gp, ci]),
+        "n3dt_neural_render_fwd": (ci, [gp, ci, ci, rp, vp, vp, vp, sz, vp]),
+        "n3dt_chw_to_hwc": (ci, [ci, ci, vp, vp, vp]),
+        "n3dt_prof_enable": (ci, [ci]),
+        "n3dt_prof_collect": (ci, [ctypes.POINTER(f32), ci, ctypes.POINTER(ci)]),
+        "n3dt_render_train_saved_bytes": (sz, [gp]),
+        "n3dt_render_train_workspace_bytes": (sz, [gp]),
+        "n3dt_render_train_fwd": (ci, [gp, ci, vp, mp] + [vp] * 14 + [vp, sz, vp, sz, vp]),
+        "n3dt_render_bwd": (ci, [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 12 + [vp, sz, vp]),
+        # n3dt_render_bwd + d_Kinv, d_xy behind d_T
+        "n3dt_render_bwd_cam": (ci, [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 14 + [vp, sz, vp]),
+        "n3dt_neural_render_train_saved_bytes": (sz, [gp, ci]),
+        "n3dt_neural_render_train_workspace_bytes": (sz, [gp, ci]),
+        "n3dt_neural_render_train_fwd": (ci, [gp, ci, ci, rp, vp, vp, vp, sz, vp, sz, vp]),
+        "n3dt_neural_render_bwd": (ci, [gp, ci, ci, rp, rp, vp, vp, vp, sz, vp, vp, sz, vp]),
+        "n3dt_loss_fwd": (ci, [ci, ci, vp, vp, vp, vp, f32, vp, vp, vp]),
+        "n3dt_loss_bwd": (ci, [ci, ci, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
+        "n3dt_fine_sample": (ci, [gp, ci, vp, vp, vp, vp, vp, vp]),
+        "n3dt_img_to_uint8": (ci, [ci, ci, vp, vp, vp]),
+        "n3dt_sample_points": (ci, [gp] + [vp] * 10 + [vp]),
+        "n3dt_embed": (ci, [ci, sz, vp, vp, vp]),
+        "n3dt_mlp_points_workspace_bytes": (sz, [gp, sz]),
+        "n3dt_mlp_points": (ci, [gp, sz, mp] + [vp] * 5 + [vp, sz, vp]),
+        "n3dt_composite": (ci, [ci, ci, ci, ci] + [vp] * 8 + [vp]),
+        "n3dt_ray_vd_bias": (ci, [gp, vp, i64, vp, vp, vp, vp, vp]),
+        "n3dt_embed_freqs": (ci, [ci, sz, ci, vp, vp, vp]),
+        "n3dt_neural_render_pack": (ci, [gp, ci, ci, rp, vp, sz, vp]),
+        "n3dt_neural_render_fwd_reuse": (ci, [gp, ci, ci, rp, vp, vp, vp, sz, vp]),
+        "n3dt_stage_inputs": (ci, [ctypes.POINTER(Stage), vp]),
+        "n3dt_graph_begin": (ci, [vp]),
+        "n3dt_graph_end": (ci, [vp, ctypes.POINTER(vp)]),
+        "n3dt_graph_launch": (ci, [vp, vp]),
+        "n3dt_graph_destroy": (ci, [vp]),
+        "n3dt_vgg_packed_bytes": (sz, [ci]),
+        "n3dt_vgg_pack": (ci, [ci, ctypes.POINTER(VggParams), vp, vp]),
+        "n3dt_vgg_saved_bytes": (sz, [ci, ci]),
+        "n3dt_vgg_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_vgg_loss_fwd": (ci, [ci, ci, ci, vp, vp, vp, vp, f32, vp, vp, sz, vp, sz, vp]),
+        "n3dt_vgg_loss_bwd": (ci, [ci, ci, ci, vp, vp, vp, vp, sz, vp, vp, sz, vp]),
+        "n3dt_vgg_conv_stage": (ci, [ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp]),
+        "n3dt_a2s_saved_bytes": (sz, [ci]),
+        "n3dt_a2s_workspace_bytes": (sz, [ci]),
+        "n3dt_a2s_fwd": (ci, [ci, a2p, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]),
+        "n3dt_a2s_bwd": (ci, [ci, a2p, vp, vp, sz, vp, vp, sz, vp]),
+        "n3dt_flat_adam_record_bytes": (sz, [ci]),
+        "n3dt_flat_adam_step": (ci, [vp, vp, ci, vp, ci, vp, vp]),
+        "n3dt_render_fwd16": (ci, [gp, ci, vp, mp] + [vp] * 19 + [vp, sz, vp]),
+        "n3dt_neural_render_fwd16_reuse": (ci, [gp, ci, ci, rp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_feat_to_rgb0": (ci, [ci, ci, vp, vp, vp, vp, vp]),
+        "n3dt_x16_pack_probe": (ci, [ci, ci, sz, vp, vp, vp]),
+        "n3dt_x16_pe_probe": (ci, [ci, ci, sz, vp, vp, vp]),
+        "n3dt_eval_metrics_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_eval_metrics": (ci, [ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_lpips_packed_bytes": (sz, []),
+        "n3dt_lpips_pack": (ci, [ctypes.POINTER(LpipsParams), vp, vp]),
+        "n3dt_lpips_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_lpips": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_mel_workspace_bytes": (sz, []),
+        "n3dt_mel_spectrogram": (ci, [i64, vp, i64, vp, i64, i64, ci, vp, vp, vp, i64, ci, vp, sz, vp]),
+        "n3dt_mel_windows": (ci, [i64, vp, i64, ci, ci, vp, vp, vp]),
+        "n3dt_syncnet_packed_bytes": (sz, []),
+        "n3dt_syncnet_pack": (ci, [ctypes.POINTER(SyncnetParams), vp, vp]),
+        "n3dt_syncnet_workspace_bytes": (sz, [ci]),
+        "n3dt_syncnet_face_windows": (ci, [ci, ci, ci, vp, vp, ci, vp, vp]),
+        "n3dt_syncnet_fwd": (ci, [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+        "n3dt_syncnet_block": (ci, [ci, ci, vp, vp, vp, vp, sz, vp]),
+        # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
+        "n3dt_flat_adam_guard_bytes": (sz, []),
+        "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),
+    }
+
+
+SIGNATURES = _signatures()
+GUARD_EXPORTS = [name for name in SIGNATURES if name.startswith("n3dt_flat_adam_guard")]
+EXPORTS = [name for name in SIGNATURES if name not in GUARD_EXPORTS]
 
 
 _LIB = None
@@ -147,153 +212,9 @@ def lib():
         raise N3dtError("libn3dt.so not found at %s -- the HIP extension is required (no CPU fallback); "
                         "run `make -C nerf-3dtalker-code_amd`" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    L.n3dt_abi_version.restype = ci
-    L.n3dt_last_error.restype = ctypes.c_char_p
-    L.n3dt_mlp_packed_bytes.restype = sz
-    L.n3dt_mlp_packed_bytes.argtypes = [ctypes.POINTER(Geom), ci]
-    L.n3dt_mlp_pack.restype = ci
-    L.n3dt_mlp_pack.argtypes = [ctypes.POINTER(Geom), ci, ctypes.POINTER(MlpParams), vp, vp]
-    L.n3dt_render_workspace_bytes.restype = sz
-    L.n3dt_render_workspace_bytes.argtypes = [ctypes.POINTER(Geom), ci]
-    L.n3dt_render_fwd.restype = ci
-    L.n3dt_render_fwd.argtypes = [ctypes.POINTER(Geom), ci, vp, ctypes.POINTER(MlpParams)] + [vp] * 15 + [vp, sz, vp]
-    L.n3dt_render_fwd16.restype = ci
-    L.n3dt_render_fwd16.argtypes = [ctypes.POINTER(Geom), ci, vp, ctypes.POINTER(MlpParams)] + [vp] * 19 + [vp, sz, vp]
-    L.n3dt_neural_render_workspace_bytes.restype = sz
-    L.n3dt_neural_render_workspace_bytes.argtypes = [ctypes.POINTER(Geom), ci]
-    L.n3dt_neural_render_fwd.restype = ci
-    L.n3dt_neural_render_fwd.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, sz, vp]
-    L.n3dt_neural_render_fwd_reuse.restype = ci
-    L.n3dt_neural_render_fwd_reuse.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, sz, vp]
-    L.n3dt_neural_render_fwd16_reuse.restype = ci
-    L.n3dt_neural_render_fwd16_reuse.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, vp, vp, vp, sz, vp]
-    L.n3dt_feat_to_rgb0.restype = ci
-    L.n3dt_feat_to_rgb0.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-    L.n3dt_neural_render_pack.restype = ci
-    L.n3dt_neural_render_pack.argtypes = [ctypes.POINTER(Geom), ci, ci, ctypes.POINTER(RenderParams), vp, sz, vp]
-    L.n3dt_chw_to_hwc.restype = ci
-    L.n3dt_chw_to_hwc.argtypes = [ci, ci, vp, vp, vp]
-    gp, mp, rp = ctypes.POINTER(Geom), ctypes.POINTER(MlpParams), ctypes.POINTER(RenderParams)
-    L.n3dt_render_train_saved_bytes.restype = sz
-    L.n3dt_render_train_saved_bytes.argtypes = [gp]
-    L.n3dt_render_train_workspace_bytes.restype = sz
-    L.n3dt_render_train_workspace_bytes.argtypes = [gp]
-    L.n3dt_render_train_fwd.restype = ci
-    L.n3dt_render_train_fwd.argtypes = [gp, ci, vp, mp] + [vp] * 14 + [vp, sz, vp, sz, vp]
-    L.n3dt_render_bwd.restype = ci
-    L.n3dt_render_bwd.argtypes = [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 12 + [vp, sz, vp]
-    L.n3dt_render_bwd_cam.restype = ci  # n3dt_render_bwd + d_Kinv, d_xy behind d_T
-    L.n3dt_render_bwd_cam.argtypes = [gp, ci, mp, mp] + [vp] * 7 + [vp, sz] + [vp] * 14 + [vp, sz, vp]
-    L.n3dt_neural_render_train_saved_bytes.restype = sz
-    L.n3dt_neural_render_train_saved_bytes.argtypes = [gp, ci]
-    L.n3dt_neural_render_train_workspace_bytes.restype = sz
-    L.n3dt_neural_render_train_workspace_bytes.argtypes = [gp, ci]
-    L.n3dt_neural_render_train_fwd.restype = ci
-    L.n3dt_neural_render_train_fwd.argtypes = [gp, ci, ci, rp, vp, vp, vp, sz, vp, sz, vp]
-    L.n3dt_neural_render_bwd.restype = ci
-    L.n3dt_neural_render_bwd.argtypes = [gp, ci, ci, rp, rp, vp, vp, vp, sz, vp, vp, sz, vp]
-    L.n3dt_loss_fwd.restype = ci
-    L.n3dt_loss_fwd.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
-    L.n3dt_loss_bwd.restype = ci
-    L.n3dt_loss_bwd.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp]
-    L.n3dt_prof_enable.restype = ci
-    L.n3dt_prof_enable.argtypes = [ci]
-    L.n3dt_prof_collect.restype = ci
-    L.n3dt_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_float), ci, ctypes.POINTER(ci)]
-    L.n3dt_fine_sample.restype = ci
-    L.n3dt_fine_sample.argtypes = [gp, ci, vp, vp, vp, vp, vp, vp]
-    L.n3dt_img_to_uint8.restype = ci
-    L.n3dt_img_to_uint8.argtypes = [ci, ci, vp, vp, vp]
-    L.n3dt_sample_points.restype = ci
-    L.n3dt_sample_points.argtypes = [gp] + [vp] * 10 + [vp]
-    L.n3dt_embed.restype = ci
-    L.n3dt_embed.argtypes = [ci, sz, vp, vp, vp]
-    L.n3dt_embed_freqs.restype = ci
-    L.n3dt_embed_freqs.argtypes = [ci, sz, ci, vp, vp, vp]
-    L.n3dt_ray_vd_bias.restype = ci
-    L.n3dt_ray_vd_bias.argtypes = [gp, vp, ctypes.c_int64, vp, vp, vp, vp, vp]
-    L.n3dt_mlp_points_workspace_bytes.restype = sz
-    L.n3dt_mlp_points_workspace_bytes.argtypes = [gp, sz]
-    L.n3dt_mlp_points.restype = ci
-    L.n3dt_mlp_points.argtypes = [gp, sz, mp] + [vp] * 5 + [vp, sz, vp]
-    L.n3dt_composite.restype = ci
-    L.n3dt_composite.argtypes = [ci, ci, ci, ci] + [vp] * 8 + [vp]
-    L.n3dt_x16_pack_probe.restype = ci
-    L.n3dt_x16_pack_probe.argtypes = [ci, ci, sz, vp, vp, vp]
-    L.n3dt_x16_pe_probe.restype = ci
-    L.n3dt_x16_pe_probe.argtypes = [ci, ci, sz, vp, vp, vp]
-    L.n3dt_stage_inputs.restype = ci
-    L.n3dt_stage_inputs.argtypes = [ctypes.POINTER(Stage), vp]
-    L.n3dt_graph_begin.restype = ci
-    L.n3dt_graph_begin.argtypes = [vp]
-    L.n3dt_graph_end.restype = ci
-    L.n3dt_graph_end.argtypes = [vp, ctypes.POINTER(vp)]
-    L.n3dt_graph_launch.restype = ci
-    L.n3dt_graph_launch.argtypes = [vp, vp]
-    L.n3dt_graph_destroy.restype = ci
-    L.n3dt_graph_destroy.argtypes = [vp]
-    L.n3dt_vgg_packed_bytes.restype = sz
-    L.n3dt_vgg_packed_bytes.argtypes = [ci]
-    L.n3dt_vgg_pack.restype = ci
-    L.n3dt_vgg_pack.argtypes = [ci, ctypes.POINTER(VggParams), vp, vp]
-    L.n3dt_vgg_saved_bytes.restype = sz
-    L.n3dt_vgg_saved_bytes.argtypes = [ci, ci]
-    L.n3dt_vgg_workspace_bytes.restype = sz
-    L.n3dt_vgg_workspace_bytes.argtypes = [ci, ci, ci]
-    L.n3dt_vgg_loss_fwd.restype = ci
-    L.n3dt_vgg_loss_fwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_float, vp, vp, sz, vp, sz, vp]
-    L.n3dt_vgg_loss_bwd.restype = ci
-    L.n3dt_vgg_loss_bwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, sz, vp, vp, sz, vp]
-    L.n3dt_vgg_conv_stage.restype = ci
-    L.n3dt_vgg_conv_stage.argtypes = [ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp]
-    L.n3dt_a2s_saved_bytes.restype = sz
-    L.n3dt_a2s_saved_bytes.argtypes = [ci]
-    L.n3dt_a2s_workspace_bytes.restype = sz
-    L.n3dt_a2s_workspace_bytes.argtypes = [ci]
-    L.n3dt_a2s_fwd.restype = ci
-    L.n3dt_a2s_fwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
-    L.n3dt_a2s_bwd.restype = ci
-    L.n3dt_a2s_bwd.argtypes = [ci, ctypes.POINTER(A2sParams), vp, vp, sz, vp, vp, sz, vp]
-    L.n3dt_flat_adam_record_bytes.restype = sz
-    L.n3dt_flat_adam_record_bytes.argtypes = [ci]
-    L.n3dt_flat_adam_step.restype = ci
-    L.n3dt_flat_adam_step.argtypes = [vp, vp, ci, vp, ci, vp, vp]
-    L.n3dt_eval_metrics_workspace_bytes.restype = sz
-    L.n3dt_eval_metrics_workspace_bytes.argtypes = [ci, ci, ci]
-    L.n3dt_eval_metrics.restype = ci
-    L.n3dt_eval_metrics.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
-    L.n3dt_lpips_packed_bytes.restype = sz
-    L.n3dt_lpips_packed_bytes.argtypes = []
-    L.n3dt_lpips_pack.restype = ci
-    L.n3dt_lpips_pack.argtypes = [ctypes.POINTER(LpipsParams), vp, vp]
-    L.n3dt_lpips_workspace_bytes.restype = sz
-    L.n3dt_lpips_workspace_bytes.argtypes = [ci, ci, ci]
-    L.n3dt_lpips.restype = ci
-    L.n3dt_lpips.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
-    i64 = ctypes.c_int64
-    L.n3dt_mel_workspace_bytes.restype = sz
-    L.n3dt_mel_workspace_bytes.argtypes = []
-    L.n3dt_mel_spectrogram.restype = ci
-    L.n3dt_mel_spectrogram.argtypes = [i64, vp, i64, vp, i64, i64, ci, vp, vp, vp, i64, ci, vp, sz, vp]
-    L.n3dt_mel_windows.restype = ci
-    L.n3dt_mel_windows.argtypes = [i64, vp, i64, ci, ci, vp, vp, vp]
-    L.n3dt_syncnet_packed_bytes.restype = sz
-    L.n3dt_syncnet_packed_bytes.argtypes = []
-    L.n3dt_syncnet_pack.restype = ci
-    L.n3dt_syncnet_pack.argtypes = [ctypes.POINTER(SyncnetParams), vp, vp]
-    L.n3dt_syncnet_workspace_bytes.restype = sz
-    L.n3dt_syncnet_workspace_bytes.argtypes = [ci]
-    L.n3dt_syncnet_face_windows.restype = ci
-    L.n3dt_syncnet_face_windows.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp]
-    L.n3dt_syncnet_fwd.restype = ci
-    L.n3dt_syncnet_fwd.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]
-    L.n3dt_syncnet_block.restype = ci
-    L.n3dt_syncnet_block.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp]
-    L.n3dt_flat_adam_guard_bytes.restype = sz
-    L.n3dt_flat_adam_guard_bytes.argtypes = []
-    L.n3dt_flat_adam_guarded_step.restype = ci
-    L.n3dt_flat_adam_guarded_step.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.n3dt_abi_version() != 5:
         raise N3dtError("libn3dt.so ABI version mismatch")
     if L.n3dt_flat_adam_guard_bytes() != ctypes.sizeof(AdamGuard):

@@ -34,7 +34,7 @@ Read off the host code of train_nr.hip:
     d_featmap = d_x + to_rgb_0^T d_rgb in fp32                                           nr16_final_kernel (:1026-1043)
   path "exact"   nr_bwd<float> (:1187-1267): the same adjoints in the reference's operator order (feat_layers^T, Blur^T, the
     un-shuffle with the residual's sum over the four repeats, layer_2^T, layer_1^T); nothing is rounded.
-  The layered bf16 backward nr_bwd<nrt_bf16> is NOT restated: the library builds featmap_nc == 256 only (n3dt_api.hip:913), every
+  The layered bf16 backward nr_bwd<nrt_bf16> is NOT restated: the library builds featmap_nc == 256 only (n3dt_api.hip: check_nr), every
   such geometry takes the fused path (nr16_supported), and the switch that forces the layered one (N3DT_NR_TRAIN_FUSED) is
   latched per process.
   In both paths d_rgb (the RGB pyramid's gradient), the sigmoid factor and every parameter gradient stay fp32.
@@ -74,7 +74,7 @@ GPU_CASES = {
     (5, 256, 2, 3): 0,
     (4, 256, 4, 1): 0,      # the fourth block is 32 -> 32: the channel clamp, inside what the library builds
 }
-# Geometries the library refuses ("only featmap_nc == 256 is built", n3dt_api.hip:913): the restatement is pinned at them on the CPU
+# Geometries the library refuses ("only featmap_nc == 256 is built", n3dt_api.hip: check_nr): the restatement is pinned at them on the CPU
 # (AUTOGRAD_CASES, FIXTURE_CASES), the GPU test asserts the refusal.
 UNBUILT_CASES = ((6, 64, 3, 2), (5, 32, 1, 1))
 AUTOGRAD_CASES = {(4, 32, 1, 1): 0, (5, 32, 2, 3): 0, (6, 64, 3, 2): 0, (4, 256, 3, 2): 0}

@@ -23,6 +23,56 @@ def test_library_exports_every_declared_symbol():
     assert L.n3dt_abi_version() == 5
 
 
+def _ctypes_class(t):
+    """The argument class of a ctypes type: every pointer is one class, the scalars are themselves."""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_size_t: "size_t", ctypes.c_float: "float", ctypes.c_int64: "int64_t"}.get(t, "unknown %r" % (t,))
+
+
+def _c_class(decl):
+    """The same classes for one C parameter (or return) declaration, `const float* xy` or `size_t workspace_bytes`."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    ctype = " ".join(words[:-1]) if len(words) > 1 else words[0]  # a parameter carries its name, a return type does not
+    return {"int": "int", "int32_t": "int", "size_t": "size_t", "float": "float", "int64_t": "int64_t"}.get(ctype, "unknown %r" % ctype)
+
+
+def test_ctypes_table_matches_the_headers_argument_by_argument():
+    """_lib.SIGNATURES is the only place Python types the C ABI, and nothing else checks it: a pointer run one short
+    ([vp] * 14 for 15) would read the workspace size from the wrong slot.  Every prototype of the two public headers is parsed
+    and its return type and each argument's class (pointer, int, size_t, float, int64_t) compared with the table's row."""
+    from n3dt import _lib
+    text = ""
+    for name in ("n3dt.h", "n3dt_flat_adam_guard.h"):
+        with open(os.path.join(REPO, "include", name)) as f:
+            text += f.read() + "\n"
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    protos = re.findall(r"^(int|size_t|const char\*|void)\s+(n3dt_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
+    names = [n for _, n, _ in protos]
+    assert len(names) == len(set(names)), "a prototype is declared twice"
+    # no prototype skipped by the parser, none missing from the table
+    assert set(names) == set(_lib.EXPORTS) | set(_lib.GUARD_EXPORTS) == set(_lib.SIGNATURES)
+    ret_class = {"int": "int", "size_t": "size_t", "const char*": "pointer", "void": "void"}
+    wrong = []
+    for ret, name, args in protos:
+        restype, argtypes = _lib.SIGNATURES[name]
+        args = " ".join(args.split())
+        want = [] if args in ("void", "") else [_c_class(a.strip()) for a in args.split(",")]
+        got = [_ctypes_class(t) for t in argtypes]
+        got_ret = "void" if restype is None else _ctypes_class(restype)
+        if any(c.startswith("unknown") for c in want + got + [got_ret]) or ret_class[ret] != got_ret or want != got:
+            wrong.append("%s: header %s(%s), table %s(%s)" % (name, ret_class[ret], ", ".join(want), got_ret, ", ".join(got)))
+    assert not wrong, "ctypes table disagrees with the headers:\n" + "\n".join(wrong)
+    # and lib() applies the table as it stands
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
 def test_geometry_validation_without_a_gpu():
     """Size queries are pure host code: they validate geometry and report errors without touching a device."""
     from n3dt import _lib, ops
