@@ -463,6 +463,56 @@ int n3dt_syncnet_fwd(int n, const void* packed, const float* mel_windows, const 
 int n3dt_syncnet_block(int block, int n, const void* packed, const float* in, float* out, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- Wav2Lip's generator: audio-driven lip-synced faces, frozen, inference only (an addition, the ABI version stays 5) ------
+ * The reference's wav_models/wav2lip.py: 51 blocks in state-dict order -- 18 of the face encoder on [6,96,96] (the outputs of its
+ * seven groups are skip features), 13 of the audio encoder on [1,80,16], 18 of the decoder (six of them ConvTranspose2d; behind
+ * each of its seven groups torch.cat((x, skip), 1)), Conv2d(80,32,3) and the plain nn.Conv2d(32,3,1) with its sigmoid.  Every
+ * block but the last is convolution + BatchNorm2d (eval mode, eps 1e-5), then for residual blocks the block's own input, then
+ * ReLU.  csrc/wav2lip.hip; the table, the classes of a transposed block's rows and the address arithmetic are
+ * csrc/wav2lip_core.h; DESIGN section 3.17.
+ *   pack    batch norm folded in float64 as n3dt_syncnet_pack does; weight[b] [C_out, C_in, kh, kw] (ConvTranspose2d:
+ *           [C_in, C_out, kh, kw]), the other five [C_out], device fp32; block 50 has weight and bias alone (its bn_* are ignored).
+ *   blocks  implicit GEMMs on the bf16 MFMA, every operand split hi + lo, three products per term, fp32 accumulation: the only mode;
+ *           block 50 accumulates in float64
+ * n3dt_wav2lip_fwd: mel_windows [n,1,80,16], face_inputs [n,6,96,96] (channels 0..2 the masked target, 3..5 the reference, BGR) ->
+ *   out [n,3,96,96] fp32 (BGR, in [0,1]).  All contiguous.
+ * n3dt_wav2lip_block runs ONE block on in [n, C_in, Hi, Wi] -> out [n, C_out, Ho, Wo]; for the last block of a decoder group
+ *   (31, 33, 36, 39, 42, 45, 48) with skip [n, C_skip, Ho, Wo] given, out is the concatenation [n, C_out + C_skip, Ho, Wo]; block 50
+ *   gives its logits (no sigmoid).  skip is ignored for every other block.
+ * n3dt_wav2lip_face_inputs: frames [n,3,height,width] fp32 RGB in [0,1] (clamped, NaN -> 0), ref_frames the same (NULL: the frames
+ *   themselves), boxes [n_boxes,4] int32 (device) = (y1, y2, x1, x2), n_boxes = n or 1 -> out [n,6,96,96]: the crops resampled to
+ *   96 x 96 bilinearly with half-pixel centres in float64, BGR, rows 48..95 of channels 0..2 zero.
+ * n3dt_wav2lip_paste: faces [n,3,96,96] (BGR) resampled the same way to each box and written over [y1:y2, x1:x2] of a copy of
+ *   frames [n,3,height,width], BGR -> RGB -> out [n,3,height,width]; outside the box out is the frame, bit for bit.
+ * A window's results depend on that window's inputs and the packed weights alone -- not on its position in the call or on n -- and
+ * are bitwise reproducible.  Everything is enqueued on `stream`, nothing synchronises, no atomics.
+ * workspace: n3dt_wav2lip_workspace_bytes(n) (about 11.2 MB a window: the seven concatenation buffers and two copies of the largest
+ * other map), 256-byte aligned, never cleared, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size query returns 0 and sets n3dt_last_error): 1 <= n <= 128 for fwd, block
+ * and the workspace (1.43 GB at 128), 1 <= n <= 4096 for face_inputs and paste; 2 <= height, width <= 4096; 0 <= block <= 50;
+ * n_boxes 1 or n; no NULL pointer but skip and ref_frames; frames and boxes 4-byte, packed and workspace 256-byte, the rest
+ * 16-byte aligned; workspace_bytes at least the query's. */
+#define N3DT_WAV2LIP_BLOCKS 51
+typedef struct N3dtWav2lipParams {
+    const float* weight[N3DT_WAV2LIP_BLOCKS];
+    const float* bias[N3DT_WAV2LIP_BLOCKS];
+    const float* bn_weight[N3DT_WAV2LIP_BLOCKS];
+    const float* bn_bias[N3DT_WAV2LIP_BLOCKS];
+    const float* bn_mean[N3DT_WAV2LIP_BLOCKS];
+    const float* bn_var[N3DT_WAV2LIP_BLOCKS];
+} N3dtWav2lipParams;
+size_t n3dt_wav2lip_packed_bytes(void);
+int n3dt_wav2lip_pack(const N3dtWav2lipParams* p, void* packed, void* stream);
+size_t n3dt_wav2lip_workspace_bytes(int n);
+int n3dt_wav2lip_fwd(int n, const void* packed, const float* mel_windows, const float* face_inputs, float* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int n3dt_wav2lip_block(int block, int n, const void* packed, const float* in, const float* skip, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int n3dt_wav2lip_face_inputs(int n, int height, int width, const float* frames, const float* ref_frames, const int32_t* boxes,
+                             int n_boxes, float* out, void* stream);
+int n3dt_wav2lip_paste(int n, int height, int width, const float* faces, const float* frames, const int32_t* boxes, int n_boxes,
+                       float* out, void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

@@ -17,6 +17,7 @@
 #include "lpips_core.h"
 #include "mel_core.h"
 #include "syncnet_core.h"
+#include "wav2lip_core.h"
 
 static thread_local char g_err[256] = "";
 
@@ -774,6 +775,96 @@ extern "C" int n3dt_syncnet_block(int block, int n, const void* packed, const fl
     }
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_syncnet_block(block, n, packed, in, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// Wav2Lip's generator (csrc/wav2lip.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* wav2lip_windows(int n) { return (n < 1 || n > W2L_MAX_WINDOWS) ? "n outside 1..128" : nullptr; }
+static const char* wav2lip_frames(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes, const float* other,
+                                  const float* out) {
+    if (n < 1 || n > W2L_MAX_FRAMES) return "n outside 1..4096";
+    if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 2..4096";
+    if (!frames || !boxes || !out) return "NULL pointer";
+    if (n_boxes != 1 && n_boxes != n) return "n_boxes must be 1 or n (one box per frame)";
+    if ((((size_t)frames) | ((size_t)boxes) | ((size_t)other)) & 3) return "frames and boxes must be 4-byte aligned";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_wav2lip_packed_bytes(void) { return n3dt_wav2lip_packed_layout_bytes(); }
+
+extern "C" int n3dt_wav2lip_pack(const N3dtWav2lipParams* p, void* packed, void* stream) {
+    if (!p || !packed) return fail(N3DT_EINVAL, "n3dt_wav2lip_pack: NULL argument");
+    if (((size_t)packed) & 255) return fail(N3DT_EINVAL, "n3dt_wav2lip_pack: packed must be 256-byte aligned");
+    for (int b = 0; b < N3DT_WAV2LIP_BLOCKS; ++b) {
+        const bool bn = b != W2L_HEAD;
+        if (!p->weight[b] || !p->bias[b] || (bn && (!p->bn_weight[b] || !p->bn_bias[b] || !p->bn_mean[b] || !p->bn_var[b])))
+            return fail(N3DT_EINVAL, "n3dt_wav2lip_pack: NULL parameter pointer");
+    }
+    n3dt_launch_wav2lip_pack(p, packed, (hipStream_t)stream);
+    return check_hip("n3dt_wav2lip_pack");
+}
+
+extern "C" size_t n3dt_wav2lip_workspace_bytes(int n) {
+    const char* what = wav2lip_windows(n);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_wav2lip_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_wav2lip_ws_bytes(n);
+}
+
+extern "C" int n3dt_wav2lip_fwd(int n, const void* packed, const float* mel_windows, const float* face_inputs, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_wav2lip_fwd";
+    const char* what = wav2lip_windows(n);
+    if (!what) {
+        if (!packed || !mel_windows || !face_inputs || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)mel_windows) | ((size_t)face_inputs) | ((size_t)out)) & 15) what = "mel_windows, face_inputs and out must be 16-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_wav2lip_ws_bytes(n)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_wav2lip_fwd(n, packed, mel_windows, face_inputs, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_wav2lip_block(int block, int n, const void* packed, const float* in, const float* skip, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_wav2lip_block";
+    const char* what = wav2lip_windows(n);
+    if (!what) {
+        if (block < 0 || block >= W2L_BLOCKS) what = "block outside 0..50";
+        else if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)in) | ((size_t)skip) | ((size_t)out)) & 15) what = "in, skip and out must be 16-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_wav2lip_ws_bytes(n)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_wav2lip_block(block, n, packed, in, skip, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_wav2lip_face_inputs(int n, int height, int width, const float* frames, const float* ref_frames, const int32_t* boxes,
+                                        int n_boxes, float* out, void* stream) {
+    static const char* who = "n3dt_wav2lip_face_inputs";
+    const char* what = wav2lip_frames(n, height, width, frames, boxes, n_boxes, ref_frames, out);
+    if (!what && (((size_t)out) & 15)) what = "out must be 16-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_wav2lip_face_inputs(n, height, width, frames, ref_frames, boxes, n_boxes == 1 ? 0 : 4, out, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_wav2lip_paste(int n, int height, int width, const float* faces, const float* frames, const int32_t* boxes, int n_boxes,
+                                  float* out, void* stream) {
+    static const char* who = "n3dt_wav2lip_paste";
+    const char* what = wav2lip_frames(n, height, width, frames, boxes, n_boxes, nullptr, out);
+    if (!what) {
+        if (!faces) what = "NULL pointer";
+        else if (((size_t)faces) & 15) what = "faces must be 16-byte aligned";
+        else if (((size_t)out) & 3) what = "out must be 4-byte aligned";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_wav2lip_paste(n, height, width, faces, frames, boxes, n_boxes == 1 ? 0 : 4, out, (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -177,4 +177,16 @@ void n3dt_launch_syncnet_faces(int n, int height, int width, const float* frames
 void n3dt_launch_syncnet_fwd(int n, const void* packed, const float* mel, const float* faces, float* audio_emb, float* face_emb,
                              double* cosv, void* workspace, hipStream_t st);
 void n3dt_launch_syncnet_block(int block, int n, const void* packed, const float* in, float* out, void* workspace, hipStream_t st);
+
+// ---- wav2lip.hip
+size_t n3dt_wav2lip_packed_layout_bytes(void);
+size_t n3dt_wav2lip_ws_bytes(int n);
+void n3dt_launch_wav2lip_pack(const N3dtWav2lipParams* p, void* packed, hipStream_t st);
+void n3dt_launch_wav2lip_face_inputs(int n, int height, int width, const float* frames, const float* ref_frames, const int* boxes,
+                                     int box_stride, float* out, hipStream_t st);
+void n3dt_launch_wav2lip_paste(int n, int height, int width, const float* faces, const float* frames, const int* boxes, int box_stride,
+                               float* out, hipStream_t st);
+void n3dt_launch_wav2lip_fwd(int n, const void* packed, const float* mel, const float* faces, float* out, void* workspace, hipStream_t st);
+void n3dt_launch_wav2lip_block(int block, int n, const void* packed, const float* in, const float* skip, float* out, void* workspace,
+                               hipStream_t st);
 }

@@ -5,5 +5,6 @@ from .audio import Audio2style  # noqa: F401
 from .mel import MelFrontend, MelStream, mel_basis  # noqa: F401
 from .optim import FlatAdam  # noqa: F401
 from .eval_utils import image_metrics, calc_eval_metrics, LPIPS, SyncNet, SyncMeter  # noqa: F401
+from .wav2lip import Wav2Lip, Wav2LipClip, load_wav2lip  # noqa: F401
 from .train import validate  # noqa: F401
-from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet  # noqa: F401,E402
+from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet, wav2lip  # noqa: F401,E402

@@ -51,6 +51,13 @@ class SyncnetParams(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p * SYNCNET_BLOCKS) for name in ("weight", "bias", "bn_weight", "bn_bias", "bn_mean", "bn_var")]
 
 
+WAV2LIP_BLOCKS = 51
+
+
+class Wav2lipParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p * WAV2LIP_BLOCKS) for name in ("weight", "bias", "bn_weight", "bn_bias", "bn_mean", "bn_var")]
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -186,6 +193,13 @@ def _signatures():
         "n3dt_syncnet_face_windows": (ci, [ci, ci, ci, vp, vp, ci, vp, vp]),
         "n3dt_syncnet_fwd": (ci, [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
         "n3dt_syncnet_block": (ci, [ci, ci, vp, vp, vp, vp, sz, vp]),
+        "n3dt_wav2lip_packed_bytes": (sz, []),
+        "n3dt_wav2lip_pack": (ci, [ctypes.POINTER(Wav2lipParams), vp, vp]),
+        "n3dt_wav2lip_workspace_bytes": (sz, [ci]),
+        "n3dt_wav2lip_fwd": (ci, [ci, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_wav2lip_block": (ci, [ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_wav2lip_face_inputs": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),
+        "n3dt_wav2lip_paste": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),
         # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
         "n3dt_flat_adam_guard_bytes": (sz, []),
         "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),

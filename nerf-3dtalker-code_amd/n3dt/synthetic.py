@@ -379,6 +379,40 @@ def syncnet_state_dict(seed=0):
     return sd
 
 
+WAV2LIP_HEAD_WEIGHT_SCALE = 16.0
+WAV2LIP_HEAD_BIAS_SCALE = 2.0
+
+
+def wav2lip_state_dict(seed=0):
+    """Seeded stand-in for the weights of Wav2Lip's generator (`wav2lip.pth` cannot be fetched offline), under the reference's
+    keys for `Wav2Lip` (n3dt.wav2lip.load_wav2lip), by syncnet_state_dict's rules: every convolution U(-1 / sqrt(fan_in),
+    1 / sqrt(fan_in)) in weights and bias -- for a ConvTranspose2d weight [C_in, C_out, kh, kw] the fan-in is C_in kh kw with C_in
+    on axis 0 -- and non-trivial batch-norm tensors.  With these the class keeps O(1) activations through all 51 blocks, but its
+    logits stay within +-0.21: too flat to test a sigmoid.  The plain output convolution's weights are therefore scaled by
+    WAV2LIP_HEAD_WEIGHT_SCALE and its bias by WAV2LIP_HEAD_BIAS_SCALE, chosen so that the image of the fixture's windows spans
+    [0.2, 0.8] with at most 1 % of it outside (0.02, 0.98)."""
+    from .wav2lip import BLOCKS, HEAD, block_names
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for b, (name, (tr, cin, cout, (kh, kw), _, _, _, _)) in enumerate(zip(block_names(), BLOCKS)):
+        bound = 1.0 / math.sqrt(cin * kh * kw)
+        shape = (cin, cout, kh, kw) if tr else (cout, cin, kh, kw)
+        weight = (torch.rand(shape, generator=gen) * 2.0 - 1.0) * bound
+        bias = (torch.rand(cout, generator=gen) * 2.0 - 1.0) * bound
+        if b == HEAD:
+            sd[name + ".weight"] = weight * WAV2LIP_HEAD_WEIGHT_SCALE
+            sd[name + ".bias"] = bias * WAV2LIP_HEAD_BIAS_SCALE
+            continue
+        sd[name + ".conv_block.0.weight"] = weight
+        sd[name + ".conv_block.0.bias"] = bias
+        sd[name + ".conv_block.1.weight"] = torch.rand(cout, generator=gen) + 0.5
+        sd[name + ".conv_block.1.bias"] = torch.randn(cout, generator=gen) * 0.1
+        sd[name + ".conv_block.1.running_mean"] = torch.randn(cout, generator=gen) * 0.1
+        sd[name + ".conv_block.1.running_var"] = torch.rand(cout, generator=gen) + 0.5
+        sd[name + ".conv_block.1.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    return sd
+
+
 def mel_batch(B, seed=0):
     """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
     range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""
