@@ -513,6 +513,46 @@ int n3dt_wav2lip_face_inputs(int n, int height, int width, const float* frames, 
 int n3dt_wav2lip_paste(int n, int height, int width, const float* faces, const float* frames, const int32_t* boxes, int n_boxes,
                        float* out, void* stream);
 
+/* ---- S3FD face detector: frames to Wav2Lip crop boxes -----------------------------------
+ * The reference's face_detection/detection/sfd (net_s3fd.py under detect.py, bbox.py, sfd_detector.py and api.py), frozen and
+ * inference-only, with the caller's weights: 19 backbone convolutions in state-dict order (conv1_1 .. conv7_2), five 2 x 2 max
+ * pools, three L2Norms and six levels' conf / loc heads (strides 4 .. 128), then scores, decode and greedy NMS in float64.
+ * csrc/s3fd.hip; the table and the run-time geometry are csrc/s3fd_core.h.  Blocks for the single-block entry: 0..18 the
+ * convolutions, 19..23 the pools, 24..26 the norms, 27..32 the head pairs (their stored columns: conf, then loc; no max-out).
+ * weight / bias [31]: the 19 convolutions, then (conf, loc) of each level; norm_weight [3].
+ * heads: x [n,3,height,width] mean-subtracted -> out[12] = cls1, reg1, .. cls6, reg6 (NCHW, cls1 after the max-out).
+ * detect: frames [n,3,height,width] fp32 RGB in [0,1] (clamped, NaN -> 0; 255 u - (104, 117, 123) on R, G, B) -> dets
+ *   [n,max_faces,5] float64 (x1, y1, x2, y2, score) in descending score, unused rows 0; count [n]; left [n], the positions still
+ *   standing where max_faces cut the NMS short; scores [n,P] float64 or NULL.
+ * boxes: dets, count of n_frames frames -> boxes [n_frames,4] int32 (y1, y2, x1, x2) from each frame's top detection: clipped at
+ *   0, truncated, padded, clamped to the frame, smoothed over `smooth` frames (0: not) as the reference's get_smoothened_boxes
+ *   does; found [n_frames]; a frame without a detection enters as the whole frame.  scratch: 8 n_frames int32.
+ * An image's results depend on that image and the packed weights alone and are bitwise reproducible.  Everything is enqueued on
+ * `stream`, nothing synchronises, no atomics.  workspace: 256-byte aligned, never cleared, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size queries return 0 and set n3dt_last_error): 32 <= height, width <=
+ * 4096; 1 <= n <= the result of the max_images query (a 4 GiB workspace budget, at most 1024); 1 <= max_faces <= 64. */
+#define N3DT_S3FD_PARAMS 31
+#define N3DT_S3FD_BLOCKS 33
+typedef struct N3dtS3fdParams {
+    const float* weight[N3DT_S3FD_PARAMS];
+    const float* bias[N3DT_S3FD_PARAMS];
+    const float* norm_weight[3];
+} N3dtS3fdParams;
+size_t n3dt_s3fd_packed_bytes(void);
+int n3dt_s3fd_pack(const N3dtS3fdParams* p, void* packed, void* stream);
+int n3dt_s3fd_max_images(int height, int width);
+int n3dt_s3fd_positions(int height, int width);
+size_t n3dt_s3fd_workspace_bytes(int n, int height, int width);
+int n3dt_s3fd_heads(int n, int height, int width, const void* packed, const float* x, float* const* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int n3dt_s3fd_detect(int n, int height, int width, const void* packed, const float* frames, int max_faces, double* scores, double* dets,
+                     int32_t* count, int32_t* left, void* workspace, size_t workspace_bytes, void* stream);
+int n3dt_s3fd_boxes(int n_frames, int height, int width, int max_faces, const double* dets, const int32_t* count, int pady1, int pady2,
+                    int padx1, int padx2, int smooth, int32_t* boxes, int32_t* found, int32_t* scratch, void* stream);
+size_t n3dt_s3fd_block_workspace_bytes(int block, int n, int height, int width);
+int n3dt_s3fd_block(int block, int n, int height, int width, const void* packed, const float* in, float* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

@@ -18,6 +18,7 @@
 #include "mel_core.h"
 #include "syncnet_core.h"
 #include "wav2lip_core.h"
+#include "s3fd_core.h"
 
 static thread_local char g_err[256] = "";
 
@@ -865,6 +866,141 @@ extern "C" int n3dt_wav2lip_paste(int n, int height, int width, const float* fac
     }
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_wav2lip_paste(n, height, width, faces, frames, boxes, n_boxes == 1 ? 0 : 4, out, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// The S3FD face detector (csrc/s3fd.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* s3fd_size(int n, int height, int width) {
+    if (!s3_hw_ok(height, width)) return "height and width must be in 32..4096";
+    if (n < 1 || n > s3_max_images(height, width)) return "n outside 1..n3dt_s3fd_max_images (the workspace budget)";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_s3fd_packed_bytes(void) { return n3dt_s3fd_packed_layout_bytes(); }
+
+extern "C" int n3dt_s3fd_pack(const N3dtS3fdParams* p, void* packed, void* stream) {
+    if (!p || !packed) return fail(N3DT_EINVAL, "n3dt_s3fd_pack: NULL argument");
+    if (((size_t)packed) & 255) return fail(N3DT_EINVAL, "n3dt_s3fd_pack: packed must be 256-byte aligned");
+    for (int b = 0; b < N3DT_S3FD_PARAMS; ++b)
+        if (!p->weight[b] || !p->bias[b]) return fail(N3DT_EINVAL, "n3dt_s3fd_pack: NULL parameter pointer");
+    for (int l = 0; l < 3; ++l)
+        if (!p->norm_weight[l]) return fail(N3DT_EINVAL, "n3dt_s3fd_pack: NULL parameter pointer");
+    n3dt_launch_s3fd_pack(p, packed, (hipStream_t)stream);
+    return check_hip("n3dt_s3fd_pack");
+}
+
+extern "C" int n3dt_s3fd_max_images(int height, int width) {
+    if (!s3_hw_ok(height, width)) {
+        (void)fail(N3DT_EINVAL, "n3dt_s3fd_max_images: height and width must be in 32..4096");
+        return 0;
+    }
+    return s3_max_images(height, width);
+}
+
+extern "C" int n3dt_s3fd_positions(int height, int width) {
+    if (!s3_hw_ok(height, width)) {
+        (void)fail(N3DT_EINVAL, "n3dt_s3fd_positions: height and width must be in 32..4096");
+        return 0;
+    }
+    const S3Sizes s = s3_sizes(height, width);
+    return s3_positions(&s, nullptr);
+}
+
+extern "C" size_t n3dt_s3fd_workspace_bytes(int n, int height, int width) {
+    const char* what = s3fd_size(n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_s3fd_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_s3fd_ws_bytes(n, height, width);
+}
+
+extern "C" int n3dt_s3fd_heads(int n, int height, int width, const void* packed, const float* x, float* const* out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_s3fd_heads";
+    const char* what = s3fd_size(n, height, width);
+    if (!what) {
+        if (!packed || !x || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_s3fd_ws_bytes(n, height, width)) what = "workspace too small";
+        else
+            for (int i = 0; i < 12 && !what; ++i)
+                if (!out[i] || (((size_t)out[i]) & 3)) what = "out[i] NULL or not 4-byte aligned";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_s3fd_heads(n, height, width, packed, x, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_s3fd_detect(int n, int height, int width, const void* packed, const float* frames, int max_faces, double* scores,
+                                double* dets, int32_t* count, int32_t* left, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_s3fd_detect";
+    const char* what = s3fd_size(n, height, width);
+    if (!what) {
+        if (max_faces < 1 || max_faces > S3_MAX_FACES) what = "max_faces outside 1..64";
+        else if (!packed || !frames || !dets || !count || !left || !workspace) what = "NULL pointer";
+        else if ((((size_t)dets) | ((size_t)scores)) & 7) what = "dets and scores must be 8-byte aligned";
+        else if ((((size_t)frames) | ((size_t)count) | ((size_t)left)) & 3) what = "frames, count and left must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_s3fd_ws_bytes(n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_s3fd_detect(n, height, width, packed, frames, max_faces, scores, dets, count, left, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_s3fd_boxes(int n_frames, int height, int width, int max_faces, const double* dets, const int32_t* count, int pady1,
+                               int pady2, int padx1, int padx2, int smooth, int32_t* boxes, int32_t* found, int32_t* scratch, void* stream) {
+    static const char* who = "n3dt_s3fd_boxes";
+    const char* what = nullptr;
+    const int lim = 1 << 20;
+    if (n_frames < 1 || n_frames > S3_MAX_CLIP) what = "n_frames outside 1..2^20";
+    else if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
+    else if (max_faces < 1 || max_faces > S3_MAX_FACES) what = "max_faces outside 1..64";
+    else if (smooth < 0 || smooth > S3_MAX_SMOOTH) what = "smooth outside 0..64";
+    else if (pady1 < -lim || pady1 > lim || pady2 < -lim || pady2 > lim || padx1 < -lim || padx1 > lim || padx2 < -lim || padx2 > lim)
+        what = "pads outside -2^20..2^20";
+    else if (!dets || !count || !boxes || !found || !scratch) what = "NULL pointer";
+    else if (((size_t)dets) & 7) what = "dets must be 8-byte aligned";
+    else if ((((size_t)count) | ((size_t)boxes) | ((size_t)found) | ((size_t)scratch)) & 3) what = "count, boxes, found and scratch must be 4-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    const int pads[4] = {pady1, pady2, padx1, padx2};
+    n3dt_launch_s3fd_boxes(n_frames, height, width, max_faces, dets, count, pads, smooth, boxes, found, scratch, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// one block at a caller-given input size: the output must not be empty, and the maps stay inside the workspace budget
+static const char* s3fd_block_size(int block, int n, int height, int width) {
+    if (block < 0 || block >= S3_BLOCKS) return "block outside 0..32";
+    if (n < 1 || n > S3_MAX_IMAGES) return "n outside 1..1024";
+    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW + 4 || width > SN_MAX_FRAME_HW + 4) return "height and width must be in 1..4100";
+    const bool pool = block >= S3_FIRST_POOL && block < S3_FIRST_NORM;
+    if (pool && (height < 2 || width < 2)) return "a pool needs 2 x 2 pixels";
+    if (n3dt_s3fd_block_ws_bytes(block, n, height, width) > S3_WS_BUDGET) return "the block's maps exceed the workspace budget";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_s3fd_block_workspace_bytes(int block, int n, int height, int width) {
+    const char* what = s3fd_block_size(block, n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_s3fd_block_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_s3fd_block_ws_bytes(block, n, height, width);
+}
+
+extern "C" int n3dt_s3fd_block(int block, int n, int height, int width, const void* packed, const float* in, float* out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_s3fd_block";
+    const char* what = s3fd_block_size(block, n, height, width);
+    if (!what) {
+        if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)in) | ((size_t)out)) & 3) what = "in and out must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_s3fd_block_ws_bytes(block, n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_s3fd_block(block, n, height, width, packed, in, out, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -189,4 +189,17 @@ void n3dt_launch_wav2lip_paste(int n, int height, int width, const float* faces,
 void n3dt_launch_wav2lip_fwd(int n, const void* packed, const float* mel, const float* faces, float* out, void* workspace, hipStream_t st);
 void n3dt_launch_wav2lip_block(int block, int n, const void* packed, const float* in, const float* skip, float* out, void* workspace,
                                hipStream_t st);
+
+// ---- s3fd.hip
+size_t n3dt_s3fd_packed_layout_bytes(void);
+size_t n3dt_s3fd_ws_bytes(int n, int H, int W);
+size_t n3dt_s3fd_block_ws_bytes(int block, int n, int Hi, int Wi);
+void n3dt_launch_s3fd_pack(const N3dtS3fdParams* p, void* packed, hipStream_t st);
+void n3dt_launch_s3fd_heads(int n, int H, int W, const void* packed, const float* x, float* const* out, void* workspace, hipStream_t st);
+void n3dt_launch_s3fd_detect(int n, int H, int W, const void* packed, const float* frames, int max_faces, double* scores, double* dets,
+                             int* count, int* left, void* workspace, hipStream_t st);
+void n3dt_launch_s3fd_boxes(int F, int H, int W, int max_faces, const double* dets, const int* count, const int* pads, int T, int* boxes,
+                            int* found, int* scratch, hipStream_t st);
+void n3dt_launch_s3fd_block(int block, int n, int Hi, int Wi, const void* packed, const float* in, float* out, void* workspace,
+                            hipStream_t st);
 }

@@ -58,6 +58,14 @@ class Wav2lipParams(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p * WAV2LIP_BLOCKS) for name in ("weight", "bias", "bn_weight", "bn_bias", "bn_mean", "bn_var")]
 
 
+S3FD_PARAMS = 31
+S3FD_BLOCKS = 33
+
+
+class S3fdParams(ctypes.Structure):
+    _fields_ = [("weight", ctypes.c_void_p * S3FD_PARAMS), ("bias", ctypes.c_void_p * S3FD_PARAMS), ("norm_weight", ctypes.c_void_p * 3)]
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -200,6 +208,16 @@ def _signatures():
         "n3dt_wav2lip_block": (ci, [ci, ci, vp, vp, vp, vp, vp, sz, vp]),
         "n3dt_wav2lip_face_inputs": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),
         "n3dt_wav2lip_paste": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp]),
+        "n3dt_s3fd_packed_bytes": (sz, []),
+        "n3dt_s3fd_pack": (ci, [ctypes.POINTER(S3fdParams), vp, vp]),
+        "n3dt_s3fd_max_images": (ci, [ci, ci]),
+        "n3dt_s3fd_positions": (ci, [ci, ci]),
+        "n3dt_s3fd_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_s3fd_heads": (ci, [ci, ci, ci, vp, vp, ctypes.POINTER(vp), vp, sz, vp]),
+        "n3dt_s3fd_detect": (ci, [ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_s3fd_boxes": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+        "n3dt_s3fd_block_workspace_bytes": (sz, [ci, ci, ci, ci]),
+        "n3dt_s3fd_block": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
         # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
         "n3dt_flat_adam_guard_bytes": (sz, []),
         "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),

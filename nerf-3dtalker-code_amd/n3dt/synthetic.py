@@ -413,6 +413,41 @@ def wav2lip_state_dict(seed=0):
     return sd
 
 
+S3FD_INPUT_SCALE = 1.0 / 64.0
+S3FD_CONF_SCALE = 6.0
+S3FD_LOC_SCALE = 2.0
+S3FD_FACE_BIAS = (-6.988, -8.967, -3.788, -18.223, -4.062, 0.819)
+S3FD_EMPTY_FACE_BIAS = (-60.0,) * 6
+
+
+def s3fd_state_dict(seed=0, face_bias=S3FD_FACE_BIAS):
+    """Seeded stand-in for the weights of the S3FD face detector (`s3fd-619a316812.pth` cannot be fetched offline), under the keys
+    of the reference's `net_s3fd.s3fd` (n3dt.s3fd.load_s3fd).  He-scaled -- N(0, 2 / fan_in) weights, biases N(0.1, 0.05^2) -- so
+    that 19 ReLU layers keep O(1) activations; conv1_1, which sees 255 u - mean, is scaled by S3FD_INPUT_SCALE on top.  L2Norm
+    weights are the reference's scales (10, 8, 5) times U(0.75, 1.25).  The heads are N(0, 1 / fan_in) times S3FD_CONF_SCALE /
+    S3FD_LOC_SCALE with N(0, 0.5^2) biases, and `face_bias[l]` is added to the bias of level l's face channel (the last conf
+    channel): S3FD_FACE_BIAS leaves a few per cent of the head positions above the 0.5 score threshold on the fixture's frames,
+    S3FD_EMPTY_FACE_BIAS none.  Never stored."""
+    from .s3fd import CONVS, LEVEL_C, LEVEL_CONF, LEVEL_SOURCES, NORMS
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for i, (name, cin, cout, k, _, _, _, _) in enumerate(CONVS):
+        std = math.sqrt(2.0 / (cin * k * k)) * (S3FD_INPUT_SCALE if i == 0 else 1.0)
+        sd[name + ".weight"] = torch.randn(cout, cin, k, k, generator=gen) * std
+        sd[name + ".bias"] = 0.1 + 0.05 * torch.randn(cout, generator=gen)
+    for name, c, scale in zip(NORMS, LEVEL_C, (10.0, 8.0, 5.0)):
+        sd[name + ".weight"] = scale * (0.75 + 0.5 * torch.rand(c, generator=gen))
+    for src, c, conf, fb in zip(LEVEL_SOURCES, LEVEL_C, LEVEL_CONF, face_bias):
+        std = math.sqrt(1.0 / (c * 9))
+        sd[src + "_mbox_conf.weight"] = torch.randn(conf, c, 3, 3, generator=gen) * std * S3FD_CONF_SCALE
+        bias = 0.5 * torch.randn(conf, generator=gen)
+        bias[conf - 1] += fb
+        sd[src + "_mbox_conf.bias"] = bias
+        sd[src + "_mbox_loc.weight"] = torch.randn(4, c, 3, 3, generator=gen) * std * S3FD_LOC_SCALE
+        sd[src + "_mbox_loc.bias"] = 0.5 * torch.randn(4, generator=gen)
+    return sd
+
+
 def mel_batch(B, seed=0):
     """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
     range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""
