@@ -59,14 +59,18 @@ static A2sSaved a2s_saved(float* b, int T) {
     for (int k = 0; k < 2; ++k) { s.Y[k] = b; b += a2s_lin_out[k] * t; }
     return s;
 }
+// Workspace: XP[l] [2][T][2560] (layer l's input projections, forward) and DC[l] [2][T][640] (its cell-state gradients) per
+// LSTM layer, then DH1, DH0 [T][1280], DZ3 [T][64], DY2 [T][320], DY1 [T][640]: 16384 T floats.  The backward writes layer l's
+// pre-activation gradients DG[l] over XP[l] (the forward is done with it), so after a forward + backward every intermediate of
+// both layers is still there: XP[l] after n3dt_a2s_fwd, DG[l] and DC[l] after n3dt_a2s_bwd.
 struct A2sWs {
-    float *XP, *DC, *DH1, *DH0, *DZ3, *DY2, *DY1;  // XP (forward) and the dgates (backward) share one region
+    float *XP[2], *DC[2], *DH1, *DH0, *DZ3, *DY2, *DY1;
 };
 static A2sWs a2s_ws(float* b, int T) {
     A2sWs w;
     const long t = T;
-    w.XP = b;  b += 2 * A2S_G * t;
-    w.DC = b;  b += 2 * A2S_H * t;
+    for (int l = 0; l < 2; ++l) { w.XP[l] = b; b += 2 * A2S_G * t; }
+    for (int l = 0; l < 2; ++l) { w.DC[l] = b; b += 2 * A2S_H * t; }
     w.DH1 = b; b += 2 * A2S_H * t;
     w.DH0 = b; b += 2 * A2S_H * t;
     w.DZ3 = b; b += 64 * t;
@@ -76,7 +80,7 @@ static A2sWs a2s_ws(float* b, int T) {
 }
 
 extern "C" size_t n3dt_a2s_saved_floats(int T) { return (size_t)T * (A2S_IN + 4 * A2S_H + 4 * A2S_G + 4 * A2S_H + 2 * 1024 + 960); }
-extern "C" size_t n3dt_a2s_ws_floats(int T) { return (size_t)T * (2 * A2S_G + 6 * A2S_H + 1024); }
+extern "C" size_t n3dt_a2s_ws_floats(int T) { return (size_t)T * (4 * A2S_G + 8 * A2S_H + 1024); }
 
 __device__ __forceinline__ float a2s_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -261,12 +265,12 @@ extern "C" void n3dt_launch_a2s_fwd(int T, const N3dtA2sParams* p, const float* 
     for (int l = 0; l < 2; ++l) {
         const float* X = l ? sv.H[0] : sv.X0;
         for (int d = 0; d < 2; ++d) {
-            Gemm32 g = a2s_mm(T, A2S_G, A2S_IN, X, A2S_IN, 0, p->w_ih[2 * l + d], A2S_IN, 0, w.XP + (long)d * T * A2S_G, A2S_G);
+            Gemm32 g = a2s_mm(T, A2S_G, A2S_IN, X, A2S_IN, 0, p->w_ih[2 * l + d], A2S_IN, 0, w.XP[l] + (long)d * T * A2S_G, A2S_G);
             g.bias = p->b_ih[2 * l + d];
             n3dt_gemm32(g, st);
         }
         for (int s = 0; s < T; ++s)
-            hipLaunchKernelGGL(a2s_step_fwd, dim3(2 * A2S_NB), dim3(256), 0, st, T, s, w.XP, p->w_hh[2 * l], p->w_hh[2 * l + 1],
+            hipLaunchKernelGGL(a2s_step_fwd, dim3(2 * A2S_NB), dim3(256), 0, st, T, s, w.XP[l], p->w_hh[2 * l], p->w_hh[2 * l + 1],
                                p->b_hh[2 * l], p->b_hh[2 * l + 1], sv.H[l], sv.G[l], sv.C[l]);
     }
     const float* X = sv.H[1];
@@ -300,12 +304,12 @@ extern "C" void n3dt_launch_a2s_bwd(int T, const N3dtA2sParams* p, const float* 
         n3dt_gemm32(a2s_mm(T, ni, no, dz[k], no, 0, p->lin_w[k], ni, 1, dx_out[k], ni), st);
         dy = dx_out[k];
     }
-    float* DG = w.XP;
     for (int l = 1; l >= 0; --l) {
+        float* DG = w.XP[l];
         const float* dHout = l ? w.DH1 : w.DH0;
         for (int s = 0; s < T; ++s)
             hipLaunchKernelGGL(a2s_step_bwd, dim3(2 * A2S_NB), dim3(256), 0, st, T, s, p->w_hh[2 * l], p->w_hh[2 * l + 1], sv.G[l], sv.C[l],
-                               dHout, DG, w.DC);
+                               dHout, DG, w.DC[l]);
         const float* X = l ? sv.H[0] : sv.X0;
         for (int d = 0; d < 2; ++d) {
             const int k = 2 * l + d;
