@@ -553,6 +553,58 @@ size_t n3dt_s3fd_block_workspace_bytes(int block, int n, int height, int width);
 int n3dt_s3fd_block(int block, int n, int height, int width, const void* packed, const float* in, float* out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- 3-D face reconstruction net: frames to expression codes -------------------------------------
+ * The reference's net_recon (s_face3d/models/networks.py: ReconNetWrapper over resnet50, use_last_fc=False) behind the crop of
+ * s_face3d/util/preprocess.py's align_img as CropAndExtract.generate calls it, frozen and inference-only, with the caller's
+ * weights.  csrc/face_recon.hip; the table and the run-time geometry are csrc/face_recon_core.h.  Blocks for the single-block
+ * entry: 0..52 the convolutions in state-dict order (conv1; per bottleneck conv1, conv2, conv3 and, in a layer's first,
+ * downsample.0), each with its BatchNorm folded in and its ReLU (none behind a downsample); 53 the 3 x 3 / 2 max pool; 54 the
+ * global average; 55 the 257-column head (the seven final_layers as one matrix: id 80, exp 64, tex 80, angle 3, gamma 27,
+ * (tx, ty) 2, tz 1).
+ * pack: weight[53] [C_out, C_in, k, k]; bn_weight / bn_bias / bn_mean / bn_var [53] [C_out] and bn_eps[53] (host doubles): eval-mode
+ *   BatchNorm2d folded into weight and bias in float64; head_weight[7] [cols, 2048], head_bias[7] [cols].
+ * fwd: x [n,3,height,width] fp32 (the reference feeds RGB in [0,1]) -> out [n,257].
+ * block: in [n,C_in,height,width] -> out [n,C_out,Ho,Wo]; a bottleneck's third convolution takes the identity as skip
+ *   [n,C_out,Ho,Wo] and gives relu(conv + skip), every other block takes skip = NULL; 54 gives [n,2048] and 55 takes [n,2048]
+ *   (height = width = 1) and gives [n,257].
+ * align: frames [n,3,height,width] fp32 RGB in [0,1] (clamped, NaN -> 0) and landmarks [n,points,2] float64 image pixels, points 68
+ *   or 5 (NULL: every frame gets the fallback a frame whose landmarks average exactly -1 gets) -> crops [n,3,224,224] fp32 in
+ *   [0,1], the crop align_img cuts from PIL's BICUBIC resize (quantize 1: through bytes as PIL's byte path rounds; 0: nothing
+ *   rounded); trans_params [n,5] float64 (w0, h0, s, t0, t1); geom [n,4] int32 (w, h, left, up); status [n] int32, 1 for
+ *   non-finite landmarks, w or h < 1 or s outside [1/16, 16] (such a frame's crop is zeros).  lm3d_std [5,3] and pinv [4,5], the
+ *   pseudo-inverse of [lm3d_std, 1], float64 on the device.
+ * An image's results depend on that image and the packed weights alone and are bitwise reproducible.  Everything is enqueued on
+ * `stream`, nothing synchronises, no atomics.  workspace: 256-byte aligned, never cleared, contents immaterial between calls.
+ * Limits (N3DT_EINVAL before anything is enqueued; the size queries return 0 and set n3dt_last_error): fwd 32 <= height, width <=
+ * 4096; 1 <= n <= the result of the max_images query (a 4 GiB workspace budget, at most 1024); align 2 <= height, width <= 4096,
+ * 1 <= n <= 2^20. */
+#define N3DT_FACE_RECON_CONVS 53
+#define N3DT_FACE_RECON_HEADS 7
+#define N3DT_FACE_RECON_BLOCKS 56
+#define N3DT_FACE_RECON_COEFFS 257
+typedef struct N3dtFaceReconParams {
+    const float* weight[N3DT_FACE_RECON_CONVS];
+    const float* bn_weight[N3DT_FACE_RECON_CONVS];
+    const float* bn_bias[N3DT_FACE_RECON_CONVS];
+    const float* bn_mean[N3DT_FACE_RECON_CONVS];
+    const float* bn_var[N3DT_FACE_RECON_CONVS];
+    double bn_eps[N3DT_FACE_RECON_CONVS];
+    const float* head_weight[N3DT_FACE_RECON_HEADS];
+    const float* head_bias[N3DT_FACE_RECON_HEADS];
+} N3dtFaceReconParams;
+size_t n3dt_face_recon_packed_bytes(void);
+int n3dt_face_recon_pack(const N3dtFaceReconParams* p, void* packed, void* stream);
+int n3dt_face_recon_max_images(int height, int width);
+size_t n3dt_face_recon_workspace_bytes(int n, int height, int width);
+int n3dt_face_recon_fwd(int n, int height, int width, const void* packed, const float* x, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t n3dt_face_recon_block_workspace_bytes(int block, int n, int height, int width);
+int n3dt_face_recon_block(int block, int n, int height, int width, const void* packed, const float* in, const float* skip, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int n3dt_face_recon_align(int n, int height, int width, const float* frames, const double* landmarks, int points, const double* lm3d_std,
+                          const double* pinv, int quantize, float* crops, double* trans_params, int32_t* geom, int32_t* status,
+                          void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

@@ -19,6 +19,7 @@
 #include "syncnet_core.h"
 #include "wav2lip_core.h"
 #include "s3fd_core.h"
+#include "face_recon_core.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1001,6 +1002,118 @@ extern "C" int n3dt_s3fd_block(int block, int n, int height, int width, const vo
     }
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_s3fd_block(block, n, height, width, packed, in, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// The 3-D face reconstruction net (csrc/face_recon.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* face_recon_size(int n, int height, int width) {
+    if (!fr_hw_ok(height, width)) return "height and width must be in 32..4096";
+    if (n < 1 || n > fr_max_images(height, width)) return "n outside 1..n3dt_face_recon_max_images (the workspace budget)";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_face_recon_packed_bytes(void) { return n3dt_face_recon_packed_layout_bytes(); }
+
+extern "C" int n3dt_face_recon_pack(const N3dtFaceReconParams* p, void* packed, void* stream) {
+    static const char* who = "n3dt_face_recon_pack";
+    if (!p || !packed) return failf(N3DT_EINVAL, "%s: NULL argument", who);
+    if (((size_t)packed) & 255) return failf(N3DT_EINVAL, "%s: packed must be 256-byte aligned", who);
+    for (int j = 0; j < N3DT_FACE_RECON_CONVS; ++j) {
+        if (!p->weight[j] || !p->bn_weight[j] || !p->bn_bias[j] || !p->bn_mean[j] || !p->bn_var[j])
+            return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+        if (!(p->bn_eps[j] > 0.0) || !(p->bn_eps[j] < 1.0)) return failf(N3DT_EINVAL, "%s: bn_eps outside (0, 1)", who);
+    }
+    for (int i = 0; i < N3DT_FACE_RECON_HEADS; ++i)
+        if (!p->head_weight[i] || !p->head_bias[i]) return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+    n3dt_launch_face_recon_pack(p, packed, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_face_recon_max_images(int height, int width) {
+    if (!fr_hw_ok(height, width)) {
+        (void)fail(N3DT_EINVAL, "n3dt_face_recon_max_images: height and width must be in 32..4096");
+        return 0;
+    }
+    return fr_max_images(height, width);
+}
+
+extern "C" size_t n3dt_face_recon_workspace_bytes(int n, int height, int width) {
+    const char* what = face_recon_size(n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_face_recon_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_face_recon_ws_bytes(n, height, width);
+}
+
+extern "C" int n3dt_face_recon_fwd(int n, int height, int width, const void* packed, const float* x, float* out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_face_recon_fwd";
+    const char* what = face_recon_size(n, height, width);
+    if (!what) {
+        if (!packed || !x || !out || !workspace) what = "NULL pointer";
+        else if ((((size_t)x) | ((size_t)out)) & 3) what = "x and out must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_face_recon_ws_bytes(n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_face_recon_fwd(n, height, width, packed, x, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// one block at a caller-given input size: the output must not be empty, and the maps stay inside the workspace budget
+static const char* face_recon_block_size(int block, int n, int height, int width) {
+    if (block < 0 || block >= FR_BLOCKS) return "block outside 0..55";
+    if (n < 1 || n > FR_MAX_IMAGES) return "n outside 1..1024";
+    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (block == 0 && (height < 2 || width < 2)) return "the stem needs 2 x 2 pixels";
+    if (block == FR_HEAD_BLOCK && (height != 1 || width != 1)) return "the head takes height = width = 1";
+    if (n3dt_face_recon_block_ws_bytes(block, n, height, width) > FR_WS_BUDGET) return "the block's maps exceed the workspace budget";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_face_recon_block_workspace_bytes(int block, int n, int height, int width) {
+    const char* what = face_recon_block_size(block, n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_face_recon_block_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_face_recon_block_ws_bytes(block, n, height, width);
+}
+
+extern "C" int n3dt_face_recon_block(int block, int n, int height, int width, const void* packed, const float* in, const float* skip,
+                                     float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_face_recon_block";
+    const char* what = face_recon_block_size(block, n, height, width);
+    if (!what) {
+        const bool third = block < FR_CONVS && fr_conv(block).role == FR_CONV3;
+        if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if (third && !skip) what = "a bottleneck's third convolution takes the identity as skip";
+        else if (!third && skip) what = "only a bottleneck's third convolution takes a skip";
+        else if ((((size_t)in) | ((size_t)out) | ((size_t)skip)) & 3) what = "in, skip and out must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_face_recon_block_ws_bytes(block, n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_face_recon_block(block, n, height, width, packed, in, skip, out, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_face_recon_align(int n, int height, int width, const float* frames, const double* landmarks, int points,
+                                     const double* lm3d_std, const double* pinv, int quantize, float* crops, double* trans_params,
+                                     int32_t* geom, int32_t* status, void* stream) {
+    static const char* who = "n3dt_face_recon_align";
+    const char* what = nullptr;
+    if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
+    else if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
+    else if (landmarks && points != 68 && points != 5) what = "points must be 68 or 5";
+    else if (!frames || !lm3d_std || !pinv || !crops || !trans_params || !geom || !status) what = "NULL pointer";
+    else if ((((size_t)landmarks) | ((size_t)lm3d_std) | ((size_t)pinv) | ((size_t)trans_params)) & 7)
+        what = "landmarks, lm3d_std, pinv and trans_params must be 8-byte aligned";
+    else if ((((size_t)frames) | ((size_t)crops) | ((size_t)geom) | ((size_t)status)) & 3) what = "frames, crops, geom and status must be 4-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_face_recon_align(n, height, width, frames, landmarks, points, lm3d_std, pinv, quantize ? 1 : 0, crops, trans_params, geom, status,
+                                 (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -202,4 +202,16 @@ void n3dt_launch_s3fd_boxes(int F, int H, int W, int max_faces, const double* de
                             int* found, int* scratch, hipStream_t st);
 void n3dt_launch_s3fd_block(int block, int n, int Hi, int Wi, const void* packed, const float* in, float* out, void* workspace,
                             hipStream_t st);
+
+// ---- face_recon.hip
+size_t n3dt_face_recon_packed_layout_bytes(void);
+size_t n3dt_face_recon_ws_bytes(int n, int H, int W);
+size_t n3dt_face_recon_block_ws_bytes(int block, int n, int Hi, int Wi);
+void n3dt_launch_face_recon_pack(const N3dtFaceReconParams* p, void* packed, hipStream_t st);
+void n3dt_launch_face_recon_fwd(int n, int H, int W, const void* packed, const float* x, float* out, void* workspace, hipStream_t st);
+void n3dt_launch_face_recon_block(int block, int n, int Hi, int Wi, const void* packed, const float* in, const float* skip, float* out,
+                                  void* workspace, hipStream_t st);
+void n3dt_launch_face_recon_align(int n, int H, int W, const float* frames, const double* landmarks, int points, const double* lm3d_std,
+                                  const double* pinv, int quantize, float* crops, double* trans_params, int* geom, int* status,
+                                  hipStream_t st);
 }

@@ -66,6 +66,18 @@ class S3fdParams(ctypes.Structure):
     _fields_ = [("weight", ctypes.c_void_p * S3FD_PARAMS), ("bias", ctypes.c_void_p * S3FD_PARAMS), ("norm_weight", ctypes.c_void_p * 3)]
 
 
+FACE_RECON_CONVS = 53
+FACE_RECON_HEADS = 7
+FACE_RECON_BLOCKS = 56
+FACE_RECON_COEFFS = 257
+
+
+class FaceReconParams(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_void_p * FACE_RECON_CONVS) for name in ("weight", "bn_weight", "bn_bias", "bn_mean", "bn_var")] +
+                [("bn_eps", ctypes.c_double * FACE_RECON_CONVS), ("head_weight", ctypes.c_void_p * FACE_RECON_HEADS),
+                 ("head_bias", ctypes.c_void_p * FACE_RECON_HEADS)])
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -218,6 +230,14 @@ def _signatures():
         "n3dt_s3fd_boxes": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "n3dt_s3fd_block_workspace_bytes": (sz, [ci, ci, ci, ci]),
         "n3dt_s3fd_block": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+        "n3dt_face_recon_packed_bytes": (sz, []),
+        "n3dt_face_recon_pack": (ci, [ctypes.POINTER(FaceReconParams), vp, vp]),
+        "n3dt_face_recon_max_images": (ci, [ci, ci]),
+        "n3dt_face_recon_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_face_recon_fwd": (ci, [ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+        "n3dt_face_recon_block_workspace_bytes": (sz, [ci, ci, ci, ci]),
+        "n3dt_face_recon_block": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_face_recon_align": (ci, [ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]),
         # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
         "n3dt_flat_adam_guard_bytes": (sz, []),
         "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),

@@ -448,6 +448,47 @@ def s3fd_state_dict(seed=0, face_bias=S3FD_FACE_BIAS):
     return sd
 
 
+FACE_RECON_BN3_GAMMA = 0.5
+FACE_RECON_HEAD_SCALE = 1.0
+
+
+def face_recon_state_dict(seed=0):
+    """Seeded stand-in for the weights of the 3-D face reconstruction net (the pretrained `net_recon` checkpoint cannot be fetched
+    offline), under the keys of the reference's `ReconNetWrapper('resnet50', use_last_fc=False)` (n3dt.face_recon.load_face_recon).
+    Convolutions are He-scaled, N(0, 2 / fan_in).  BatchNorm statistics are near the identity -- running_mean N(0, 0.1^2),
+    running_var U(0.75, 1.25), beta N(0.1, 0.1^2), gamma U(0.75, 1.25) -- except that the last BatchNorm of a residual branch and a
+    downsample branch's carry gamma times FACE_RECON_BN3_GAMMA and sqrt(1 - FACE_RECON_BN3_GAMMA^2): sixteen residual additions
+    then neither blow the activations up nor let the branch die.  The seven final_layers, which the reference initialises to
+    zero, are N(0, 1 / 2048) times FACE_RECON_HEAD_SCALE with N(0, 0.5^2) biases.  Never stored."""
+    from .face_recon import CONVS, FEAT, HEAD_COLS
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for conv, bn, cin, cout, k, _, _, role, _ in CONVS:
+        sd[conv + ".weight"] = torch.randn(cout, cin, k, k, generator=gen) * math.sqrt(2.0 / (cin * k * k))
+        gamma = 0.75 + 0.5 * torch.rand(cout, generator=gen)
+        if role == 3:
+            gamma = gamma * FACE_RECON_BN3_GAMMA
+        elif role == 4:
+            gamma = gamma * math.sqrt(1.0 - FACE_RECON_BN3_GAMMA ** 2)
+        sd[bn + ".weight"] = gamma
+        sd[bn + ".bias"] = 0.1 + 0.1 * torch.randn(cout, generator=gen)
+        sd[bn + ".running_mean"] = 0.1 * torch.randn(cout, generator=gen)
+        sd[bn + ".running_var"] = 0.75 + 0.5 * torch.rand(cout, generator=gen)
+        sd[bn + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    for i, cols in enumerate(HEAD_COLS):
+        sd["final_layers.%d.weight" % i] = torch.randn(cols, FEAT, 1, 1, generator=gen) * (FACE_RECON_HEAD_SCALE / math.sqrt(FEAT))
+        sd["final_layers.%d.bias" % i] = 0.5 * torch.randn(cols, generator=gen)
+    return sd
+
+
+def face_recon_lm3d():
+    """A stand-in for the [5,3] standard landmarks the reference's load_lm3d reads from its BFM folder (left eye, right eye, nose,
+    left and right mouth corner; float64): a plausible face for smoke runs and timing, NOT the reference's values -- those the
+    caller supplies."""
+    return torch.tensor([[-0.31, 0.29, 0.03], [0.31, 0.29, 0.03], [0.0, 0.03, 0.45], [-0.25, -0.33, 0.12], [0.25, -0.33, 0.12]],
+                        dtype=torch.float64).numpy()
+
+
 def mel_batch(B, seed=0):
     """Seeded stand-in for the mel windows the reference's data loader hands Audio2style: [B, 80, 16] float32 in [-4, 4) (the
     range of Wav2Lip's normalised log-mel), quantised to 1/32 so that the values are exact in every precision."""
