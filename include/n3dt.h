@@ -605,6 +605,58 @@ int n3dt_face_recon_align(int n, int height, int width, const float* frames, con
                           const double* pinv, int quantize, float* crops, double* trans_params, int32_t* geom, int32_t* status,
                           void* stream);
 
+/* ---- AWing FAN landmark detector: frames to 68 landmarks ---------------------------------------------
+ * The reference's KeypointExtractor network (s_face3d/util/my_awing_arch.py: FAN over HourGlass / ConvBlock / CoordConvTh, with
+ * calculate_points as get_landmarks calls it), frozen and inference-only, with the caller's weights.  csrc/fan.hip; the table, the
+ * launch plan and the index rules are csrc/fan_core.h.  num_modules 1..4 stacks, num_landmarks N in 1..127.
+ * Convolutions (weight[j] and its companions): 0 the stem CoordConv; 1..4 conv2's conv1, conv2, conv3, downsample.2; 5..7 conv3's;
+ *   8..11 conv4's; then 47 per stack: the hourglass coordconv, 14 ConvBlocks of 3 (the hourglass's 13 in state-dict order, then
+ *   top_m), conv_last, l, bl, al (the last stack has neither bl nor al: NULL).  bias[j]: the convolution's bias or NULL.  bn_*[j]:
+ *   the BatchNorm in FRONT of a ConvBlock's convolution (downsample.0), or the one BEHIND the stem (bn1) and conv_last (bn_end),
+ *   else NULL; eps 1e-5.  coords256 [3,256,256] and coords64 [3,64,64]: the xx, yy, rr channels as AddCoordsTh computes them in fp32.
+ * Blocks of the single-block entry: 0 the stem (256 x 256 only), 1..3 the ConvBlocks conv2..conv4, 4 the 2 x 2 average pool (256
+ *   channels, even sizes), 5 the upsample-add (in: the lower map; skip: the upper, twice as large); then 19 per stack: coordconv (64 x
+ *   64 only; from the second stack on it takes gates [n,4096]), the 13 hourglass ConvBlocks, top_m, conv_last (+ bn_end + ReLU), l,
+ *   bl (skip: previous), al (skip: previous + bl).
+ * fwd: x [n,3,256,256] fp32 BGR in [0,1] -> heat [num_modules][n,N+1,64,64].  gates uint8 [n, max(num_modules-1,1), 4096]:
+ *   compute_gates 1 writes clamp(previous heat map's last channel, 0, 1) > 0.05f there, 0 reads what the caller left.
+ * crops: frames [n,3,height,width] fp32 RGB + boxes [n,4] int32 (y1, y2, x1, x2) -> [n,3,256,256] BGR, bilinear, half-pixel
+ *   centres; a box with a negative start, an empty extent or an end outside the frame gives zeros.
+ * points: heat, landmark l of frame f at heat + f * frame_stride + l * 4096, -> pts [n,N,2] float64 (x, y) in heat-map cells and
+ *   status [n] (2: a landmark's argmax is cell 4095, where the reference raises IndexError; the frame's points are -1).
+ * tail: pts, that status and the boxes -> out [n,P,2] float64 image pixels and status (| 4 for a bad box; such a frame is -1).
+ *   table [P][2] int32 NOT NULL: P output points, each the mean of two of the N rounded to fp32, the origin added in fp32; NULL:
+ *   P = N, float64 throughout.  carry 1: a failed frame takes the last frame before it that did not fail.
+ * An image's results depend on that image, its gates and the packed weights alone and are bitwise reproducible.  Everything is
+ * enqueued on `stream`, nothing synchronises, no atomics.  workspace: 256-byte aligned, never cleared. */
+#define N3DT_FAN_MAX_CONVS 200
+#define N3DT_FAN_MAX_BLOCKS 82
+typedef struct N3dtFanParams {
+    int32_t num_modules, num_landmarks;
+    const float* weight[N3DT_FAN_MAX_CONVS];
+    const float* bias[N3DT_FAN_MAX_CONVS];
+    const float* bn_weight[N3DT_FAN_MAX_CONVS];
+    const float* bn_bias[N3DT_FAN_MAX_CONVS];
+    const float* bn_mean[N3DT_FAN_MAX_CONVS];
+    const float* bn_var[N3DT_FAN_MAX_CONVS];
+    const float* coords256;
+    const float* coords64;
+} N3dtFanParams;
+size_t n3dt_fan_packed_bytes(int num_modules, int num_landmarks);
+int n3dt_fan_pack(const N3dtFanParams* p, void* packed, void* stream);
+int n3dt_fan_max_images(int num_modules, int num_landmarks);
+size_t n3dt_fan_workspace_bytes(int num_modules, int num_landmarks, int n);
+int n3dt_fan_fwd(int num_modules, int num_landmarks, int end_relu, int n, const void* packed, const float* x, int compute_gates,
+                 uint8_t* gates, float* heat, void* workspace, size_t workspace_bytes, void* stream);
+size_t n3dt_fan_block_workspace_bytes(int block, int num_modules, int num_landmarks, int n, int height, int width);
+int n3dt_fan_block(int block, int num_modules, int num_landmarks, int end_relu, int n, int height, int width, const void* packed,
+                   const float* in, const float* skip, const uint8_t* gates, float* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int n3dt_fan_crops(int n, int height, int width, const float* frames, const int32_t* boxes, float* out, void* stream);
+int n3dt_fan_points(int n, int num_landmarks, const float* heat, int64_t frame_stride, double* pts, int32_t* status, void* stream);
+int n3dt_fan_tail(int n, int num_landmarks, int points_out, int height, int width, const double* pts, const int32_t* decode_status,
+                  const int32_t* boxes, const int32_t* table, int carry, double* out, int32_t* status, void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

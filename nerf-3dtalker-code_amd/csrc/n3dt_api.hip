@@ -20,6 +20,7 @@
 #include "wav2lip_core.h"
 #include "s3fd_core.h"
 #include "face_recon_core.h"
+#include "fan_core.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1114,6 +1115,171 @@ extern "C" int n3dt_face_recon_align(int n, int height, int width, const float* 
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_face_recon_align(n, height, width, frames, landmarks, points, lm3d_std, pinv, quantize ? 1 : 0, crops, trans_params, geom, status,
                                  (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// The AWing FAN landmark detector (csrc/fan.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* fan_net(int modules, int N) {
+    if (modules < 1 || modules > FAN_MAX_MODULES) return "num_modules outside 1..4";
+    if (N < 1 || N > FAN_MAX_LANDMARKS) return "num_landmarks outside 1..127";
+    return nullptr;
+}
+
+static int fan_max_images(int modules, int N) {
+    const size_t one = n3dt_fan_ws_bytes(modules, N, 1);
+    const size_t n = FAN_WS_BUDGET / one;
+    return (int)(n > FAN_MAX_IMAGES ? FAN_MAX_IMAGES : n);
+}
+
+extern "C" size_t n3dt_fan_packed_bytes(int num_modules, int num_landmarks) {
+    const char* what = fan_net(num_modules, num_landmarks);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_fan_packed_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_fan_packed_layout_bytes(num_modules, num_landmarks);
+}
+
+extern "C" int n3dt_fan_pack(const N3dtFanParams* p, void* packed, void* stream) {
+    static const char* who = "n3dt_fan_pack";
+    if (!p || !packed) return failf(N3DT_EINVAL, "%s: NULL argument", who);
+    const char* what = fan_net(p->num_modules, p->num_landmarks);
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    if (((size_t)packed) & 255) return failf(N3DT_EINVAL, "%s: packed must be 256-byte aligned", who);
+    if (!p->coords256 || !p->coords64) return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+    for (int j = 0; j < fan_convs(p->num_modules); ++j) {
+        if (!fan_conv_exists(j, p->num_modules)) continue;
+        const FanConv c = fan_conv(j, p->num_landmarks);
+        if (!p->weight[j] || (c.bias && !p->bias[j])) return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+        if ((c.pre || c.post) && (!p->bn_weight[j] || !p->bn_bias[j] || !p->bn_mean[j] || !p->bn_var[j]))
+            return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+    }
+    n3dt_launch_fan_pack(p, packed, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_fan_max_images(int num_modules, int num_landmarks) {
+    const char* what = fan_net(num_modules, num_landmarks);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_fan_max_images: %s", what);
+        return 0;
+    }
+    return fan_max_images(num_modules, num_landmarks);
+}
+
+static const char* fan_size(int modules, int N, int n) {
+    const char* what = fan_net(modules, N);
+    if (what) return what;
+    if (n < 1 || n > fan_max_images(modules, N)) return "n outside 1..n3dt_fan_max_images (the workspace budget)";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_fan_workspace_bytes(int num_modules, int num_landmarks, int n) {
+    const char* what = fan_size(num_modules, num_landmarks, n);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_fan_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_fan_ws_bytes(num_modules, num_landmarks, n);
+}
+
+extern "C" int n3dt_fan_fwd(int num_modules, int num_landmarks, int end_relu, int n, const void* packed, const float* x, int compute_gates,
+                            uint8_t* gates, float* heat, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_fan_fwd";
+    const char* what = fan_size(num_modules, num_landmarks, n);
+    if (!what) {
+        if (!packed || !x || !heat || !workspace || !gates) what = "NULL pointer";
+        else if ((((size_t)x) | ((size_t)heat)) & 3) what = "x and heat must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_fan_ws_bytes(num_modules, num_landmarks, n)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_fan_fwd(num_modules, num_landmarks, end_relu ? 1 : 0, n, packed, x, compute_gates ? 1 : 0, gates, heat, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+static const char* fan_block_size(int block, int modules, int N, int n, int height, int width) {
+    const char* what = fan_net(modules, N);
+    if (what) return what;
+    if (!fan_block_exists(block, modules)) return "no such block (the last stack has neither bl nor al)";
+    if (n < 1 || n > FAN_MAX_IMAGES) return "n outside 1..1024";
+    if (height < 1 || width < 1 || height > 1024 || width > 1024) return "height and width must be in 1..1024";
+    const FanBlock k = fan_block(block, N);
+    if (k.fixed_hw && (height != k.fixed_hw || width != k.fixed_hw)) return "a CoordConv takes its own geometry only (the stem 256 x 256, a stack's 64 x 64)";
+    if (block == FAN_POOL_BLOCK && ((height | width) & 1)) return "the pool takes even sizes";
+    if (n3dt_fan_block_ws_bytes(block, N, n, height, width) > FAN_WS_BUDGET) return "the block's maps exceed the workspace budget";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_fan_block_workspace_bytes(int block, int num_modules, int num_landmarks, int n, int height, int width) {
+    const char* what = fan_block_size(block, num_modules, num_landmarks, n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_fan_block_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_fan_block_ws_bytes(block, num_landmarks, n, height, width);
+}
+
+extern "C" int n3dt_fan_block(int block, int num_modules, int num_landmarks, int end_relu, int n, int height, int width, const void* packed,
+                              const float* in, const float* skip, const uint8_t* gates, float* out, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    static const char* who = "n3dt_fan_block";
+    const char* what = fan_block_size(block, num_modules, num_landmarks, n, height, width);
+    if (!what) {
+        const FanBlock k = fan_block(block, num_landmarks);
+        const bool gated = k.fixed_hw == FAN_HEAT && block >= FAN_FRONT_BLOCKS + FAN_STACK_BLOCKS;
+        if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if (k.takes_skip && !skip) what = "this block takes a skip";
+        else if (!k.takes_skip && skip) what = "this block takes no skip";
+        else if (gated && !gates) what = "a coordconv behind the first stack takes gates";
+        else if (!gated && gates) what = "this block takes no gates";
+        else if ((((size_t)in) | ((size_t)out) | ((size_t)skip)) & 3) what = "in, skip and out must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_fan_block_ws_bytes(block, num_landmarks, n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_fan_block(block, num_modules, num_landmarks, end_relu ? 1 : 0, n, height, width, packed, in, skip, gates, out, workspace,
+                          (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_fan_crops(int n, int height, int width, const float* frames, const int32_t* boxes, float* out, void* stream) {
+    static const char* who = "n3dt_fan_crops";
+    const char* what = nullptr;
+    if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
+    else if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
+    else if (!frames || !boxes || !out) what = "NULL pointer";
+    else if ((((size_t)frames) | ((size_t)boxes) | ((size_t)out)) & 3) what = "frames, boxes and out must be 4-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_fan_crops(n, height, width, frames, boxes, out, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_fan_points(int n, int num_landmarks, const float* heat, int64_t frame_stride, double* pts, int32_t* status, void* stream) {
+    static const char* who = "n3dt_fan_points";
+    const char* what = nullptr;
+    if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
+    else if (num_landmarks < 1 || num_landmarks > FAN_MAX_LANDMARKS) what = "num_landmarks outside 1..127";
+    else if (frame_stride < (int64_t)num_landmarks * FAN_CELLS) what = "frame_stride below num_landmarks * 4096";
+    else if (!heat || !pts || !status) what = "NULL pointer";
+    else if ((((size_t)heat) | ((size_t)status)) & 3 || ((size_t)pts) & 7) what = "heat and status must be 4-byte, pts 8-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_fan_points(n, num_landmarks, heat, frame_stride, pts, status, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_fan_tail(int n, int num_landmarks, int points_out, int height, int width, const double* pts, const int32_t* decode_status,
+                             const int32_t* boxes, const int32_t* table, int carry, double* out, int32_t* status, void* stream) {
+    static const char* who = "n3dt_fan_tail";
+    const char* what = nullptr;
+    if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
+    else if (num_landmarks < 1 || num_landmarks > FAN_MAX_LANDMARKS) what = "num_landmarks outside 1..127";
+    else if (points_out < 1 || points_out > 1024 || (!table && points_out != num_landmarks)) what = "points_out outside 1..1024, or not num_landmarks without a table";
+    else if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
+    else if (!pts || !decode_status || !boxes || !out || !status) what = "NULL pointer";
+    else if ((((size_t)pts) | ((size_t)out)) & 7) what = "pts and out must be 8-byte aligned";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_fan_tail(n, num_landmarks, points_out, height, width, pts, decode_status, boxes, table, carry ? 1 : 0, out, status, (hipStream_t)stream);
     return check_hip(who);
 }
 

@@ -214,4 +214,18 @@ void n3dt_launch_face_recon_block(int block, int n, int Hi, int Wi, const void* 
 void n3dt_launch_face_recon_align(int n, int H, int W, const float* frames, const double* landmarks, int points, const double* lm3d_std,
                                   const double* pinv, int quantize, float* crops, double* trans_params, int* geom, int* status,
                                   hipStream_t st);
+
+// ---- fan.hip
+size_t n3dt_fan_packed_layout_bytes(int modules, int N);
+size_t n3dt_fan_ws_bytes(int modules, int N, int n);
+size_t n3dt_fan_block_ws_bytes(int block, int N, int n, int H, int W);
+void n3dt_launch_fan_pack(const N3dtFanParams* q, void* packed, hipStream_t st);
+void n3dt_launch_fan_fwd(int modules, int N, int end_relu, int n, const void* packed, const float* x, int compute_gates, uint8_t* gates,
+                         float* heat, void* workspace, hipStream_t st);
+void n3dt_launch_fan_block(int block, int modules, int N, int end_relu, int n, int H, int W, const void* packed, const float* in,
+                           const float* skip, const uint8_t* gates, float* out, void* workspace, hipStream_t st);
+void n3dt_launch_fan_crops(int n, int H, int W, const float* frames, const int* boxes, float* out, hipStream_t st);
+void n3dt_launch_fan_points(int n, int N, const float* heat, long long frame_stride, double* pts, int* status, hipStream_t st);
+void n3dt_launch_fan_tail(int n, int N, int P, int H, int W, const double* pts, const int* dstatus, const int* boxes, const int* table,
+                          int carry, double* out, int* status, hipStream_t st);
 }

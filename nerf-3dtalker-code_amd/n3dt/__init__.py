@@ -8,5 +8,6 @@ from .eval_utils import image_metrics, calc_eval_metrics, LPIPS, SyncNet, SyncMe
 from .wav2lip import Wav2Lip, Wav2LipClip, load_wav2lip  # noqa: F401
 from .s3fd import S3FD, load_s3fd  # noqa: F401
 from .face_recon import FaceRecon, load_face_recon  # noqa: F401
+from .fan import FAN, load_fan  # noqa: F401
 from .train import validate  # noqa: F401
-from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet, wav2lip, s3fd, face_recon  # noqa: F401,E402
+from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet, wav2lip, s3fd, face_recon, fan  # noqa: F401,E402

@@ -78,6 +78,16 @@ class FaceReconParams(ctypes.Structure):
                  ("head_bias", ctypes.c_void_p * FACE_RECON_HEADS)])
 
 
+FAN_MAX_CONVS = 200
+FAN_MAX_BLOCKS = 82
+
+
+class FanParams(ctypes.Structure):
+    _fields_ = ([("num_modules", ctypes.c_int32), ("num_landmarks", ctypes.c_int32)] +
+                [(name, ctypes.c_void_p * FAN_MAX_CONVS) for name in ("weight", "bias", "bn_weight", "bn_bias", "bn_mean", "bn_var")] +
+                [("coords256", ctypes.c_void_p), ("coords64", ctypes.c_void_p)])
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -238,6 +248,16 @@ def _signatures():
         "n3dt_face_recon_block_workspace_bytes": (sz, [ci, ci, ci, ci]),
         "n3dt_face_recon_block": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
         "n3dt_face_recon_align": (ci, [ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]),
+        "n3dt_fan_packed_bytes": (sz, [ci, ci]),
+        "n3dt_fan_pack": (ci, [ctypes.POINTER(FanParams), vp, vp]),
+        "n3dt_fan_max_images": (ci, [ci, ci]),
+        "n3dt_fan_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_fan_fwd": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, sz, vp]),
+        "n3dt_fan_block_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
+        "n3dt_fan_block": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_fan_crops": (ci, [ci, ci, ci, vp, vp, vp, vp]),
+        "n3dt_fan_points": (ci, [ci, ci, vp, i64, vp, vp, vp]),
+        "n3dt_fan_tail": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
         # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
         "n3dt_flat_adam_guard_bytes": (sz, []),
         "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),

@@ -481,6 +481,128 @@ def face_recon_state_dict(seed=0):
     return sd
 
 
+FAN_BRANCH_SCALE = 0.35
+FAN_HEAT_SCALE = 1.0
+FAN_COORD_SCALE = 0.1
+FAN_CALIBRATION_IMAGES = 2
+FAN_BOUNDARY_MEAN = 0.95
+
+
+def _fan_calibrate(sd, num_modules):
+    """Walk the network in float64 over FAN_CALIBRATION_IMAGES seeded noise images and, in front of every BatchNorm, set its running
+    statistics to those of its input, as training would have left them.  The statistics are quantised to float16 precision, so
+    that a last-bit difference between two machines' float64 sums does not reach the weights."""
+    import torch.nn.functional as F
+    from .fan import HG_BLOCKS, coords
+    gen = torch.Generator().manual_seed(977)
+    x = torch.rand(FAN_CALIBRATION_IMAGES, 3, 256, 256, generator=gen).double()
+    w = lambda k: sd[k].double()  # noqa: E731
+
+    def bn(name, t, relu=True):
+        sd[name + ".running_mean"] = t.mean(dim=(0, 2, 3)).to(torch.float16).float()
+        sd[name + ".running_var"] = t.var(dim=(0, 2, 3), unbiased=False).clamp(1e-4, 6e4).to(torch.float16).float()
+        g = w(name + ".weight") / torch.sqrt(w(name + ".running_var") + 1e-5)
+        y = (t - w(name + ".running_mean")[None, :, None, None]) * g[None, :, None, None] + w(name + ".bias")[None, :, None, None]
+        return torch.relu(y) if relu else y
+
+    def cb(name, t):
+        o1 = F.conv2d(bn(name + ".bn1", t), w(name + ".conv1.weight"), None, 1, 1)
+        o2 = F.conv2d(bn(name + ".bn2", o1), w(name + ".conv2.weight"), None, 1, 1)
+        o3 = F.conv2d(bn(name + ".bn3", o2), w(name + ".conv3.weight"), None, 1, 1)
+        res = t
+        if name + ".downsample.2.weight" in sd:
+            res = F.conv2d(bn(name + ".downsample.0", t), w(name + ".downsample.2.weight"))
+        return torch.cat((o1, o2, o3), 1) + res
+
+    def hourglass(s, level, t):
+        up1 = cb("m%d.b1_%d" % (s, level), t)
+        low = cb("m%d.b2_%d" % (s, level), F.avg_pool2d(t, 2, 2))
+        low = hourglass(s, level - 1, low) if level > 1 else cb("m%d.b2_plus_1" % s, low)
+        low = cb("m%d.b3_%d" % (s, level), low)
+        return up1 + F.interpolate(low, scale_factor=2, mode="nearest")
+
+    assert len(HG_BLOCKS) == 13
+    n = x.shape[0]
+    c256, c64 = coords(256).double()[None].expand(n, -1, -1, -1), coords(64).double()[None].expand(n, -1, -1, -1)
+    y = bn("bn1", F.conv2d(torch.cat((x, c256), 1), w("conv1.conv.weight"), w("conv1.conv.bias"), 2, 3))
+    previous = cb("conv4", cb("conv3", F.avg_pool2d(cb("conv2", y), 2, 2)))
+    tmp = None
+    for s in range(num_modules):
+        t = torch.cat((previous, c64), 1)
+        if s > 0:
+            gate = (torch.clamp(tmp[:, -1:].float(), 0.0, 1.0) > 0.05).double()
+            t = torch.cat((t, gate * c64[:, :2]), 1)
+        t = F.conv2d(t, w("m%d.coordconv.conv.weight" % s), w("m%d.coordconv.conv.bias" % s))
+        ll = cb("top_m_%d" % s, hourglass(s, 4, t))
+        ll = bn("bn_end%d" % s, F.conv2d(ll, w("conv_last%d.weight" % s), w("conv_last%d.bias" % s)))
+        tmp = F.conv2d(ll, w("l%d.weight" % s), w("l%d.bias" % s))
+        # the boundary channel's bias: its mean FAN_BOUNDARY_MEAN standard deviations above the gate, so that both sides of the gate
+        # are populated and few cells lie right on it
+        shift = (0.05 + FAN_BOUNDARY_MEAN * tmp[:, -1].std() - tmp[:, -1].mean()).to(torch.float16).float()
+        sd["l%d.bias" % s][-1] += shift
+        tmp[:, -1] += shift.double()
+        if s < num_modules - 1:
+            previous = previous + F.conv2d(ll, w("bl%d.weight" % s), w("bl%d.bias" % s)) + F.conv2d(tmp, w("al%d.weight" % s), w("al%d.bias" % s))
+
+
+def fan_state_dict(seed=0, num_modules=4, num_landmarks=98):
+    """Seeded stand-in for the weights of the AWing FAN landmark detector (the pretrained alignment_WFLW_4HG.pth cannot be fetched
+    offline), under the keys of the reference's `FAN(num_modules, num_landmarks=...)` (n3dt.fan.load_fan).  Default initialisation
+    is useless here: its heat maps are smooth and peak on the border, because every ReLU leaves a positive mean that the zero
+    padding removes along the border only.  Here
+    * every convolution's weights are centred over their input channels per (output, tap) -- with like channels the means cancel
+      tap by tap, on the border too; the stem's image kernels sum to zero, its and the hourglass CoordConvs' coordinate channels
+      carry FAN_COORD_SCALE of the weight of a feature channel;
+    * a ConvBlock's convolutions are N(0, 2 / fan_in) times FAN_BRANCH_SCALE, so that a block adds about half its input's
+      magnitude to the residual and 59 of them neither blow the activations up nor leave a branch dead; l is N(0, 1 / 256) times
+      FAN_HEAT_SCALE;
+    * gamma is U(0.9, 1.1), beta N(0.1, 0.05^2), and every BatchNorm's running statistics are those of its input over
+      FAN_CALIBRATION_IMAGES seeded noise images (_fan_calibrate), as training leaves them: the channels in front of every ReLU are
+      alike, the heat maps noise-like with peaks all over the map; the boundary channel's bias puts its mean FAN_BOUNDARY_MEAN
+      standard deviations above the 0.05 gate: both sides of the gate are populated, and few cells lie on it.
+    Takes a few seconds (one float64 forward).  Never stored."""
+    from .fan import state_dict_keys
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape in state_dict_keys(num_modules, num_landmarks).items():
+        name, part = key.rsplit(".", 1)
+        leaf = name.rsplit(".", 1)[-1]
+        if part == "num_batches_tracked":
+            sd[key] = torch.tensor(0, dtype=torch.int64)
+        elif len(shape) == 4:
+            cout, cin, k, _ = shape
+            w = torch.randn(shape, generator=gen)
+            feat = 3 if name == "conv1.conv" else 256 if "coordconv" in name else cin  # the channels in front of the coordinates'
+            if k == 3:
+                scale = FAN_BRANCH_SCALE * math.sqrt(2.0 / (cin * 9))
+            elif name == "conv1.conv":
+                scale = math.sqrt(2.0 / (3 * 49))
+            elif name[0] == "l" and name[1:].isdigit():
+                scale = FAN_HEAT_SCALE * math.sqrt(1.0 / cin)
+            elif name[:2] in ("al", "bl"):
+                scale = 0.25 * math.sqrt(1.0 / cin)
+            else:  # downsample.2, conv_last, coordconv
+                scale = math.sqrt(1.0 / feat)
+            w[:, feat:] *= FAN_COORD_SCALE
+            if name == "conv1.conv":
+                w[:, :3] -= w[:, :3].mean(dim=(1, 2, 3), keepdim=True)
+            else:
+                w[:, :feat] -= w[:, :feat].mean(dim=1, keepdim=True)
+            sd[key] = w * scale
+        elif part == "weight":  # a BatchNorm's gamma
+            sd[key] = 0.9 + 0.2 * torch.rand(shape, generator=gen)
+        elif part == "bias" and (leaf.startswith("bn") or leaf == "0"):
+            sd[key] = 0.1 + 0.05 * torch.randn(shape, generator=gen)
+        elif part == "bias":
+            sd[key] = 0.05 * torch.randn(shape, generator=gen)
+        elif part == "running_mean":
+            sd[key] = torch.zeros(shape)
+        else:
+            sd[key] = torch.ones(shape)
+    _fan_calibrate(sd, num_modules)
+    return sd
+
+
 def face_recon_lm3d():
     """A stand-in for the [5,3] standard landmarks the reference's load_lm3d reads from its BFM folder (left eye, right eye, nose,
     left and right mouth corner; float64): a plausible face for smoke runs and timing, NOT the reference's values -- those the
