@@ -788,7 +788,9 @@ __global__ __launch_bounds__(64) void fine_sample_kernel(N3dtGeom g, int n_fine,
     }
     __syncthreads();
     for (int i = lane; i < Nu; i += 64) {
-        const float u = u_in ? u_in[rayg * Nu + i] : n3dt_linspace01(i, Nu);
+        // torch.linspace(0, 1, 1) is [0] (n_fine = 0); n3dt_linspace01's step would be 1 / 0 and u = 1 - inf * 0 a NaN, which takes
+        // rank 0 in the sort below together with the nearest plane and leaves one output slot unwritten
+        const float u = u_in ? u_in[rayg * Nu + i] : (Nu > 1 ? n3dt_linspace01(i, Nu) : 0.0f);
         int lo = 0, hi = Nc - 1;  // upper bound: number of cdf entries <= u
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;

@@ -138,7 +138,7 @@ void orc_fine_sample(long R, int Nc, int Nf, const float* weight, const float* z
         for (int j = 0; j < Nt; ++j) { run += w[j] / total; cdf[j + 1] = run; }   /* pdf, cumsum (:224-225) */
         for (int j = 0; j < Nc; ++j) o[j] = z[j];
         for (int i = 0; i < Nu; ++i) {
-            float u = u_in ? u_in[r * Nu + i] : linspace01(i, Nu);                /* :229-232 */
+            float u = u_in ? u_in[r * Nu + i] : (Nu > 1 ? linspace01(i, Nu) : 0.0f); /* :229-232; linspace(0, 1, 1) = [0] */
             int inds = 0;                                                          /* searchsorted(right=True) (:235) */
             while (inds < Nt + 1 && cdf[inds] <= u) ++inds;
             int below = inds - 1 > 0 ? inds - 1 : 0;                               /* :236 */

@@ -107,6 +107,8 @@ CASES = {
     "contrast": dict(B=2, n_rays=16, n_samples=24, weights="contrast", kw={}, vd=0),
     "gaze": dict(B=2, n_rays=16, n_samples=24, weights="seed", kw={"include_gaze": True, "eye_gaze_dim": 64, "audio_dim": 0}, vd=0),
     "vd": dict(B=1, n_rays=9, n_samples=40, weights="seed", kw={}, vd=27),
+    # the hierarchical pass: z_planes_given = 1, the 16 + 24 + 1 planes of hier_stagewise.given_planes passed as t_rand
+    "hier": dict(B=2, n_rays=16, n_samples=40, weights="seed", kw={}, vd=0, hier=(16, 24)),
 }
 VARIANTS = ("full", "frozen", "dfg", "zero")   # the three extra runs of cases a and tail
 
@@ -163,6 +165,12 @@ def case_inputs(name, seed=0, variant="full"):
     d_ba = torch.randn(B, n_rays, generator=gen).numpy()
     ray_bias = 0.2 * torch.randn(B, n_rays, 192, generator=gen).numpy() if c["vd"] else None
     out = pack_inputs(opt, sd, inp, case_rays(n_rays), Ns, syn.stratified_noise(B, n_rays, Ns, 7 + seed).numpy(), d_merge, c["vd"], ray_bias, name, variant, c["kw"])
+    out["planes"] = None
+    if c.get("hier"):
+        import hier_stagewise as hh   # (imports this module)
+        out["planes"] = hh.given_planes(out["T"][:, 2], n_rays, c["hier"][0], c["hier"][1], seed, out["z1"], out["z2"])
+        out["t_rand"] = None
+        assert out["planes"].shape == (B, n_rays, Ns + 1)
     if variant == "frozen":
         out["frozen"] = True
     elif variant == "dfg":
@@ -286,8 +294,14 @@ def ray_setup(dt, xy, R, Kinv):
     return h, c, w, n, dh, l
 
 
-def edges(dt, Tz, z1, z2, Ns, t_rand):
-    """stratified plane edges [B, rays, Ns + 1] (n3dt_edge_z) and the magnitude |rz1| + |rz2| their roundings scale with"""
+def edges(dt, Tz, z1, z2, Ns, t_rand, planes=None):
+    """stratified plane edges [B, rays, Ns + 1] (n3dt_edge_z) and the magnitude |rz1| + |rz2| their roundings scale with.
+    planes [B, rays, Ns + 1] (z_planes_given, the hierarchical pass): the planes themselves in dt -- they are data, nothing is computed --
+    and the largest |plane| of each frame as their magnitude"""
+    if planes is not None:
+        p = np.asarray(planes).astype(dt)
+        assert p.shape[-1] == Ns + 1
+        return p, np.abs(np.asarray(planes, dtype=np.float64)).reshape(p.shape[0], -1).max(axis=1)
     Tz = np.asarray(Tz).astype(dt)
     rz1, rz2 = Tz - dt(z1), Tz - dt(z2)
     t = np.linspace(0.0, 1.0, Ns + 1).astype(dt)
@@ -305,7 +319,7 @@ def sample(dt, inp):
     """points [P, 3], dist [P], zval [P] and their magnitudes"""
     B, n_rays, Ns = inp["B"], inp["n_rays"], inp["Ns"]
     h, c, w, n, dh, l = ray_setup(dt, inp["xy"], inp["R"], inp["Kinv"])
-    z, sz = edges(dt, inp["T"][:, 2], inp["z1"], inp["z2"], Ns, inp["t_rand"])
+    z, sz = edges(dt, inp["T"][:, 2], inp["z1"], inp["z2"], Ns, inp["t_rand"], inp.get("planes"))
     z = np.broadcast_to(z, (B, n_rays, Ns + 1))
     T = np.asarray(inp["T"]).astype(dt)
     dl = dh * l[..., None]
@@ -481,11 +495,14 @@ def composite_bwd(dt, sig_pre, dist, w_in, g, dgray, dwsum, fault=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # camera backward (train_camera_bwd_kernel) in any dtype, with the magnitude every sum carries
 # ---------------------------------------------------------------------------------------------------------------------
-def camera_bwd(dt, inp, cat5, dpe, ddist, S_dq=None):
-    """-> (d_R [B,3,3], d_T [B,3], d_Kinv [B,3,3], d_xy [B,2,rays]) and the same four as sums of absolute terms"""
+def camera_bwd(dt, inp, cat5, dpe, ddist, S_dq=None, fault=None):
+    """-> (d_R [B,3,3], d_T [B,3], d_Kinv [B,3,3], d_xy [B,2,rays]) and the same four as sums of absolute terms.
+    With given planes (the hierarchical pass) the planes are data, but d plane / d T_z = 1 as in the coarse pass (train_mlp.hip:401-411:
+    they are affine combinations of the coarse planes T_z + const), so g_tz is formed exactly as without them and g_l comes from the
+    differences z_hi - z_lo of the given planes.  fault "no_gtz": the g_tz term dropped when the planes are given."""
     B, n_rays, Ns = inp["B"], inp["n_rays"], inp["Ns"]
     h, c, w, n, dh, l = ray_setup(dt, inp["xy"], inp["R"], inp["Kinv"])
-    z, sz = edges(dt, inp["T"][:, 2], inp["z1"], inp["z2"], Ns, inp["t_rand"])
+    z, sz = edges(dt, inp["T"][:, 2], inp["z1"], inp["z2"], Ns, inp["t_rand"], inp.get("planes"))
     z = np.broadcast_to(z, (B, n_rays, Ns + 1))
     Rm, Km = np.asarray(inp["R"]).astype(dt), np.asarray(inp["Kinv"]).astype(dt)
     pe = np.asarray(cat5)[:, :64].astype(dt).reshape(B, n_rays, Ns, 64)
@@ -503,6 +520,8 @@ def camera_bwd(dt, inp, cat5, dpe, ddist, S_dq=None):
     g_dl, S_gdl = (dp * z_lo[..., None]).sum(axis=2), (S_dp * np.abs(z_lo)[..., None]).sum(axis=2)
     g_T, S_gT = dp.sum(axis=2), S_dp.sum(axis=2)
     g_tz, S_gtz = (dp * dl[:, :, None, :]).sum(axis=(2, 3)), (S_dp * np.abs(dl)[:, :, None, :]).sum(axis=(2, 3))
+    if fault == "no_gtz" and inp.get("planes") is not None:
+        g_tz = np.zeros_like(g_tz)
     g_l, S_gl = (dd * (z_hi - z_lo)).sum(axis=2), (np.abs(dd) * 2.0 * sz[:, None, None]).sum(axis=2)
     gl, S_glt = g_l + (g_dl * dh).sum(axis=-1), S_gl + (S_gdl * np.abs(dh)).sum(axis=-1)
     ez = np.array([0, 0, 1], dtype=dt)
@@ -650,7 +669,7 @@ def run_path(inp, dt=np.float32, fault=None, order=None):
         Wl = wk.w5p[:, 64:] if l == 5 else W[l]
         dH[l - 1] = np.where(sv.h[l - 1] > 0, mm_rows(dt, dcur, np.ascontiguousarray(Wl.T)), dt(0))
     wk.dha[:], wk.dhb[:] = dH[1], dH[0]
-    (d_R, d_T, d_K, d_xy), _ = camera_bwd(dt, inp, sv.cat5, wk.dpe, wk.dxr[:, 385])
+    (d_R, d_T, d_K, d_xy), _ = camera_bwd(dt, inp, sv.cat5, wk.dpe, wk.dxr[:, 385], fault=fault)
     if not frozen:   # train_unpack_grads_kernel
         off = 63 + S + (1 if fault == "unpack_off" else 0)
         gw[5][:, :63] += wk.dw5p[:, :63]

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 import f32_stagewise as fs
+import hier_stagewise as hh
 import x16_stagewise as xs
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3                    # n3dt.h: N3DT_F32 ..
@@ -63,13 +64,22 @@ FLOOR = {
     "merge_fma": 2.3e-7,   # measured 2.24e-7 (contrast, 16)
     "fg_mfma": 3.0e-6,     # measured 2.96e-6 (span, 16)           hi hi + hi lo + lo hi per k-step of 16, float32 sums: the lo lo term
     "merge_mfma": 2.5e-6,  # measured 2.41e-6 (contrast, 16)       that is never formed dominates (2^-18 of a term)
-    "rgb0": 2.3e-8,        # measured 2.21e-8 (span, 16)           two channels per lane, five-step tree over 32 lanes, four waves, + bias
+    "rgb0": 2.3e-8,        # measured 2.30e-8 (hier_span, 16)      two channels per lane, five-step tree over 32 lanes, four waves, + bias
+    # the given-plane cases (hier, hier_span) where their floor is above the table's: their own entries, the entries above stay
+    "fg_fma_hier": 2.6e-7,    # measured 2.51e-7 (hier, 32)
+    "fg_mfma_hier": 3.2e-6,   # measured 3.17e-6 (hier_span, 16)
 }
 FACTOR = 4.0
 
 
 def unit(family):
     return FACTOR * FLOOR[family]
+
+
+def family_of(name, family):
+    """the entry of FLOOR that judges `family` in case `name`: a given-plane case's own entry where it has one"""
+    own = family + "_hier"
+    return own if CASES[name].get("hier") and own in FLOOR else family
 
 
 def bound_bg_alpha(mag_chain):
@@ -533,6 +543,9 @@ CASES = {
     "contrast": dict(B=3, n_rays=7, n_samples=40, weights="contrast", kw={}),
     "gaze": dict(B=3, n_rays=7, n_samples=40, weights="seed0", kw={"include_gaze": True, "eye_gaze_dim": 64, "audio_dim": 0}),
     "vd": dict(B=3, n_rays=7, n_samples=40, weights="seed0", kw={}, vd=True),
+    # the hierarchical pass: z_planes_given = 1, the case carries its N_c + N_f + 1 planes (hier_stagewise.given_planes), one ray's by hand
+    "hier": dict(B=3, n_rays=7, n_samples=40, weights="seed0", kw={}, hier=(16, 24)),
+    "hier_span": dict(B=3, n_rays=45, n_samples=65, weights="seed0", kw={}, hier=(24, 41)),
 }
 FEATMAP_SIZE = 8
 
@@ -566,12 +579,16 @@ def case_inputs(name):
     assert ws[0].shape[1] == 63 + S + U and ws[5].shape[1] == 63 + S + HID and ws[10].shape[1] == HID + A
     audio = inp["audiostyle"].numpy().astype(np.float32) if U > 0 else None
     codes = (inp["shape_code"].numpy().astype(np.float32), inp["appea_code"].numpy().astype(np.float32), audio)
+    planes = None
+    if c.get("hier"):
+        planes = hh.given_planes(inp["batch_Tvecs"].numpy().reshape(c["B"], 3)[:, 2], c["n_rays"], c["hier"][0], c["hier"][1], 0, opt.world_z1, opt.world_z2)
+        assert planes.shape == (c["B"], c["n_rays"], c["n_samples"] + 1)
     bg_chw = np.ascontiguousarray(sd["neural_render.bg_featmap"].reshape(C, -1)[:, rays].numpy())     # [C, n_rays]
-    return {"c": c, "opt": opt, "sd": sd, "inp": inp, "rays": rays, "ws": ws, "bs": bs, "w10_full": w10_full, "w_vd": w_vd, "vd": 27 if vd else 0,
+    return {"name": name, "c": c, "opt": opt, "sd": sd, "inp": inp, "rays": rays, "ws": ws, "bs": bs, "w10_full": w10_full, "w_vd": w_vd, "vd": 27 if vd else 0,
             "S": S, "A": A, "U": U, "codes": codes, "bg_chw": bg_chw, "bg_hwc": np.ascontiguousarray(bg_chw.T),
             "w3": sd["neural_render.feat_2_rgb_list.0.weight"].reshape(3, C).numpy().copy(),
             "b3": sd["neural_render.feat_2_rgb_list.0.bias"].numpy().copy(),
-            "B": c["B"], "n_rays": c["n_rays"], "Ns": c["n_samples"]}
+            "B": c["B"], "n_rays": c["n_rays"], "Ns": c["n_samples"], "planes": planes}
 
 
 def directions32(ci):
@@ -593,6 +610,9 @@ def cpu_points(name):
     inp, opt, B, n_rays, Ns = ci["inp"], ci["opt"], ci["B"], ci["n_rays"], ci["Ns"]
     s = orc.sample(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(), Ns,
                    opt.world_z1, opt.world_z2)
+    if ci["planes"] is not None:   # z_planes_given: the oracle's FineSample._calc_sample_points_by_zvals on the case's planes
+        s.update(orc.sample_planes(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(),
+                                   ci["planes"]))
     pe = orc.embed(s["pts"])                                                     # [B, 63, rays, Ns] float32
     x = np.concatenate([f64(pe), np.zeros((B, 1, n_rays, Ns))], axis=1)          # channel 63 = the zero padding
     x = np.moveaxis(x, 1, -1).reshape(B, n_rays * Ns, 64)

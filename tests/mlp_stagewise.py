@@ -59,6 +59,11 @@ The rules (judge()); everything downstream of a stored value is judged from the 
 Rule 7's bitwise properties hold by construction: a wave's arithmetic depends on nothing but its block's own samples, tables and the
 shared weight stream (nerf_fwd_x16.hip:300-323: blk -> ray, frame; every wave reads the same pieces), and nothing is atomic.
 
+Given planes (cases hier and hier_span of head_stagewise.CASES: z_planes_given, the planes of hier_stagewise.given_planes passed as t_rand)
+go through the same rules, with two additions: a sample between two equal planes (dist == 0) stores a weight of exactly 0 (figure
+zero_dist_nonzero, under rule 1) and rule 5 runs across it (x = 1 + 1e-10f); and rule 1's dalpha carries an expf of one ulp (see judge()).
+Where their measured floor is above the table's they have their own entry (FLOOR_GIVEN).
+
 Units: U_family = 4 x FLOOR[family][precision]; a floor is the largest figure of the float32-ordered CPU emulations (chain() modes
 "asc", "desc", "torch", and "fma" for fp32: the k order nerf_fwd_f32.hip walks) through the sequential float32 compositing
 (composite32) against this reference over all CASES; test_mlp_stagewise_cpu.py re-measures every one.  No number comes from a GPU run.
@@ -99,12 +104,29 @@ FLOOR = {
     "zsum": {"fp32": 1.27e-7, "bf16": 1.16e-7, "fp16": 1.2e-7, "bf16x3": 1.23e-7},
     "eps": {"fp32": 2.05e-7, "bf16": 3.1e-7, "fp16": 4.0e-7, "bf16x3": 3.2e-7},
 }
+# The given-plane cases (hier, hier_span: z_planes_given) where their measured floor is above the table's: their own entries, the table
+# above stays.  Fine planes cluster: neighbouring samples are nearly the same point, so their 16-bit encodings and hence their errors are the
+# same and do not average out over a block (g, g_rms), and the plane distances are a tenth of a uniform slab's, so what float32 exp adds
+# beyond a correct rounding of e -- an error of alpha that the conditioning term does not carry -- is ten times larger in sigma = a / dist.
+FLOOR_GIVEN = {
+    "sigma": {"fp16": 1.6e-4, "bf16x3": 1.0e-5},              # measured 1.715e-4 at the table's unit (hier_span asc), 9.77e-6 (hier_span asc)
+    "sigma_rms": {"bf16": 4.6e-4, "fp16": 8.3e-5},            # measured 4.51e-4 (hier_span asc), 8.03e-5 (hier_span torch)
+    "g": {"fp32": 1.9e-7, "bf16": 1.0e-3},                    # measured 1.874e-7 (hier_span torch), 9.99e-4 (hier_span asc)
+    "g_rms": {"bf16": 2.4e-4},                                # measured 2.35e-4 (hier_span asc)
+}
+GIVEN_CASES = tuple(n for n, c in hs.CASES.items() if c.get("hier"))
 FACTOR = 4.0
 FAMILIES = tuple(FLOOR)
 
 
-def unit(family, prec):
-    return FACTOR * FLOOR[family][prec]
+def floor_of(family, prec, name=None):
+    own = FLOOR_GIVEN.get(family, {}) if name in GIVEN_CASES else {}
+    return own.get(prec, FLOOR[family][prec])
+
+
+def unit(family, prec, name=None):
+    """name: the case; a given-plane case takes its own entry where it has one"""
+    return FACTOR * floor_of(family, prec, name)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -175,7 +197,7 @@ def cpu_geometry(name):
     B = ci["B"]
     g = {"B": B, "n_rays": ci["n_rays"], "Ns": ci["Ns"], "xy": inp["batch_xy"].numpy(), "R": inp["batch_Rmats"].numpy().reshape(B, 3, 3),
          "Kinv": inp["batch_inv_inmats"].numpy().reshape(B, 3, 3), "T": inp["batch_Tvecs"].numpy().reshape(B, 3), "z1": opt.world_z1,
-         "z2": opt.world_z2, "t_rand": None}
+         "z2": opt.world_z2, "t_rand": None, "planes": ci["planes"]}
     (pts, dist, zval), _ = fs.sample(np.float32, g)
     R, Ns = B * ci["n_rays"], ci["Ns"]
     return pts.reshape(R, Ns, 3), dist.reshape(R, Ns), zval.reshape(R, Ns)
@@ -388,7 +410,7 @@ def reference(src, rays):
     Ns = src["Ns"]
     o = chain(src, "ref", point_index(Ns, rays))
     n = len(rays)
-    return {"rays": np.asarray(rays), "sigma": o["sigma"].reshape(n, Ns), "mag_sigma": o["mag_sigma"].reshape(n, Ns), "g": o["g"].reshape(n, Ns, G),
+    return {"name": src["name"], "rays": np.asarray(rays), "sigma": o["sigma"].reshape(n, Ns), "mag_sigma": o["mag_sigma"].reshape(n, Ns), "g": o["g"].reshape(n, Ns, G),
             "mag_g": o["mag_g"].reshape(n, Ns, G), "dist": src["dist"][rays].astype(np.float64), "zval": src["zval"][rays].astype(np.float64)}
 
 
@@ -412,6 +434,8 @@ def composite32(sigma, g, dist, zval, bs, fault=None):
     s, gd = blocks(np.asarray(sigma, dtype=np.float32), bs), blocks(np.asarray(g, dtype=np.float32), bs)
     d, zv = blocks(np.asarray(dist, dtype=np.float32), bs), blocks(np.asarray(zval, dtype=np.float32), bs)
     live = blocks(np.ones(sigma.shape, dtype=bool), bs, False)
+    if fault == "min_dist":      # a live sample's distance is never taken as 0 (given planes: two equal planes)
+        d = np.where(live, np.maximum(d, np.float32(1e-4)), d)
     if fault == "dead_dist":     # the dead lanes take the block's last live sample, its distance included
         li = np.maximum(live.sum(2) - 1, 0)
         take = lambda a: np.where(live if a.ndim == 3 else live[..., None], a, np.take_along_axis(a, li.reshape(li.shape + (1,) * (a.ndim - 2)), axis=2))
@@ -452,14 +476,15 @@ def judge(ref, part, wlocal, prec):
     error in units of its magnitude (to be divided by unit()), the counts of the exact rules, the shares and the widths"""
     p = hs.PRECS[prec]
     bs = hs.block_samples(p)
-    f = {}
+    name = ref.get("name")
+    f = {"name": name}
     sig, mag = blocks(ref["sigma"], bs), blocks(ref["mag_sigma"], bs, 1.0)
     d, zv = blocks(ref["dist"], bs), blocks(ref["zval"], bs)
     live = blocks(np.ones(ref["sigma"].shape, dtype=bool), bs, False)
     w = np.asarray(wlocal, dtype=np.float64)
     wbits = np.ascontiguousarray(wlocal, dtype=np.float32).view(np.uint32)
     pt = np.asarray(part, dtype=np.float64)
-    dsig = unit("sigma", prec) * mag
+    dsig = unit("sigma", prec, name) * mag
     # ---- rule 1
     alpha, dal, early, tl_err = np.zeros_like(w), np.zeros_like(w), np.zeros(w.shape, dtype=bool), np.zeros_like(w)
     Tl, acc, ok, scan = np.ones(w.shape[:2]), np.zeros(w.shape[:2]), np.ones(w.shape[:2], dtype=bool), np.zeros(w.shape[:2])
@@ -477,6 +502,12 @@ def judge(ref, part, wlocal, prec):
         a_arg = -np.log1p(-alpha)
         srec = a_arg / d
         dalpha = dal + 0.5 * ulp32(x1) + x1 * a_arg * U32 + np.where(alpha > 0.5, 0.5 * ulp32(alpha), 0.0)
+        if name in GIVEN_CASES:
+            # given planes: an expf of ONE ulp, not a correct rounding of e, enters the conditioning -- half a spacing of x more.  With
+            # uniform planes that excess is part of the floor of family sigma (above); with fine planes it cannot be: dist spans three
+            # decades, the excess grows as 1 / dist like cond itself, and a unit that carried it would admit samples (cond <= dsigma / 2)
+            # whose excess is larger again -- measured: the floor tripled at every step and had no fixed point
+            dalpha = dalpha + 0.5 * ulp32(x1)
         cond = dalpha / (x1 * d) / (1.0 - 2.0 * np.minimum(tl_err, TL_ERR_MAX))
         eligible = live & (d > 0) & early & (alpha < 1.0) & (tl_err <= TL_ERR_MAX) & np.isfinite(srec) & np.isfinite(cond)
         judged = eligible & (sig > dsig) & (cond <= 0.5 * dsig)
@@ -487,6 +518,10 @@ def judge(ref, part, wlocal, prec):
     rms = lambda v: np.sqrt((v ** 2).sum(2)[nj > 0] / nj[nj > 0])
     f["sigma_rms"] = float(np.maximum(rms(rel) - rms(crel), 0.0).max()) if (nj > 0).any() else 0.0
     f["neg_nonzero"] = int((live & (sig < -dsig) & (wbits != 0)).sum())
+    # (given planes: a sample between two equal planes has dist = 0, alpha = 1 - expf(-(sigma 0)) = 0 and a stored weight of exactly 0, so
+    #  it adds exactly nothing to part[:192], which rule 3 then judges from the stored weights; its x is 1 + 1e-10f in rule 5)
+    f["zero_dist"] = int((live & (d == 0)).sum())
+    f["zero_dist_nonzero"] = int((live & (d == 0) & (wbits != 0)).sum())
     positive = live & (sig > 0)
     f["share"] = float(judged.sum()) / max(int(positive.sum()), 1)
     # ---- rule 2
@@ -510,7 +545,7 @@ def judge(ref, part, wlocal, prec):
     # ---- rule 4
     f["zsum"] = hs.ratio(pt[..., G + 1], (w * zv).sum(2), np.abs(w * zv).sum(2))
     # ---- rule 5
-    eps = unit("eps", prec)
+    eps = unit("eps", prec, name)
     T_lo = np.prod(np.where(live, np.maximum(x_lo * (1 - 4 * U32) - X_ABS, X_MIN), 1.0), axis=2)
     T_hi = np.prod(np.where(live, x_hi * (1 + 4 * U32) + X_ABS, 1.0), axis=2)
     t = pt[..., G + 2]
@@ -522,14 +557,14 @@ def judge(ref, part, wlocal, prec):
 
 
 RULES = {"sigma": "1a", "sigma_rms": "1b", "neg_nonzero": "1 (negative density)", "interval": "2", "g": "3a", "g_rms": "3b", "zsum": "4", "tprod": "5",
-         "pad_nonzero": "6", "dead_nonzero": "7 (dead lanes)"}
+         "pad_nonzero": "6", "dead_nonzero": "7 (dead lanes)", "zero_dist_nonzero": "1 (zero-width sample)"}
 
 
 def verdict(f, prec):
     """figure -> its share of the bound (<= 1 passes); the exact rules count violations (0 passes)"""
-    v = {k: f[k] / unit(k, prec) for k in ("sigma", "sigma_rms", "g", "g_rms", "zsum")}
+    v = {k: f[k] / unit(k, prec, f.get("name")) for k in ("sigma", "sigma_rms", "g", "g_rms", "zsum")}
     v["interval"], v["tprod"] = f["interval"], f["tprod"]
-    for k in ("neg_nonzero", "pad_nonzero", "dead_nonzero"):
+    for k in ("neg_nonzero", "pad_nonzero", "dead_nonzero", "zero_dist_nonzero"):
         v[k] = float("inf") if f[k] else 0.0
     return v
 
@@ -541,7 +576,7 @@ def failing(v):
 def show(tag, f, prec):
     """prints every figure of one judged call before it is asserted"""
     v = verdict(f, prec)
-    print("%-30s 1a %.3f  1b %.3f  2 %.3f  3a %.3f  3b %.3f  4 %.3f  5 %.3f | exact-rule violations %d %d %d | judged share %.3f | width q50 %.2e q90 %.2e q99 %.2e"
+    print("%-30s 1a %.3f  1b %.3f  2 %.3f  3a %.3f  3b %.3f  4 %.3f  5 %.3f | exact-rule violations %d %d %d, %d of %d zero-width samples | judged share %.3f | width q50 %.2e q90 %.2e q99 %.2e"
           % (tag, v["sigma"], v["sigma_rms"], v["interval"], v["g"], v["g_rms"], v["zsum"], v["tprod"], f["neg_nonzero"], f["pad_nonzero"],
-             f["dead_nonzero"], f["share"], f["width"][0], f["width"][1], f["width"][2]))
+             f["dead_nonzero"], f["zero_dist_nonzero"], f["zero_dist"], f["share"], f["width"][0], f["width"][1], f["width"][2]))
     return v

@@ -41,7 +41,7 @@ def run(name, variant="full"):
     B, n_rays, Ns, vd = inp["B"], inp["n_rays"], inp["Ns"], inp["vd"]
     t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev())  # noqa: E731
     xy = t(inp["xy"])
-    geom = ops.make_geom(B, n_rays, Ns, 384, 256, inp["S"], inp["A"], inp["U"], fs.FEATMAP_SIZE, 2, inp["z1"], inp["z2"], xy.stride(), vd_dim=vd)
+    geom = ops.make_geom(B, n_rays, Ns, 384, 256, inp["S"], inp["A"], inp["U"], fs.FEATMAP_SIZE, 2, inp["z1"], inp["z2"], xy.stride(), int(inp["planes"] is not None), vd_dim=vd)
     Ls, Lw = fs.saved_layout(B, n_rays, Ns, vd), fs.ws_layout(B, n_rays, Ns)
     saved_floats, ws_floats, saved_bytes = fs.library_totals(geom)
     assert (saved_floats, ws_floats) == (Ls["total"], Lw["total"]) and saved_bytes >= 4 * saved_floats
@@ -49,6 +49,8 @@ def run(name, variant="full"):
     params = ops.mlp_params(ws_, bs_)
     packed = ops.pack_mlp(geom, _lib.F32, params, dev())
     R, T, Kinv, shape, appea, audio, tr, bg, rb = (t(inp[k]) for k in ("R", "T", "Kinv", "shape", "appea", "audio", "t_rand", "bg", "ray_bias"))
+    if inp["planes"] is not None:   # the hierarchical pass: z_planes_given, the planes go where t_rand goes
+        tr = t(inp["planes"])
     dm, dfg, dba = t(inp["d_merge"]), t(inp["d_fg"]), t(inp["d_ba"])
     runs = []
     for _ in range(2 if variant == "full" else 1):

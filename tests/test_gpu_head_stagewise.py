@@ -61,7 +61,8 @@ def device_inputs(name):
          "T": ops._f32c(inp["batch_Tvecs"].to(dev())).view(ci["B"], 3), "Kinv": ops._f32c(inp["batch_inv_inmats"].to(dev())),
          "shape": t(ci["codes"][0]), "appea": t(ci["codes"][1]), "audio": t(ci["codes"][2]) if ci["U"] > 0 else None,
          "ws": [t(w) for w in ci["ws"]], "bs": [t(b) for b in ci["bs"]], "w10_full": t(ci["w10_full"]),
-         "bg": {0: t(ci["bg_chw"]), 1: t(ci["bg_hwc"])}, "w3": t(ci["w3"]), "b3": t(ci["b3"])}
+         "bg": {0: t(ci["bg_chw"]), 1: t(ci["bg_hwc"])}, "w3": t(ci["w3"]), "b3": t(ci["b3"]),
+         "planes": t(ci["planes"]) if ci["planes"] is not None else None}   # the hierarchical cases: z_planes_given, passed as t_rand
     d["params"] = ops.mlp_params(d["ws"], d["bs"])
     return d
 
@@ -69,7 +70,7 @@ def device_inputs(name):
 def make_geom(ci, d, hwc):
     from n3dt import ops
     return ops.make_geom(ci["B"], ci["n_rays"], ci["Ns"], 384, 256, ci["S"], ci["A"], ci["U"], hs.FEATMAP_SIZE, 2, ci["opt"].world_z1,
-                         ci["opt"].world_z2, d["xy"].stride(), 0, hwc, vd_dim=ci["vd"])
+                         ci["opt"].world_z2, d["xy"].stride(), int(ci["planes"] is not None), hwc, vd_dim=ci["vd"])
 
 
 @functools.lru_cache(maxsize=None)
@@ -111,7 +112,7 @@ def run(name, prec, outset, hwc=1, fill=0x00, rep=0):
     if outset in ("map16", "both"):
         dt16 = torch.bfloat16 if hs.MAP16[p] == "bf16" else torch.float16
         kw.update(merge16_out=filled((B, n_rays, hs.C), dt16, fill), rgb0_out=filled((B, 3, n_rays), torch.float32, fill), rgb0_wb=(d["w3"], d["b3"]))
-    out = ops.render_fwd(geom, p, packed(name, prec)[0], d["params"], d["xy"], d["R"], d["T"], d["Kinv"], d["shape"], d["appea"], d["audio"], None,
+    out = ops.render_fwd(geom, p, packed(name, prec)[0], d["params"], d["xy"], d["R"], d["T"], d["Kinv"], d["shape"], d["appea"], d["audio"], d["planes"],
                          d["bg"][hwc] if kw["want_merge"] else None, ws=ws, ray_bias=ray_bias, **kw)
     torch.cuda.synchronize()
     raw = ws.cpu().numpy()
@@ -262,7 +263,7 @@ def check_head(tag, r, form):
     bg = hs.bg_rows(ci["bg_hwc"], r["R"], ci["n_rays"])
     ref = hs.head_ref(r["part"], ci["ws"][11], ci["bs"][11], bg)
     if "fg_feat" in r:
-        held(tag + " fg_feat", "fg_" + form, r["fg_feat"], ref["fg"], ref["mag_fg"])
+        held(tag + " fg_feat", hs.family_of(ci["name"], "fg_" + form), r["fg_feat"], ref["fg"], ref["mag_fg"])
     if "merge_feat" in r:
         held(tag + " merge_feat", "merge_" + form, r["merge_feat"], ref["merge"], ref["mag_merge"])
     if "bg_alpha" in r:

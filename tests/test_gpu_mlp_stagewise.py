@@ -30,7 +30,7 @@ def geometry(name):
     """the float32 points [R, Ns, 3], plane distances and z values [R, Ns] of ops.sample_points for the case's geometry"""
     from n3dt import ops
     ci, d = hs.case_inputs(name), device_inputs(name)
-    s = ops.sample_points(make_geom(ci, d, 1), d["xy"], d["R"], d["T"], d["Kinv"])
+    s = ops.sample_points(make_geom(ci, d, 1), d["xy"], d["R"], d["T"], d["Kinv"], d["planes"])
     torch.cuda.synchronize()
     R, Ns = ci["B"] * ci["n_rays"], ci["Ns"]
     pts = s["pts"].permute(0, 2, 3, 1).reshape(R, Ns, 3).contiguous()

@@ -48,7 +48,7 @@ def run(name):
     net.load_state_dict(sd, strict=True)
     prec = _lib.BF16
     xy = inp["batch_xy"].to(dev()).contiguous()
-    geom = net._geom(B, n_rays, xy, n_samples=Ns)
+    geom = net._geom(B, n_rays, xy, n_samples=Ns, z_planes_given=int(bool(c.get("hier"))))   # (hier: t_rand below holds the planes)
     params, ws, bs = net._mlp_params()
     packed = net._packed(geom, prec, params, ws, bs)
     R, T, Kinv = (ops._f32c(inp[k].to(dev())) for k in ("batch_Rmats", "batch_Tvecs", "batch_inv_inmats"))
@@ -122,6 +122,9 @@ def _oracle_points(r):
     B, n_rays, Ns = c["B"], c["n_rays"], c["n_samples"]
     o = orc.sample(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(), Ns,
                    opt.world_z1, opt.world_z2, r["t_rand"].numpy())
+    if c.get("hier"):   # the oracle's FineSample._calc_sample_points_by_zvals on the given planes
+        o = orc.sample_planes(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(),
+                              r["t_rand"].numpy())
     pts = np.zeros((B, n_rays, sv.bpr * 32, 3))
     pts[:, :, :Ns] = np.moveaxis(o["pts"].astype(np.float64), 1, 3)
     dist = np.zeros((B, n_rays, sv.bpr * 32))
@@ -208,10 +211,10 @@ def test_weight_bias_and_code_gradients(name):
         got = r["runs"][0]["gw"][l] if k[0] == "w" else r["runs"][0]["gb"][l].reshape(1, -1)
         assert got.shape == val.shape, (k, got.shape, val.shape)
         e = _family_errors(got.astype(np.float64), val, mag, fams, fam_of_col, n_terms)
-        print("%s %-4s %s" % (name, k, "  ".join("%s %.3e (bound %.3e)" % (f, v, 4 * xs.DW_FLOOR[f]) for f, v in e.items())))
+        print("%s %-4s %s" % (name, k, "  ".join("%s %.3e (bound %.3e)" % (f, v, 4 * xs.dw_floor(name, f)) for f, v in e.items())))
         for f, v in e.items():
             worst[f] = max(worst.get(f, 0.0), v)
-            assert v <= 4 * xs.DW_FLOOR[f], (k, f, v)
+            assert v <= 4 * xs.dw_floor(name, f), (k, f, v)
     # per frame, as the weight-gradient kernels leave them: dfold[f][bias_offset(l)] = row sums of dZ_l (dw_x16_body's rowsum,
     # train_x16.inc:846-851), rs_rgb[f] = [db_m (192) | d b_density], copied to dfold[f][bias_offset(10)] (train16_finish_kernel, :1009-1014);
     # train_fold_bwd_kernel only reads them, so they survive the backward
@@ -221,15 +224,15 @@ def test_weight_bias_and_code_gradients(name):
     for k, got in per_frame:
         assert got.shape == ref[k][0].shape == (B, got.shape[1])
         v = xs.grad_error(got, ref[k][0], ref[k][1], n_terms)
-        print("%s %-5s per frame: bias %.3e (bound %.3e)" % (name, k, v, 4 * xs.DW_FLOOR["bias"]))
-        assert v <= 4 * xs.DW_FLOOR["bias"], (k, v)
+        print("%s %-5s per frame: bias %.3e (bound %.3e)" % (name, k, v, 4 * xs.dw_floor(name, "bias")))
+        assert v <= 4 * xs.dw_floor(name, "bias"), (k, v)
     for k, got in zip(("d_shape", "d_appea", "d_audio"), r["runs"][0]["codes"]):
         if k not in ref:
             assert got is None
             continue
         v = xs.grad_error(got, ref[k][0], ref[k][1], n_terms)
-        print("%s %-8s latent %.3e (bound %.3e)" % (name, k, v, 4 * xs.DW_FLOOR["latent"]))
-        assert v <= 4 * xs.DW_FLOOR["latent"], (k, v)
+        print("%s %-8s latent %.3e (bound %.3e)" % (name, k, v, 4 * xs.dw_floor(name, "latent")))
+        assert v <= 4 * xs.dw_floor(name, "latent"), (k, v)
     print("%s: largest error per family %s" % (name, {f: "%.3e" % v for f, v in worst.items()}))
 
 

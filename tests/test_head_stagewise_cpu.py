@@ -65,7 +65,7 @@ def measured():
             put("chain", hs.ratio(e["ds"], ref["dsum"], ref["mag_chain_d"]), where)
             put("G", hs.ratio(e["G"], ref["G"], ref["mag_G"]), where)
             for form in ("fma", "mfma"):
-                put("fg_" + form, hs.ratio(e["fg_" + form], ref["fg"], ref["mag_fg"]), where)
+                put(hs.family_of(name, "fg_" + form), hs.ratio(e["fg_" + form], ref["fg"], ref["mag_fg"]), where)
                 put("merge_" + form, hs.ratio(e["merge_" + form], ref["merge"], ref["mag_merge"]), where)
             r0, m0 = hs.rgb0_ref(e["merge_mfma"], st["ci"]["w3"], st["ci"]["b3"])
             put("rgb0", hs.ratio(e["rgb0"], r0, m0), where)
@@ -143,7 +143,14 @@ def test_restatement_against_the_oracle(name):
     skip_neural_render=True (include_vd for case vd): fg_feat and bg_alpha at 1e-5; both block sizes give the same rays."""
     from oracle import oracle as orc
     ci = hs.case_inputs(name)
-    ref = orc.forward(ci["sd"], ci["opt"], ci["inp"], skip_neural_render=True, include_vd=bool(ci["vd"]))
+    if ci["planes"] is not None:   # the hierarchical cases: the oracle's fine pass on the case's planes (oracle.forward_hier's second half)
+        inp = ci["inp"]
+        f = orc.sample_planes(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(), ci["planes"])
+        rgb, dens = orc.mlp(ci["sd"], orc.embed(f["pts"]), ci["codes"][0], ci["codes"][1], ci["codes"][2])
+        fg, ba, _, _ = orc.composite(rgb, dens, f["z_dists"], f["zvals"])
+        ref = {"fg_feat": fg, "bg_alpha": ba}
+    else:
+        ref = orc.forward(ci["sd"], ci["opt"], ci["inp"], skip_neural_render=True, include_vd=bool(ci["vd"]))
     fg_o, ba_o = np.moveaxis(ref["fg_feat"], 1, 2).reshape(-1, hs.C), ref["bg_alpha"].reshape(-1)
     pt = hs.cpu_points(name)
     e_s = float((np.abs(np.maximum(pt["sigma64"], 0.0) - pt["sigma"]) / pt["sigma_mag"]).max())

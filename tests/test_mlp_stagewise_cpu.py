@@ -18,11 +18,12 @@ import numpy as np
 import pytest
 
 import head_stagewise as hs
+import hier_stagewise as hh
 import mlp_stagewise as ms
 
 ALL = list(hs.CASES)
 FMA_CASES = ("one", "ragged")      # the one-fmaf-per-k chain costs a numpy pass per k: two rays of two small cases
-FAULT_CASES = ("ragged", "span", "contrast")
+FAULT_CASES = ("ragged", "span", "contrast", "hier")
 
 
 @functools.lru_cache(maxsize=None)
@@ -32,7 +33,8 @@ def emul_rays(name):
     R = ci["B"] * ci["n_rays"]
     if R <= 21:
         return tuple(range(R))
-    return tuple(sorted(set(np.linspace(0, R - 1, 16).astype(int).tolist()) | set(range(0, R, ci["n_rays"]))))
+    edge = {hh.EDGE_RAY} if ci["planes"] is not None else set()    # a given-plane case: the ray whose planes are made by hand
+    return tuple(sorted(set(np.linspace(0, R - 1, 16).astype(int).tolist()) | set(range(0, R, ci["n_rays"])) | edge))
 
 
 @functools.lru_cache(maxsize=None)
@@ -42,7 +44,7 @@ def ref_of(name, prec):
 
 
 def restrict(ref, n):
-    return {k: v[:n] for k, v in ref.items()}
+    return {k: (v if isinstance(v, str) else v[:n]) for k, v in ref.items()}
 
 
 def composited(src, ref, sigma, g, prec, fault=None):
@@ -77,10 +79,13 @@ def modes_of(name, prec):
     return ms.MODES + (("fma",) if prec == "fp32" and name in FMA_CASES else ())
 
 
+BASE = tuple(n for n in ALL if n not in ms.GIVEN_CASES)    # the cases the table FLOOR is measured over
+
+
 @functools.lru_cache(maxsize=None)
-def measured(prec):
+def measured(prec, cases=BASE):
     out = {}
-    for name in ALL:
+    for name in cases:
         for mode in modes_of(name, prec):
             f = emulation(name, prec, mode)["figs"]
             for family, key in (("sigma", "sigma_chain"), ("sigma_rms", "sigma_rms_chain"), ("g", "g"), ("g_rms", "g_rms"), ("zsum", "zsum"), ("eps", "eps")):
@@ -100,6 +105,20 @@ def test_floor_is_its_recorded_constant(family, prec):
 
 
 @pytest.mark.parametrize("prec", ms.PRECISIONS)
+@pytest.mark.parametrize("family", ms.FAMILIES)
+def test_floor_of_the_given_plane_cases(family, prec):
+    """hier and hier_span: below the table's floor, or the family has its own entry in FLOOR_GIVEN, which is then the measured floor
+    rounded up and above the table's (an entry of its own only where the table does not hold)"""
+    r, where = measured(prec, ms.GIVEN_CASES)[family]
+    rec, own = ms.FLOOR[family][prec], ms.FLOOR_GIVEN.get(family, {}).get(prec)
+    print("%-10s %-7s given planes: measured floor %.3e (%s), table %.3e, own entry %s" % (family, prec, r, where, rec, own))
+    if own is None:
+        assert 0.0 < r <= rec
+    else:
+        assert rec < own and r <= own <= 1.25 * r
+
+
+@pytest.mark.parametrize("prec", ms.PRECISIONS)
 @pytest.mark.parametrize("name", ALL)
 def test_every_emulation_passes_every_rule(name, prec):
     for mode in modes_of(name, prec):
@@ -109,12 +128,16 @@ def test_every_emulation_passes_every_rule(name, prec):
 
 
 @pytest.mark.parametrize("prec", ms.PRECISIONS)
-@pytest.mark.parametrize("name", ms.SHARE_CASES)
+@pytest.mark.parametrize("name", ms.SHARE_CASES + ms.GIVEN_CASES)
 def test_rule_1_judges_nine_tenths_of_the_positive_densities(name, prec):
+    """the given-plane cases print their share only, as deep and contrast do: fine planes cluster, a tenth of a uniform slab apart and
+    less, and the recovery's conditioning (with the one-ulp expf of these cases) grows as 1 / dist past half the density unit: the float64
+    reference alone keeps 0.73 (hier) and 0.55 (hier_span) of the positive densities in fp32, 0.94 - 0.98 in the other precisions, so
+    the two cases are not in SHARE_CASES"""
     for mode in modes_of(name, prec):
         share = emulation(name, prec, mode)["figs"]["share"]
         print("%s %s %s: %.3f of the live samples with a positive reference density are judged" % (name, prec, mode, share))
-        assert share >= ms.SHARE_MIN, (name, prec, mode, share)
+        assert name in ms.GIVEN_CASES or share >= ms.SHARE_MIN, (name, prec, mode, share)
 
 
 def test_the_chain_agrees_with_the_restated_chain_of_the_head_pin():
@@ -142,7 +165,7 @@ CHAIN_FAULTS = {
     "neighbour_bias": ("neighbour_bias",), "no_pe_L5": ("no_pe_L5",), "col63": ("col63",), "density_row1": ("density_row1",),
     "no_density_bias": ("no_density_bias",), "no_wlo_xhi": ("no_wlo_xhi",), "no_xlo": ("no_xlo",),
 }
-COMPOSITE_FAULTS = ("dead_dist", "inclusive", "no_eps", "tprod_lane30", "zval_shift", "g_prev_weight")
+COMPOSITE_FAULTS = ("dead_dist", "inclusive", "no_eps", "tprod_lane30", "zval_shift", "g_prev_weight", "min_dist")
 X3_ONLY = ("no_wlo_xhi", "no_xlo")
 FAULTS = list(CHAIN_FAULTS) + ["pack_trunc"] + list(COMPOSITE_FAULTS)
 

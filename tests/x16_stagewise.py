@@ -73,6 +73,15 @@ DW_FLOOR = {
     "bias": 1.3e-7,      # row sums of dZ_l (bias gradients, per-frame folded biases)
     "latent": 1.7e-7,    # latent columns of modules 0, 5, RGB_layer_1 and d_shape / d_appea / d_audio, from the per-frame sums
 }
+# the given-plane case e_hier where its measured floor is above the table's: its own entries, the table stays
+DW_FLOOR_GIVEN = {"pe": 2.7e-7, "bias": 1.5e-7, "latent": 1.9e-7}   # measured 2.617e-7, 1.471e-7, 1.830e-7
+
+
+def dw_floor(name, fam):
+    """the weight-gradient floor of family fam in case name"""
+    return DW_FLOOR_GIVEN.get(fam, DW_FLOOR[fam]) if CASES[name].get("hier") else DW_FLOOR[fam]
+
+
 # spread between the two bias routes of the free-running CPU emulation (free_forward, route_spread), cases a - c; the inference
 # kernel is held to 4 x this against the training forward
 ROUTE_FLOOR = {"weight": 5.0e-4, "fg_feat": 8.0e-4, "bg_alpha": 6.0e-4}   # measured 4.6e-4, 7.1e-4, 5.7e-4 (case a)
@@ -734,6 +743,8 @@ CASES = {
     "c": dict(B=2, n_rays=25, n_samples=40, weights="seed0", kw={}),
     "d_contrast": dict(B=2, n_rays=16, n_samples=24, weights="contrast", kw={}),
     "d_gaze": dict(B=2, n_rays=16, n_samples=24, weights="seed0", kw={"include_gaze": True, "eye_gaze_dim": 64, "audio_dim": 0}),
+    # the hierarchical pass: z_planes_given = 1; case_inputs returns the 16 + 24 + 1 planes (hier_stagewise.given_planes) where t_rand goes
+    "e_hier": dict(B=2, n_rays=16, n_samples=40, weights="seed0", kw={}, hier=(16, 24)),
 }
 FEATMAP_SIZE = 8  # the rays of a case are taken from an 8 x 8 grid
 
@@ -760,6 +771,11 @@ def case_inputs(name):
     inp = dict(inp)
     inp["batch_xy"] = inp["batch_xy"][:, :, rays].contiguous()
     t_rand = syn.stratified_noise(c["B"], c["n_rays"], c["n_samples"], 7)
+    if c.get("hier"):   # given planes [B, rays, samples + 1]: the kernels take them through the t_rand argument
+        import hier_stagewise as hh
+        t_rand = torch.from_numpy(hh.given_planes(inp["batch_Tvecs"].numpy().reshape(c["B"], 3)[:, 2], c["n_rays"], c["hier"][0], c["hier"][1], 0,
+                                                  opt.world_z1, opt.world_z2))
+        assert tuple(t_rand.shape) == (c["B"], c["n_rays"], c["n_samples"] + 1)
     d_merge = torch.randn(c["B"], c["n_rays"], 256, generator=torch.Generator().manual_seed(9))
     return opt, sd, inp, rays, t_rand, d_merge
 
@@ -771,8 +787,9 @@ def mlp_arrays(sd, prefix="fg_CD_predictor."):
     return ws, bs
 
 
-def sample_points64(xy, R, T, Kinv, n_samples, z1, z2, t_rand):
-    """GenSamplePoints in float64 (n3dt_device.h:33-106): points [B, rays, samples, 3], plane distances [B, rays, samples]"""
+def sample_points64(xy, R, T, Kinv, n_samples, z1, z2, t_rand, given=False):
+    """GenSamplePoints in float64 (n3dt_device.h:33-106): points [B, rays, samples, 3], plane distances [B, rays, samples].
+    given (z_planes_given, n3dt_device.h:90-93): t_rand holds the samples + 1 planes of every ray themselves"""
     xy, R, T, Kinv, t_rand = (np.asarray(a, dtype=np.float64) for a in (xy, R, T, Kinv, t_rand))
     B, _, n_rays = xy.shape
     h = np.concatenate([xy, np.ones((B, 1, n_rays))], axis=1)
@@ -785,7 +802,7 @@ def sample_points64(xy, R, T, Kinv, n_samples, z1, z2, t_rand):
     mid = 0.5 * (zv[:, 1:] + zv[:, :-1])
     lower = np.concatenate([zv[:, :1], mid], axis=1)
     upper = np.concatenate([mid, zv[:, -1:]], axis=1)
-    z = lower[:, None, :] + (upper - lower)[:, None, :] * t_rand           # [B, rays, edges]
+    z = t_rand if given else lower[:, None, :] + (upper - lower)[:, None, :] * t_rand           # [B, rays, edges]
     dist = (z[..., 1:] - z[..., :-1]) * l[..., None]
     pts = T[:, None, None, :] + (np.moveaxis(d, 1, 2) * l[..., None])[:, :, None, :] * z[..., :-1, None]
     return pts, dist
@@ -830,7 +847,7 @@ class Emulation:
         fold[:, bias_offset(10):bias_offset(10) + 192] = (b64[10] + w64[10][:, :384] @ b64[9] + appea @ w64[10][:, 384:].T).astype(np.float32)
         # sample points of padded blocks: lanes beyond n_samples carry the point 0 and dist 0 (n3dt_device.h:101-105)
         pts, dist = sample_points64(inp["batch_xy"].numpy(), inp["batch_Rmats"].numpy(), inp["batch_Tvecs"].numpy(), inp["batch_inv_inmats"].numpy(),
-                                    Ns, opt.world_z1, opt.world_z2, t_rand.numpy())
+                                    Ns, opt.world_z1, opt.world_z2, t_rand.numpy(), given=bool(c.get("hier")))
         P = np.zeros((B, n_rays, bpr * 32, 3))
         P[:, :, :Ns] = pts
         D = np.zeros((B, n_rays, bpr * 32), dtype=np.float32)
