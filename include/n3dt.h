@@ -657,6 +657,69 @@ int n3dt_fan_points(int n, int num_landmarks, const float* heat, int64_t frame_s
 int n3dt_fan_tail(int n, int num_landmarks, int points_out, int height, int width, const double* pts, const int32_t* decode_status,
                   const int32_t* boxes, const int32_t* table, int carry, double* out, int32_t* status, void* stream);
 
+/* ---- head-mask generator: BiSeNet parsing to head and eye masks ---------------------------------------
+ * The reference's DataProcess/Gen_HeadMask.py: BiSeNet(n_classes) over DataProcess/resnet.py's ResNet-18, frozen and
+ * inference-only, with the caller's weights, then argmax, LUT, largest component, hair erosion, largest component, green-screen
+ * filter and the dilated eye mask, on byte maps.  csrc/head_mask.hip; the table, the run-time geometry and the index rules are
+ * csrc/head_mask_core.h.  n_classes 1..32; any image 32..4096 high and wide.
+ * Convolutions (weight[j]; bn_*[j] the BatchNorm behind it or NULL; eps 1e-5 unless bn_eps says otherwise), state-dict order:
+ *   0 cp.resnet.conv1; then per BasicBlock conv1, conv2 and (layer2..4, block 0) downsample.0: 1..4 layer1, 5..9 layer2, 10..14
+ *   layer3, 15..19 layer4; 20, 21 cp.arm16's conv, conv_atten; 22, 23 cp.arm32's; 24 cp.conv_head32; 25 cp.conv_head16; 26
+ *   cp.conv_avg; 27..29 ffm's convblk, conv1, conv2; 30, 31 conv_out's conv, conv_out; 32, 33 conv_out16's; 34, 35 conv_out32's.
+ * Blocks of the single-block entry: the 36 convolutions, then 36 the max pool.  A spatial block takes in [n,C_in,src_height,
+ *   src_width], read as a height x width map through torch's nearest rule, and gives [n,C_out,Ho,Wo]; aux is the shortcut
+ *   [n,C_out,Ho,Wo] of a BasicBlock's conv2 (required there), the second 128 channels of block 27's input (required), or, with
+ *   scale on block 25, a map [n,128,src_height,src_width] added behind the scale.  scale, addvec [n,C_in] (blocks 24, 25, 30
+ *   only, 16-byte aligned): the fetched value v becomes v * scale + (addvec | aux | v on block 30 | 0).  The five small blocks (21,
+ *   23, 26, 28, 29) average in [n,C_in,height,width] and give [n,C_out] through the 1 x 1 convolution in float64.
+ * fwd: x [n,3,height,width] fp32, normalised -> for bit o of `outputs` (1 out, 2 out16, 4 out32) the map at out / out16 / out32:
+ *   [n,n_classes,h,w] low-resolution logits (h, w: 1/8, 1/8 and 1/16 by the convolutions' floor rules), or with `upsample`
+ *   [n,n_classes,height,width], bilinear with align_corners.  Only the convolutions the selected outputs need are run.
+ * frames: bytes [n,height,width,3] RGB, or (frames_are_float) fp32 [n,3,height,width] in [0,1] rounded once -> rgb bytes
+ *   [n,height,width,3] and x = (byte / 255 - mean) / std with the ImageNet constants, fp32.
+ * resize: bytes [n,src_height,src_width,channels] -> [n,height,width,channels], bilinear with half-pixel centres in float64, rounded
+ *   to the nearest byte; OpenCV's fixed-point INTER_LINEAR is not reproduced.
+ * labels: logits [n,n_classes,h,w] -> uint8 [n,height,width]: argmax of the align_corners interpolation, float64, first maximum.
+ * green: rgb -> 255 where OpenCV's 8-bit hue of the bytes taken as (B, G, R) lies in hue_lo..hue_hi, else 0.
+ * postprocess: labels, rgb, lut [256], element [elem_h, elem_w] anchored at (anchor_y, anchor_x) -> head, eye [n,height,width]
+ *   in {0, 255}.  Integer atomics only; the result does not depend on scheduling.
+ * Everything is enqueued on `stream`, nothing synchronises.  Workspaces: 256-byte aligned, caller-owned, never cleared; their
+ * contents do not matter. */
+#define N3DT_HEAD_MASK_CONVS 36
+#define N3DT_HEAD_MASK_BLOCKS 37
+#define N3DT_HEAD_MASK_MAX_CLASSES 32
+typedef struct N3dtHeadMaskParams {
+    int32_t n_classes, reserved;
+    const float* weight[N3DT_HEAD_MASK_CONVS];
+    const float* bn_weight[N3DT_HEAD_MASK_CONVS];
+    const float* bn_bias[N3DT_HEAD_MASK_CONVS];
+    const float* bn_mean[N3DT_HEAD_MASK_CONVS];
+    const float* bn_var[N3DT_HEAD_MASK_CONVS];
+    double bn_eps;
+} N3dtHeadMaskParams;
+size_t n3dt_head_mask_packed_bytes(void);
+int n3dt_head_mask_pack(const N3dtHeadMaskParams* p, void* packed, void* stream);
+int n3dt_head_mask_max_images(int height, int width);
+size_t n3dt_head_mask_workspace_bytes(int n, int height, int width);
+int n3dt_head_mask_fwd(int n, int height, int width, int n_classes, const void* packed, const float* x, int outputs, int upsample,
+                       float* out, float* out16, float* out32, void* workspace, size_t workspace_bytes, void* stream);
+size_t n3dt_head_mask_block_workspace_bytes(int block, int n, int height, int width, int src_height, int src_width);
+int n3dt_head_mask_block(int block, int n, int height, int width, int src_height, int src_width, int n_classes, const void* packed,
+                         const float* in, const float* aux, const float* scale, const float* addvec, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int n3dt_head_mask_frames(int n, int height, int width, const void* frames, int frames_are_float, uint8_t* rgb, float* x,
+                          void* stream);
+int n3dt_head_mask_resize(int n, int src_height, int src_width, int channels, const uint8_t* src, int height, int width, uint8_t* dst,
+                          void* stream);
+int n3dt_head_mask_labels(int n, int n_classes, int h, int w, int height, int width, const float* logits, uint8_t* labels,
+                          void* stream);
+int n3dt_head_mask_green(int n, int height, int width, const uint8_t* rgb, int hue_lo, int hue_hi, uint8_t* cleared, void* stream);
+size_t n3dt_head_mask_postprocess_workspace_bytes(int n, int height, int width);
+int n3dt_head_mask_postprocess(int n, int height, int width, const uint8_t* labels, const uint8_t* rgb, const uint8_t* lut,
+                               const uint8_t* element, int elem_h, int elem_w, int anchor_y, int anchor_x, int dilations, int erosions,
+                               int hue_lo, int hue_hi, uint8_t* head, uint8_t* eye, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* ---- fused loss tail -----------------------------------------------------------------
  * The three MSE data terms of the reference's loss (Utils/HeadNeRFLossUtils.py:125-146: bg_loss, head_loss,
  * nonhead_loss, including its nan_to_num) in one pass, and their gradient in one more; replaces three boolean-mask

@@ -21,6 +21,7 @@
 #include "s3fd_core.h"
 #include "face_recon_core.h"
 #include "fan_core.h"
+#include "head_mask_core.h"
 
 static thread_local char g_err[256] = "";
 
@@ -1280,6 +1281,200 @@ extern "C" int n3dt_fan_tail(int n, int num_landmarks, int points_out, int heigh
     else if ((((size_t)pts) | ((size_t)out)) & 7) what = "pts and out must be 8-byte aligned";
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
     n3dt_launch_fan_tail(n, num_landmarks, points_out, height, width, pts, decode_status, boxes, table, carry ? 1 : 0, out, status, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// The head-mask generator (csrc/head_mask.hip): the limits of include/n3dt.h, checked before anything is enqueued
+static const char* head_mask_size(int n, int height, int width) {
+    if (!hm_hw_ok(height, width)) return "height and width must be in 32..4096";
+    if (n < 1 || n > hm_max_images(height, width)) return "n outside 1..n3dt_head_mask_max_images (the workspace budget)";
+    return nullptr;
+}
+
+static const char* head_mask_pixels(int n, int height, int width) {
+    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (n < 1 || (size_t)n * height * width > ((size_t)1 << 30)) return "n outside 1..2^30 / (height width)";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_head_mask_packed_bytes(void) { return n3dt_head_mask_packed_layout_bytes(); }
+
+extern "C" int n3dt_head_mask_pack(const N3dtHeadMaskParams* p, void* packed, void* stream) {
+    static const char* who = "n3dt_head_mask_pack";
+    if (!p || !packed) return failf(N3DT_EINVAL, "%s: NULL argument", who);
+    if (((size_t)packed) & 255) return failf(N3DT_EINVAL, "%s: packed must be 256-byte aligned", who);
+    if (p->n_classes < 1 || p->n_classes > HM_MAX_CLASSES) return failf(N3DT_EINVAL, "%s: n_classes outside 1..32", who);
+    if (!(p->bn_eps > 0.0) || !(p->bn_eps < 1.0)) return failf(N3DT_EINVAL, "%s: bn_eps outside (0, 1)", who);
+    for (int j = 0; j < HM_CONVS; ++j) {
+        if (!p->weight[j]) return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+        if (HM_TABLE[j].bn && (!p->bn_weight[j] || !p->bn_bias[j] || !p->bn_mean[j] || !p->bn_var[j]))
+            return failf(N3DT_EINVAL, "%s: NULL parameter pointer", who);
+    }
+    n3dt_launch_head_mask_pack(p, packed, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_head_mask_max_images(int height, int width) {
+    if (!hm_hw_ok(height, width)) {
+        (void)fail(N3DT_EINVAL, "n3dt_head_mask_max_images: height and width must be in 32..4096");
+        return 0;
+    }
+    return hm_max_images(height, width);
+}
+
+extern "C" size_t n3dt_head_mask_workspace_bytes(int n, int height, int width) {
+    const char* what = head_mask_size(n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_head_mask_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_head_mask_ws_bytes(n, height, width);
+}
+
+extern "C" int n3dt_head_mask_fwd(int n, int height, int width, int n_classes, const void* packed, const float* x, int outputs, int upsample,
+                                  float* out, float* out16, float* out32, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_head_mask_fwd";
+    const char* what = head_mask_size(n, height, width);
+    float* outs[3] = {out, out16, out32};
+    if (!what) {
+        if (n_classes < 1 || n_classes > HM_MAX_CLASSES) what = "n_classes outside 1..32";
+        else if (outputs < 1 || outputs > 7) what = "outputs must be a non-empty set of bits 1, 2, 4";
+        else if (!packed || !x || !workspace) what = "NULL pointer";
+        else if (((outputs & 1) && !out) || ((outputs & 2) && !out16) || ((outputs & 4) && !out32)) what = "a selected output is NULL";
+        else if ((((size_t)x) | ((size_t)out) | ((size_t)out16) | ((size_t)out32)) & 3) what = "x and the outputs must be 4-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_head_mask_ws_bytes(n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_fwd(n, height, width, n_classes, packed, x, outputs, upsample ? 1 : 0, outs, workspace, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+// one block at a caller-given geometry: the output must not be empty, and the maps stay inside the workspace budget
+static const char* head_mask_block_size(int block, int n, int height, int width, int src_height, int src_width) {
+    if (block < 0 || block >= HM_BLOCKS) return "block outside 0..36";
+    if (n < 1 || n > HM_MAX_IMAGES) return "n outside 1..1024";
+    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (src_height < 1 || src_width < 1 || src_height > height || src_width > width) return "src_height and src_width must be in 1..height, 1..width";
+    const bool resamples = block == HM_HEAD32 || block == HM_HEAD16;
+    if (!resamples && (src_height != height || src_width != width)) return "only blocks 24 and 25 read through the nearest upsample";
+    if (block == 0 && (height < 2 || width < 2)) return "the stem needs 2 x 2 pixels";
+    if (n3dt_head_mask_block_ws_bytes(block, n, height, width, src_height, src_width) > HM_WS_BUDGET) return "the block's maps exceed the workspace budget";
+    return nullptr;
+}
+
+extern "C" size_t n3dt_head_mask_block_workspace_bytes(int block, int n, int height, int width, int src_height, int src_width) {
+    const char* what = head_mask_block_size(block, n, height, width, src_height, src_width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_head_mask_block_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_head_mask_block_ws_bytes(block, n, height, width, src_height, src_width);
+}
+
+extern "C" int n3dt_head_mask_block(int block, int n, int height, int width, int src_height, int src_width, int n_classes, const void* packed,
+                                    const float* in, const float* aux, const float* scale, const float* addvec, float* out, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    static const char* who = "n3dt_head_mask_block";
+    const char* what = head_mask_block_size(block, n, height, width, src_height, src_width);
+    if (!what) {
+        const bool conv = block < HM_CONVS;
+        const bool needs_aux = conv && (hm_takes_skip(block) || block == HM_FFM_BLK);
+        const bool may_aux = needs_aux || (block == HM_HEAD16 && scale);
+        const bool may_scale = block == HM_HEAD32 || block == HM_HEAD16 || block == HM_OUT;
+        if (n_classes < 1 || n_classes > HM_MAX_CLASSES) what = "n_classes outside 1..32";
+        else if (!packed || !in || !out || !workspace) what = "NULL pointer";
+        else if (needs_aux && !aux) what = "this block takes aux (a shortcut, or the second half of the channels)";
+        else if (!may_aux && aux) what = "this block takes no aux";
+        else if (!may_scale && (scale || addvec)) what = "only blocks 24, 25 and 30 take a scale";
+        else if (addvec && !scale) what = "addvec needs a scale";
+        else if (addvec && (aux || block == HM_OUT)) what = "one added term at most";
+        else if ((((size_t)in) | ((size_t)out) | ((size_t)aux)) & 3) what = "in, aux and out must be 4-byte aligned";
+        else if ((((size_t)scale) | ((size_t)addvec)) & 15) what = "scale and addvec must be 16-byte aligned";
+        else if ((((size_t)packed) | ((size_t)workspace)) & 255) what = "packed and the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_head_mask_block_ws_bytes(block, n, height, width, src_height, src_width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_block(block, n, height, width, src_height, src_width, n_classes, packed, in, aux, scale, addvec, out, workspace,
+                                (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_head_mask_frames(int n, int height, int width, const void* frames, int frames_are_float, uint8_t* rgb, float* x, void* stream) {
+    static const char* who = "n3dt_head_mask_frames";
+    const char* what = head_mask_pixels(n, height, width);
+    if (!what) {
+        if (!frames || !rgb || !x) what = "NULL pointer";
+        else if ((((size_t)x) | (frames_are_float ? (size_t)frames : 0)) & 3) what = "x and float frames must be 4-byte aligned";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_frames(n, height, width, frames, frames_are_float ? 1 : 0, rgb, x, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_head_mask_resize(int n, int src_height, int src_width, int channels, const uint8_t* src, int height, int width, uint8_t* dst,
+                                     void* stream) {
+    static const char* who = "n3dt_head_mask_resize";
+    const char* what = head_mask_pixels(n, height, width);
+    if (!what) what = head_mask_pixels(n, src_height, src_width);
+    if (!what) {
+        if (channels < 1 || channels > 4) what = "channels outside 1..4";
+        else if (!src || !dst) what = "NULL pointer";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_resize(n, src_height, src_width, channels, src, height, width, dst, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_head_mask_labels(int n, int n_classes, int h, int w, int height, int width, const float* logits, uint8_t* labels, void* stream) {
+    static const char* who = "n3dt_head_mask_labels";
+    const char* what = head_mask_pixels(n, height, width);
+    if (!what) {
+        if (n_classes < 1 || n_classes > 256) what = "n_classes outside 1..256";
+        else if (h < 1 || w < 1 || h > SN_MAX_FRAME_HW || w > SN_MAX_FRAME_HW) what = "h and w must be in 1..4096";
+        else if (!logits || !labels) what = "NULL pointer";
+        else if (((size_t)logits) & 3) what = "logits must be 4-byte aligned";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_labels(n, n_classes, h, w, height, width, logits, labels, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" int n3dt_head_mask_green(int n, int height, int width, const uint8_t* rgb, int hue_lo, int hue_hi, uint8_t* cleared, void* stream) {
+    static const char* who = "n3dt_head_mask_green";
+    const char* what = head_mask_pixels(n, height, width);
+    if (!what && (!rgb || !cleared)) what = "NULL pointer";
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_green(n, height, width, rgb, hue_lo, hue_hi, cleared, (hipStream_t)stream);
+    return check_hip(who);
+}
+
+extern "C" size_t n3dt_head_mask_postprocess_workspace_bytes(int n, int height, int width) {
+    const char* what = head_mask_pixels(n, height, width);
+    if (what) {
+        (void)failf(N3DT_EINVAL, "n3dt_head_mask_postprocess_workspace_bytes: %s", what);
+        return 0;
+    }
+    return n3dt_head_mask_post_ws_bytes(n, height, width);
+}
+
+extern "C" int n3dt_head_mask_postprocess(int n, int height, int width, const uint8_t* labels, const uint8_t* rgb, const uint8_t* lut,
+                                          const uint8_t* element, int elem_h, int elem_w, int anchor_y, int anchor_x, int dilations, int erosions,
+                                          int hue_lo, int hue_hi, uint8_t* head, uint8_t* eye, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    static const char* who = "n3dt_head_mask_postprocess";
+    const char* what = head_mask_pixels(n, height, width);
+    if (!what) {
+        if (!labels || !rgb || !lut || !element || !head || !eye || !workspace) what = "NULL pointer";
+        else if (elem_h < 1 || elem_w < 1 || elem_h > HM_MAX_ELEMENT || elem_w > HM_MAX_ELEMENT) what = "the element must be 1..64 high and wide";
+        else if (anchor_y < 0 || anchor_y >= elem_h || anchor_x < 0 || anchor_x >= elem_w) what = "the anchor lies outside the element";
+        else if (dilations < 0 || dilations > 64 || erosions < 0 || erosions > 1024) what = "dilations outside 0..64 or erosions outside 0..1024";
+        else if (((size_t)workspace) & 255) what = "the workspace must be 256-byte aligned";
+        else if (workspace_bytes < n3dt_head_mask_post_ws_bytes(n, height, width)) what = "workspace too small";
+    }
+    if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
+    n3dt_launch_head_mask_postprocess(n, height, width, labels, rgb, lut, element, elem_h, elem_w, anchor_y, anchor_x, dilations, erosions, hue_lo, hue_hi,
+                                      head, eye, workspace, (hipStream_t)stream);
     return check_hip(who);
 }
 

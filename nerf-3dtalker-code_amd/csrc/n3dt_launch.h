@@ -228,4 +228,22 @@ void n3dt_launch_fan_crops(int n, int H, int W, const float* frames, const int* 
 void n3dt_launch_fan_points(int n, int N, const float* heat, long long frame_stride, double* pts, int* status, hipStream_t st);
 void n3dt_launch_fan_tail(int n, int N, int P, int H, int W, const double* pts, const int* dstatus, const int* boxes, const int* table,
                           int carry, double* out, int* status, hipStream_t st);
+
+// ---- head_mask.hip
+size_t n3dt_head_mask_packed_layout_bytes(void);
+size_t n3dt_head_mask_ws_bytes(int n, int H, int W);
+size_t n3dt_head_mask_block_ws_bytes(int block, int n, int Hi, int Wi, int Hs, int Ws);
+size_t n3dt_head_mask_post_ws_bytes(int n, int H, int W);
+void n3dt_launch_head_mask_pack(const N3dtHeadMaskParams* p, void* packed, hipStream_t st);
+void n3dt_launch_head_mask_fwd(int n, int H, int W, int n_classes, const void* packed, const float* x, int outputs, int upsample,
+                               float* const* out, void* workspace, hipStream_t st);
+void n3dt_launch_head_mask_block(int block, int n, int Hi, int Wi, int Hs, int Ws, int n_classes, const void* packed, const float* in,
+                                 const float* aux, const float* scale, const float* addvec, float* out, void* workspace, hipStream_t st);
+void n3dt_launch_head_mask_frames(int n, int H, int W, const void* frames, int is_float, uint8_t* rgb, float* x, hipStream_t st);
+void n3dt_launch_head_mask_resize(int n, int Hs, int Ws, int C, const uint8_t* src, int Hd, int Wd, uint8_t* dst, hipStream_t st);
+void n3dt_launch_head_mask_labels(int n, int nc, int h, int w, int H, int W, const float* logits, uint8_t* labels, hipStream_t st);
+void n3dt_launch_head_mask_green(int n, int H, int W, const uint8_t* rgb, int hue_lo, int hue_hi, uint8_t* cleared, hipStream_t st);
+void n3dt_launch_head_mask_postprocess(int n, int H, int W, const uint8_t* labels, const uint8_t* rgb, const uint8_t* lut, const uint8_t* element,
+                                       int eh, int ew, int ay, int ax, int dilations, int erosions, int hue_lo, int hue_hi, uint8_t* head,
+                                       uint8_t* eye, void* workspace, hipStream_t st);
 }

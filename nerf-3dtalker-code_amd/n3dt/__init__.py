@@ -9,5 +9,6 @@ from .wav2lip import Wav2Lip, Wav2LipClip, load_wav2lip  # noqa: F401
 from .s3fd import S3FD, load_s3fd  # noqa: F401
 from .face_recon import FaceRecon, load_face_recon  # noqa: F401
 from .fan import FAN, load_fan  # noqa: F401
+from .head_mask import HeadMask, load_head_mask  # noqa: F401
 from .train import validate  # noqa: F401
-from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet, wav2lip, s3fd, face_recon, fan  # noqa: F401,E402
+from . import checkpoint, render_utils, parallel, train, fitting, audio, optim, eval_utils, mel, syncnet, wav2lip, s3fd, face_recon, fan, head_mask  # noqa: F401,E402

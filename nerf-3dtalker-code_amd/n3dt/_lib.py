@@ -88,6 +88,17 @@ class FanParams(ctypes.Structure):
                 [("coords256", ctypes.c_void_p), ("coords64", ctypes.c_void_p)])
 
 
+HEAD_MASK_CONVS = 36
+HEAD_MASK_BLOCKS = 37
+HEAD_MASK_MAX_CLASSES = 32
+
+
+class HeadMaskParams(ctypes.Structure):
+    _fields_ = ([("n_classes", ctypes.c_int32), ("reserved", ctypes.c_int32)] +
+                [(name, ctypes.c_void_p * HEAD_MASK_CONVS) for name in ("weight", "bn_weight", "bn_bias", "bn_mean", "bn_var")] +
+                [("bn_eps", ctypes.c_double)])
+
+
 class A2sParams(ctypes.Structure):
     _fields_ = [("w_ih", ctypes.c_void_p * 4), ("w_hh", ctypes.c_void_p * 4), ("b_ih", ctypes.c_void_p * 4), ("b_hh", ctypes.c_void_p * 4),
                 ("lin_w", ctypes.c_void_p * 3), ("lin_b", ctypes.c_void_p * 3)]
@@ -258,6 +269,19 @@ def _signatures():
         "n3dt_fan_crops": (ci, [ci, ci, ci, vp, vp, vp, vp]),
         "n3dt_fan_points": (ci, [ci, ci, vp, i64, vp, vp, vp]),
         "n3dt_fan_tail": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
+        "n3dt_head_mask_packed_bytes": (sz, []),
+        "n3dt_head_mask_pack": (ci, [ctypes.POINTER(HeadMaskParams), vp, vp]),
+        "n3dt_head_mask_max_images": (ci, [ci, ci]),
+        "n3dt_head_mask_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_head_mask_fwd": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp]),
+        "n3dt_head_mask_block_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
+        "n3dt_head_mask_block": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "n3dt_head_mask_frames": (ci, [ci, ci, ci, vp, ci, vp, vp, vp]),
+        "n3dt_head_mask_resize": (ci, [ci, ci, ci, ci, vp, ci, ci, vp, vp]),
+        "n3dt_head_mask_labels": (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp]),
+        "n3dt_head_mask_green": (ci, [ci, ci, ci, vp, ci, ci, vp, vp]),
+        "n3dt_head_mask_postprocess_workspace_bytes": (sz, [ci, ci, ci]),
+        "n3dt_head_mask_postprocess": (ci, [ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
         # the entry points include/n3dt_flat_adam_guard.h declares (n3dt.h includes that file)
         "n3dt_flat_adam_guard_bytes": (sz, []),
         "n3dt_flat_adam_guarded_step": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp]),

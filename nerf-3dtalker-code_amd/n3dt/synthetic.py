@@ -603,6 +603,89 @@ def fan_state_dict(seed=0, num_modules=4, num_landmarks=98):
     return sd
 
 
+HEAD_MASK_BN2_GAMMA = 0.5
+HEAD_MASK_HEAD_SCALE = 8.0
+HEAD_MASK_CALIBRATION_IMAGES = 2
+
+
+def _head_mask_mids(sd, x):
+    """the inputs of the three heads' last 1 x 1 convolutions, float64, for x [n,3,H,W]"""
+    import torch.nn.functional as F
+    w = lambda k: sd[k].double()  # noqa: E731
+
+    def bn(name, t):
+        g = w(name + ".weight") / torch.sqrt(w(name + ".running_var") + 1e-5)
+        return (t - w(name + ".running_mean")[None, :, None, None]) * g[None, :, None, None] + w(name + ".bias")[None, :, None, None]
+
+    def cbr(name, t, pad=1):
+        return torch.relu(bn(name + ".bn", F.conv2d(t, w(name + ".conv.weight"), None, 1, pad)))
+
+    def arm(name, t):
+        f = cbr(name + ".conv", t)
+        return f * torch.sigmoid(bn(name + ".bn_atten", F.conv2d(f.mean((2, 3), keepdim=True), w(name + ".conv_atten.weight"))))
+
+    r = "cp.resnet."
+    t = F.max_pool2d(torch.relu(bn(r + "bn1", F.conv2d(x, w(r + "conv1.weight"), None, 2, 3))), 3, 2, 1)
+    feats = []
+    for layer in range(1, 5):
+        for b in range(2):
+            p = "%slayer%d.%d." % (r, layer, b)
+            s = 2 if (layer > 1 and b == 0) else 1
+            y = torch.relu(bn(p + "bn1", F.conv2d(t, w(p + "conv1.weight"), None, s, 1)))
+            y = bn(p + "bn2", F.conv2d(y, w(p + "conv2.weight"), None, 1, 1))
+            sc = bn(p + "downsample.1", F.conv2d(t, w(p + "downsample.0.weight"), None, s, 0)) if p + "downsample.0.weight" in sd else t
+            t = torch.relu(sc + y)
+        feats.append(t)
+    _, f8, f16, f32 = feats
+    s32 = arm("cp.arm32", f32) + cbr("cp.conv_avg", f32.mean((2, 3), keepdim=True), 0)
+    cp16 = cbr("cp.conv_head32", F.interpolate(s32, f16.shape[2:], mode="nearest"))
+    cp8 = cbr("cp.conv_head16", F.interpolate(arm("cp.arm16", f16) + cp16, f8.shape[2:], mode="nearest"))
+    f = cbr("ffm.convblk", torch.cat([f8, cp8], 1), 0)
+    a = torch.sigmoid(F.conv2d(torch.relu(F.conv2d(f.mean((2, 3), keepdim=True), w("ffm.conv1.weight"))), w("ffm.conv2.weight")))
+    return cbr("conv_out.conv", f * a + f), cbr("conv_out16.conv", cp8), cbr("conv_out32.conv", cp16)
+
+
+def head_mask_state_dict(seed=0, n_classes=19):
+    """Seeded stand-in for the weights of the face parser (faceparsing_model.pth cannot be fetched offline), under the keys of the
+    reference's `BiSeNet(n_classes)` (n3dt.head_mask.load_head_mask).  Convolutions are He-scaled; BatchNorm statistics are near the
+    identity as in face_recon_state_dict, a residual branch's last BatchNorm and a downsample branch's carry gamma times
+    HEAD_MASK_BN2_GAMMA and sqrt(1 - HEAD_MASK_BN2_GAMMA^2).  The heads have no bias, and the features in front of them are
+    positive: as drawn, one class would win everywhere.  So each head's last 1 x 1 convolution, N(0, HEAD_MASK_HEAD_SCALE^2 /
+    C_in), is made orthogonal to the mean of its input over HEAD_MASK_CALIBRATION_IMAGES seeded noise images (float64; the
+    direction is quantised to float16 so that a last-bit difference between two machines' sums does not reach the weights): the
+    logits are then centred and every class wins somewhere.  Never stored."""
+    from .head_mask import CONVS, SKIP_BLOCKS
+    gen = torch.Generator().manual_seed(seed)
+    sd = {}
+    for j, (conv, bn, cin, cout, k, _, _, _, _) in enumerate(CONVS):
+        cout = cout or n_classes
+        scale = math.sqrt(2.0 / (cin * k * k)) if bn is not None else (HEAD_MASK_HEAD_SCALE if conv.endswith("conv_out") else 1.0) / math.sqrt(cin)
+        sd[conv + ".weight"] = torch.randn(cout, cin, k, k, generator=gen) * scale
+        if bn is None:
+            continue
+        gamma = 0.75 + 0.5 * torch.rand(cout, generator=gen)
+        if j in SKIP_BLOCKS:
+            gamma = gamma * HEAD_MASK_BN2_GAMMA
+        elif "downsample" in conv:
+            gamma = gamma * math.sqrt(1.0 - HEAD_MASK_BN2_GAMMA ** 2)
+        sd[bn + ".weight"] = gamma
+        sd[bn + ".bias"] = 0.1 + 0.1 * torch.randn(cout, generator=gen)
+        sd[bn + ".running_mean"] = 0.1 * torch.randn(cout, generator=gen)
+        sd[bn + ".running_var"] = 0.75 + 0.5 * torch.rand(cout, generator=gen)
+        sd[bn + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    x = torch.rand(HEAD_MASK_CALIBRATION_IMAGES, 3, 128, 128, generator=torch.Generator().manual_seed(991)).double()
+    x = (x - torch.tensor([0.485, 0.456, 0.406]).double()[None, :, None, None]) / torch.tensor([0.229, 0.224, 0.225]).double()[None, :, None, None]
+    with torch.no_grad():
+        mids = _head_mask_mids(sd, x)
+    for head, mid in zip(("conv_out", "conv_out16", "conv_out32"), mids):
+        mu = mid.mean((0, 2, 3))
+        u = (mu / mu.norm()).to(torch.float16).double()
+        wgt = sd[head + ".conv_out.weight"].double().flatten(1)
+        wgt = wgt - (wgt @ u)[:, None] * u[None, :] / (u @ u)
+        sd[head + ".conv_out.weight"] = wgt.float().reshape(n_classes, -1, 1, 1).contiguous()
+    return sd
+
+
 def face_recon_lm3d():
     """A stand-in for the [5,3] standard landmarks the reference's load_lm3d reads from its BFM folder (left eye, right eye, nose,
     left and right mouth corner; float64): a plausible face for smoke runs and timing, NOT the reference's values -- those the
