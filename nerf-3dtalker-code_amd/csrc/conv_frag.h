@@ -1,11 +1,13 @@
 /*
- * conv_frag.h -- the fragment arithmetic of the split-operand implicit-GEMM convolutions (vgg_loss.hip, lpips.hip, syncnet.hip;
- * DESIGN sections 3.10, 3.14, 3.16): where an element of a packed B matrix lies, and which output row an accumulator register is.
+ * conv_frag.h -- the fragment arithmetic of the split-operand implicit-GEMM convolutions (vgg_loss.hip, lpips.hip, syncnet.hip,
+ * wav2lip.hip, s3fd.hip, face_recon.hip, fan.hip, head_mask.hip; DESIGN sections 3.10, 3.14, 3.16 - 3.22): where an element of a
+ * packed B matrix lies, and which output row an accumulator register is.
  *
- * Included by csrc/conv_mfma.h, whose MFMA step reads its B fragments at cf_frag_group, by the three pack kernels, which decode
- * their element index with cf_pack_decode, by the three epilogues, which take their rows from cf_acc_row, and by
- * tests/lpips_core_host.cpp and tests/syncnet_core_host.cpp, which call the very same functions on the CPU.  Compiles as host C++
- * on its own; the __host__ __device__ qualifiers exist only under hipcc.
+ * Included by csrc/conv_mfma.h, whose MFMA step reads its B fragments at cf_frag_group, by the pack kernels (vgg's, lpips's,
+ * wav2lip's, s3fd's and conv_net.hip's shared one), which decode their element index with cf_pack_decode, by the eight
+ * epilogues, which take their rows from cf_acc_row, and by tests/lpips_core_host.cpp and the six networks' host walks
+ * (tests/syncnet_core_host.cpp and its siblings), which call the very same functions on the CPU.  Compiles as host C++ on its own;
+ * the __host__ __device__ qualifiers exist only under hipcc.
  *
  * A packed matrix B [kp][np] (kp a multiple of 16, np of 32) is kp / 16 x np / 32 fragments, the column tile fastest; a fragment
  * is 64 lanes x 8 bf16, one contiguous KiB: lane (r = lane & 31, h = lane >> 5) element j holds B[16 s + 8 h + j][32 t + r],

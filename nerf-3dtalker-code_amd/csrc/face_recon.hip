@@ -23,6 +23,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "face_recon_core.h"
 #include "n3dt_launch.h"
 
@@ -54,78 +55,9 @@ static FrPackLayout fr_layout() {
     return L;
 }
 
-// eval-mode BatchNorm2d as a scale and a shift, float64: y = (x - mean) / sqrt(var + eps) * gamma + beta
-__device__ __forceinline__ double fr_bn_scale(const float* gamma, const float* var, double eps, int n) {
-    return (double)gamma[n] / sqrt((double)var[n] + eps);
-}
-
-// W [cout, cin, k, k] -> B [K][cout], row k = tap * cin + ci (the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero), each
-// weight times its column's BatchNorm scale in float64, rounded once to fp32, then split
-__global__ __launch_bounds__(256) void face_recon_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
-                                                              const float* __restrict__ var, double eps, int cin, int cout, int taps, int K,
-                                                              int stem, __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)K * cout) return;
-    int k, n;
-    cf_pack_decode(e, cout / 32, &k, &n);
-    float w = 0.0f;
-    if (stem) {
-        if (k < FR_STEM_K) {
-            int ky, kx, c;
-            fr_stem_tap(k, &ky, &kx, &c);
-            w = (float)((double)W[((size_t)n * 3 + c) * 49 + ky * 7 + kx] * fr_bn_scale(gamma, var, eps, n));
-        }
-    } else {
-        const int tap = k / cin, ci = k - tap * cin;
-        w = (float)((double)W[((size_t)n * cin + ci) * taps + tap] * fr_bn_scale(gamma, var, eps, n));
-    }
-    const __bf16 h = (__bf16)w;
-    hi[e] = h;
-    lo[e] = conv_lo(w, h);
-}
-
-__global__ __launch_bounds__(256) void face_recon_bias_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float* __restrict__ mean, const float* __restrict__ var, double eps, int cout,
-                                                              float* __restrict__ dst) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n < cout) dst[n] = (float)((double)beta[n] - (double)mean[n] * fr_bn_scale(gamma, var, eps, n));
-}
-
-__global__ __launch_bounds__(256) void face_recon_copy_kernel(const float* __restrict__ src, size_t n, float* __restrict__ dst) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
-// ---- layouts ---------------------------------------------------------------------------------------------------------------------
-// src [n, C, H, W] -> dst [n, H + 2 pad, W + 2 pad, C]: zero in the halo.  One thread per element.
-__global__ __launch_bounds__(256) void face_recon_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad,
-                                                                 float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * Hp * Wp * C;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        int img, yp, xp;
-        fr_cell(e / C, Hp, Wp, &img, &yp, &xp);
-        float v = 0.0f;
-        if (xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad) v = src[(((size_t)img * C + c) * H + (yp - pad)) * W + (xp - pad)];
-        dst[e] = v;
-    }
-}
-
-// the interior of src [n, H + 2 pad, W + 2 pad, C] -> dst [n, C, H, W]
-__global__ __launch_bounds__(256) void face_recon_to_nchw_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad,
-                                                                 float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * C * H * W;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int x = (int)(e % W);
-        size_t t = e / W;
-        const int y = (int)(t % H);
-        t /= H;
-        const int c = (int)(t % C), img = (int)(t / C);
-        dst[e] = src[(((size_t)img * Hp + (y + pad)) * Wp + (x + pad)) * C + c];
-    }
-}
+// The pack (W [cout, cin, k, k] -> B [K][cout], row k = tap * cin + ci; the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero), the
+// eval-mode BatchNorm2d folded in as a scale and a shift in float64 -- y = (x - mean) / sqrt(var + eps) * gamma + beta -- and the
+// layouts [n,C,H,W] <-> haloed NHWC are conv_net.hip's.
 
 // ---- implicit-GEMM convolution ---------------------------------------------------------------------------------------------------
 struct FrConvArgs {
@@ -138,39 +70,35 @@ struct FrConvArgs {
     int n, Ho, Wo, Hp, Wp, Hq, Wq, cinp, np, k, stride, opad, relu;
 };
 
-// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M cells x 32 NT columns, the column tile fastest.
+// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes CN_TILE_M cells x 32 NT columns, the column tile fastest.
 // A k-step is 16 channels of one tap (C_in % 16 == 0); STEM: 16 consecutive k of the flattened (tap, channel), those from 147 on
 // read as 0 against zero weight rows.  Kernel size, stride, every map size and every halo are run-time arguments; the row index is
 // 64-bit.  Epilogue: conv + bias (+ skip), then the ReLU -- relu(bn3(conv3) + identity), the reference's order.
 template <int NT, bool STEM>
 __global__ __launch_bounds__(256) void face_recon_conv_kernel(FrConvArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long Mq = (long long)a.n * a.Hq * a.Wq;
-    const int ntn = a.np / (32 * NT);
-    const long long tile = (long long)blockIdx.x * 4 + wave;
-    const long long m0 = tile / ntn * SN_TILE_M;
-    if (m0 >= Mq) return;  // no barriers in this kernel: an idle wave may leave
-    const int nt0 = (int)(tile % ntn) * NT;
+    const ConvWaveTile t = conv_wave_tile<NT>(a.np, a.n, a.Hq, a.Wq);
+    if (t.idle()) return;  // no barriers in this kernel: an idle wave may leave
+    const int lane = t.lane, r = t.r, h = t.h, nt0 = t.nt0(NT);
+    const long long Mq = t.M, m0 = t.m0;
     const float* base[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         int img, yq, xq;
-        sn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
-        const int y = sn_clampi(yq - a.opad, 0, a.Ho - 1), x = sn_clampi(xq - a.opad, 0, a.Wo - 1);
-        base[mt] = a.in + fr_field_base(img, y, x, a.stride, a.Hp, a.Wp, a.cinp);
+        cn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
+        const int y = cn_clampi(yq - a.opad, 0, a.Ho - 1), x = cn_clampi(xq - a.opad, 0, a.Wo - 1);
+        base[mt] = a.in + cn_field_base(img, y, x, a.stride, a.Hp, a.Wp, a.cinp);
     }
     conv_f32x16 acc[2][NT];
     CONV_ZERO_ACC(acc, NT);
     float av[2][8];
 
     if (STEM) {
-        for (int s = 0; s < FR_STEM_KP / 16; ++s) {
+        for (int s = 0; s < CN_STEM_KP / 16; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = 16 * s + 8 * h + j;
-                const bool real = k < FR_STEM_K;
-                const size_t off = fr_stem_offset(real ? k : 0, a.Wp);
+                const bool real = k < CN_STEM_K;
+                const size_t off = cn_stem_offset(real ? k : 0, a.Wp);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     const float v = base[mt][off];
@@ -182,7 +110,7 @@ __global__ __launch_bounds__(256) void face_recon_conv_kernel(FrConvArgs a) {
     } else {
         int s = 0;
         for (int tap = 0; tap < a.k * a.k; ++tap) {
-            const size_t toff = sn_tap_offset(tap, a.k, a.Wp, a.cinp) + 8 * h;
+            const size_t toff = cn_tap_offset(tap, a.k, a.Wp, a.cinp) + 8 * h;
             for (int c0 = 0; c0 < a.cinp; c0 += 16, ++s) {
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
@@ -199,8 +127,8 @@ __global__ __launch_bounds__(256) void face_recon_conv_kernel(FrConvArgs a) {
             const long long m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= Mq) continue;
             int img, yq, xq;
-            sn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
-            const bool inside = sn_interior(yq, xq, a.Ho, a.Wo, a.opad);
+            cn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
+            const bool inside = cn_interior(yq, xq, a.Ho, a.Wo, a.opad);
             float* o = a.out + (size_t)m * a.np;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -216,32 +144,7 @@ __global__ __launch_bounds__(256) void face_recon_conv_kernel(FrConvArgs a) {
         }
 }
 
-// ---- pool, average, head ---------------------------------------------------------------------------------------------------------
-// in [n, Hi, Wi, C] -> out [n, Ho, Wo, C], Ho = (Hi - 1) / 2 + 1: the maximum over the taps of the 3 x 3 window that lie inside the
-// map (F.max_pool2d pads with -inf).  One thread per four channels of an output cell.
-__global__ __launch_bounds__(256) void face_recon_pool_kernel(const float* __restrict__ in, int n, int Hi, int Wi, int C, float* __restrict__ out) {
-    const int Ho = fr_pool_out(Hi), Wo = fr_pool_out(Wi), C4 = C / 4;
-    const size_t total = (size_t)n * Ho * Wo * C4;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C4) * 4;
-        int img, yo, xo;
-        fr_cell(e / C4, Ho, Wo, &img, &yo, &xo);
-        int ya, yb, xa, xb;
-        fr_pool_range(yo, Hi, &ya, &yb);
-        fr_pool_range(xo, Wi, &xa, &xb);
-        float4 v = *reinterpret_cast<const float4*>(in + (((size_t)img * Hi + ya) * Wi + xa) * C + c);
-        for (int y = ya; y < yb; ++y)
-            for (int x = xa; x < xb; ++x) {
-                const float4 t = *reinterpret_cast<const float4*>(in + (((size_t)img * Hi + y) * Wi + x) * C + c);
-                v.x = fmaxf(v.x, t.x);
-                v.y = fmaxf(v.y, t.y);
-                v.z = fmaxf(v.z, t.z);
-                v.w = fmaxf(v.w, t.w);
-            }
-        *reinterpret_cast<float4*>(out + e * 4) = v;
-    }
-}
-
+// ---- average, head (the 3 x 3 / 2 max pool is conv_net.hip's) --------------------------------------------------------------------
 // in [n, H, W, C] -> out [n, C]: the mean over the H W cells, summed in float64 in row-major order, rounded once
 __global__ __launch_bounds__(256) void face_recon_avg_kernel(const float* __restrict__ in, int n, int HW, int C, float* __restrict__ out) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -383,16 +286,15 @@ extern "C" void n3dt_launch_face_recon_pack(const N3dtFaceReconParams* p, void* 
         const FrGeom g = fr_geom(j, FR_MIN_HW, FR_MIN_HW);
         __bf16* hi = (__bf16*)(base + L.w[j]);
         const size_t n = L.elems[j];
-        face_recon_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p->weight[j], p->bn_weight[j], p->bn_var[j], p->bn_eps[j], g.cin, g.cout,
-                                                                          g.k * g.k, g.K, g.role == FR_STEM, hi, hi + n);
-        face_recon_bias_kernel<<<(g.cout + 255) / 256, 256, 0, st>>>(p->bn_weight[j], p->bn_bias[j], p->bn_mean[j], p->bn_var[j], p->bn_eps[j], g.cout,
-                                                                   (float*)(base + L.bias[j]));
+        conv_net_pack(p->weight[j], p->bn_weight[j], p->bn_var[j], p->bn_eps[j], g.cin, g.cin, g.cin, g.cout, g.cout, g.k * g.k, g.K, g.role == FR_STEM,
+                      hi, hi + n, st);
+        conv_net_shift_bn(p->bn_weight[j], p->bn_bias[j], p->bn_mean[j], p->bn_var[j], p->bn_eps[j], g.cout, (float*)(base + L.bias[j]), st);
     }
     int col = 0;
     for (int i = 0; i < FR_HEADS; ++i) {
         const size_t n = (size_t)FR_HEAD_COLS[i] * FR_FEAT;
-        face_recon_copy_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p->head_weight[i], n, (float*)(base + L.head_w) + (size_t)col * FR_FEAT);
-        face_recon_copy_kernel<<<1, 256, 0, st>>>(p->head_bias[i], (size_t)FR_HEAD_COLS[i], (float*)(base + L.head_b) + col);
+        conv_net_copy(p->head_weight[i], n, (float*)(base + L.head_w) + (size_t)col * FR_FEAT, st);
+        conv_net_copy(p->head_bias[i], (size_t)FR_HEAD_COLS[i], (float*)(base + L.head_b) + col, st);
         col += FR_HEAD_COLS[i];
     }
 }
@@ -412,8 +314,8 @@ static void fr_conv_launch(int j, int n, int Hi, int Wi, const void* packed, con
     a.Ho = g.Ho; a.Wo = g.Wo; a.Hp = g.Hp; a.Wp = g.Wp; a.Hq = g.Hq; a.Wq = g.Wq;
     a.cinp = g.cinp; a.np = g.cout; a.k = g.k; a.stride = g.stride; a.opad = g.opad; a.relu = g.relu;
     const size_t Mq = (size_t)n * g.Hq * g.Wq;
-    const size_t mtiles = (Mq + SN_TILE_M - 1) / SN_TILE_M;
-    const int nt = fr_wave_ntiles(&g, n);
+    const size_t mtiles = (Mq + CN_TILE_M - 1) / CN_TILE_M;
+    const int nt = cn_wave_ntiles((long long)Mq, g.cout);
     const size_t tiles = mtiles * (g.cout / (32 * nt));
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     if (g.role == FR_STEM) {
@@ -423,11 +325,6 @@ static void fr_conv_launch(int j, int n, int Hi, int Wi, const void* packed, con
         if (nt == 1) face_recon_conv_kernel<1, false><<<grid, 256, 0, st>>>(a);
         else face_recon_conv_kernel<2, false><<<grid, 256, 0, st>>>(a);
     }
-}
-
-static void fr_pool_launch(int n, int Hi, int Wi, const float* in, float* out, hipStream_t st) {
-    const size_t work = (size_t)n * fr_pool_out(Hi) * fr_pool_out(Wi) * (64 / 4);
-    face_recon_pool_kernel<<<conv_grid(work), 256, 0, st>>>(in, n, Hi, Wi, 64, out);
 }
 
 static void fr_avg_launch(int n, int Hi, int Wi, const float* in, float* out, hipStream_t st) {
@@ -447,12 +344,12 @@ extern "C" void n3dt_launch_face_recon_fwd(int n, int H, int W, const void* pack
     char* ws = (char*)workspace;
     float* region[FR_REGIONS];
     for (int r = 0; r < FR_REGIONS; ++r) region[r] = (float*)(ws + w.region[r]);
-    face_recon_to_nhwc_kernel<<<conv_grid((size_t)n * (H + 6) * (W + 6) * 3), 256, 0, st>>>(x, n, 3, H, W, 3, region[1]);
+    conv_net_to_nhwc(x, n, 3, H, W, 3, 3, region[1], 3, st);
     FrStep steps[FR_STEPS];
     fr_chain(H, W, steps);
     for (int s = 0; s < FR_STEPS; ++s) {
         const FrStep t = steps[s];
-        if (t.block == FR_POOL_BLOCK) fr_pool_launch(n, t.Hi, t.Wi, region[t.in], region[t.out], st);
+        if (t.block == FR_POOL_BLOCK) conv_net_max_pool(region[t.in], n, t.Hi, t.Wi, 64, region[t.out], st);
         else if (t.block == FR_AVG_BLOCK) fr_avg_launch(n, t.Hi, t.Wi, region[t.in], region[t.out], st);
         else fr_conv_launch(t.block, n, t.Hi, t.Wi, packed, region[t.in], t.skip < 0 ? nullptr : region[t.skip], region[t.out], st);
     }
@@ -483,7 +380,7 @@ static FrBlockShape fr_block_shape(int block, int Hi, int Wi) {
         b.in_elems = fr_in_elems(&g, 1);
         b.out_elems = fr_out_elems(&g, 1);
     } else if (block == FR_POOL_BLOCK) {
-        b.cin = b.cout = 64; b.Ho = fr_pool_out(Hi); b.Wo = fr_pool_out(Wi);
+        b.cin = b.cout = 64; b.Ho = cn_pool_out(Hi); b.Wo = cn_pool_out(Wi);
         b.in_elems = (size_t)Hi * Wi * 64;
         b.out_elems = (size_t)b.Ho * b.Wo * 64;
     } else if (block == FR_AVG_BLOCK) {
@@ -501,30 +398,30 @@ static FrBlockShape fr_block_shape(int block, int Hi, int Wi) {
 // three regions: the input map, the output map, the skip map (as large as the output)
 extern "C" size_t n3dt_face_recon_block_ws_bytes(int block, int n, int Hi, int Wi) {
     const FrBlockShape b = fr_block_shape(block, Hi, Wi);
-    return fr_rup256((size_t)n * b.in_elems * sizeof(float)) + 2 * fr_rup256((size_t)n * b.out_elems * sizeof(float));
+    return cn_rup256((size_t)n * b.in_elems * sizeof(float)) + 2 * cn_rup256((size_t)n * b.out_elems * sizeof(float));
 }
 
 extern "C" void n3dt_launch_face_recon_block(int block, int n, int Hi, int Wi, const void* packed, const float* in, const float* skip, float* out,
                                              void* workspace, hipStream_t st) {
     const FrBlockShape b = fr_block_shape(block, Hi, Wi);
-    const size_t out_bytes = fr_rup256((size_t)n * b.out_elems * sizeof(float));
+    const size_t out_bytes = cn_rup256((size_t)n * b.out_elems * sizeof(float));
     float* map0 = (float*)workspace;
-    float* map1 = (float*)((char*)workspace + fr_rup256((size_t)n * b.in_elems * sizeof(float)));
+    float* map1 = (float*)((char*)workspace + cn_rup256((size_t)n * b.in_elems * sizeof(float)));
     float* map2 = (float*)((char*)map1 + out_bytes);
     if (block == FR_HEAD_BLOCK) {
         fr_head_launch(n, packed, in, out, st);  // [n, 2048, 1, 1] is [n, 2048]
         return;
     }
-    face_recon_to_nhwc_kernel<<<conv_grid((size_t)n * b.in_elems), 256, 0, st>>>(in, n, b.cin, Hi, Wi, b.ipad, map0);
+    conv_net_to_nhwc(in, n, b.cin, Hi, Wi, b.ipad, b.cin, map0, b.cin, st);
     if (block == FR_AVG_BLOCK) {
         fr_avg_launch(n, Hi, Wi, map0, out, st);
         return;
     }
     if (block == FR_POOL_BLOCK) {
-        fr_pool_launch(n, Hi, Wi, map0, map1, st);
+        conv_net_max_pool(map0, n, Hi, Wi, 64, map1, st);
     } else {
-        if (skip) face_recon_to_nhwc_kernel<<<conv_grid((size_t)n * b.out_elems), 256, 0, st>>>(skip, n, b.cout, b.Ho, b.Wo, 0, map2);
+        if (skip) conv_net_to_nhwc(skip, n, b.cout, b.Ho, b.Wo, 0, b.cout, map2, b.cout, st);
         fr_conv_launch(block, n, Hi, Wi, packed, map0, skip ? map2 : nullptr, map1, st);
     }
-    face_recon_to_nchw_kernel<<<conv_grid((size_t)n * b.cout * b.Ho * b.Wo), 256, 0, st>>>(map1, n, b.cout, b.Ho, b.Wo, b.opad, out);
+    conv_net_to_nchw(map1, b.cout, n, b.cout, b.Ho, b.Wo, b.opad, out, st);
 }

@@ -5,8 +5,8 @@
  *
  * Included by csrc/face_recon.hip, whose kernels take their sizes and addresses from the functions below, and by
  * tests/face_recon_core_host.cpp, which walks the same functions over the kernels' grids on the CPU under the address and
- * undefined-behaviour sanitizers.  The rows of the implicit GEMM and the halo test are syncnet_core.h's; the fragment arithmetic
- * is conv_frag.h's.  Compiles as host C++ on its own.
+ * undefined-behaviour sanitizers.  The rows of the implicit GEMM, the halo test, the receptive field's base, the stem's gather, the pool's window and the
+ * wave-tile rule are conv_net_core.h's; the fragment arithmetic is conv_frag.h's.  Compiles as host C++ on its own.
  *
  * Blocks.  56 of them: 0..52 the convolutions in state-dict order (conv1; then per bottleneck conv1, conv2, conv3 and, in the
  * first bottleneck of a layer, downsample.0), 53 the 3 x 3 / 2 max pool, 54 the global average, 55 the 257-column head.
@@ -22,7 +22,7 @@
 
 #include <math.h>
 
-#include "syncnet_core.h"
+#include "conv_net_core.h"
 
 #define FR_CONVS 53
 #define FR_BOTTLENECKS 16
@@ -33,9 +33,6 @@
 #define FR_FEAT 2048
 #define FR_COEFFS 257
 #define FR_HEADS 7
-#define FR_STEM_K 147   /* 7 x 7 x 3 */
-#define FR_STEM_KP 160
-#define FR_STEM_ROW 21  /* 7 x 3: the (kx, c) of one ky, contiguous in NHWC */
 #define FR_MIN_HW 32
 #define FR_MAX_IMAGES 1024
 #define FR_WS_BUDGET ((size_t)4 << 30) /* bytes of workspace one call may ask for: caps n */
@@ -92,8 +89,6 @@ static inline int fr_bottleneck_first(int b) {
 }
 static inline int fr_bottleneck_down(int b) { return b == 0 || b == 3 || b == 7 || b == 13; }
 
-SN_HD int fr_pool_out(int n) { return (n + 2 - 3) / 2 + 1; }
-
 /* one GEMM: input [n, Hp, Wp, cinp] with halo pad (its own padding), output [n, Hq, Wq, cout] with halo opad; K = the packed
  * matrix's rows: k k cin, for the stem 160 */
 typedef struct FrGeom {
@@ -105,8 +100,8 @@ static inline FrGeom fr_geom(int j, int Hi, int Wi) {
     FrGeom g;
     g.Hi = Hi;
     g.Wi = Wi;
-    g.Ho = sn_conv_out(Hi, t.k, t.stride, t.pad);
-    g.Wo = sn_conv_out(Wi, t.k, t.stride, t.pad);
+    g.Ho = cn_conv_out(Hi, t.k, t.stride, t.pad);
+    g.Wo = cn_conv_out(Wi, t.k, t.stride, t.pad);
     g.pad = t.pad;
     g.opad = t.opad;
     g.Hp = Hi + 2 * t.pad;
@@ -118,7 +113,7 @@ static inline FrGeom fr_geom(int j, int Hi, int Wi) {
     g.cout = t.cout;
     g.k = t.k;
     g.stride = t.stride;
-    g.K = t.role == FR_STEM ? FR_STEM_KP : t.k * t.k * t.cin;
+    g.K = t.role == FR_STEM ? CN_STEM_KP : t.k * t.k * t.cin;
     g.relu = t.relu;
     g.role = t.role;
     return g;
@@ -127,14 +122,7 @@ static inline FrGeom fr_geom(int j, int Hi, int Wi) {
 static inline size_t fr_in_elems(const FrGeom* g, int n) { return (size_t)n * g->Hp * g->Wp * g->cinp; }
 static inline size_t fr_out_elems(const FrGeom* g, int n) { return (size_t)n * g->Hq * g->Wq * g->cout; }
 
-/* 32-column tiles per wave: two, unless that would leave fewer than 1024 waves (DESIGN 3.18's rule; every C_out here is a
- * multiple of 64) */
-static inline int fr_wave_ntiles(const FrGeom* g, int n) {
-    const size_t mtiles = ((size_t)n * g->Hq * g->Wq + SN_TILE_M - 1) / SN_TILE_M;
-    return mtiles * (size_t)(g->cout / 64) < 1024 ? 1 : 2;
-}
-
-SN_HD int fr_hw_ok(int H, int W) { return H >= FR_MIN_HW && W >= FR_MIN_HW && H <= SN_MAX_FRAME_HW && W <= SN_MAX_FRAME_HW; }
+CN_HD int fr_hw_ok(int H, int W) { return H >= FR_MIN_HW && W >= FR_MIN_HW && H <= CN_MAX_FRAME_HW && W <= CN_MAX_FRAME_HW; }
 
 /* ---- the chain -------------------------------------------------------------------------------------------------------------------
  * what the forward launches, in its order: 53 convolutions, the pool and the average (the head reads the averages and writes the
@@ -153,7 +141,7 @@ static inline void fr_chain(int H, int W, FrStep steps[FR_STEPS]) {
     steps[s++] = s0;
     const FrStep sp = {FR_POOL_BLOCK, stem.Ho, stem.Wo, 2, -1, 0};
     steps[s++] = sp;
-    int h = fr_pool_out(stem.Ho), w = fr_pool_out(stem.Wo), cur = 0;
+    int h = cn_pool_out(stem.Ho), w = cn_pool_out(stem.Wo), cur = 0;
     for (int b = 0; b < FR_BOTTLENECKS; ++b) {
         const int j = fr_bottleneck_first(b), down = fr_bottleneck_down(b);
         const FrGeom g2 = fr_geom(j + 1, h, w);
@@ -176,7 +164,7 @@ static inline void fr_chain(int H, int W, FrStep steps[FR_STEPS]) {
 
 /* the pool's output map [n, Ho, Wo, 64], no halo */
 static inline size_t fr_step_out_elems(const FrStep* st) {
-    if (st->block == FR_POOL_BLOCK) return (size_t)fr_pool_out(st->Hi) * fr_pool_out(st->Wi) * 64;
+    if (st->block == FR_POOL_BLOCK) return (size_t)cn_pool_out(st->Hi) * cn_pool_out(st->Wi) * 64;
     if (st->block == FR_AVG_BLOCK) return FR_FEAT;
     const FrGeom g = fr_geom(st->block, st->Hi, st->Wi);
     return fr_out_elems(&g, 1);
@@ -185,8 +173,6 @@ static inline size_t fr_step_out_elems(const FrStep* st) {
 typedef struct FrWorkspace {
     size_t region[FR_REGIONS], bytes[FR_REGIONS], total;
 } FrWorkspace;
-
-static inline size_t fr_rup256(size_t x) { return (x + 255) / 256 * 256; }
 
 static inline FrWorkspace fr_workspace(int n, int H, int W) {
     FrStep steps[FR_STEPS];
@@ -201,7 +187,7 @@ static inline FrWorkspace fr_workspace(int n, int H, int W) {
     size_t off = 0;
     for (int r = 0; r < FR_REGIONS; ++r) {
         w.region[r] = off;
-        w.bytes[r] = fr_rup256((size_t)n * elems[r] * sizeof(float));
+        w.bytes[r] = cn_rup256((size_t)n * elems[r] * sizeof(float));
         off += w.bytes[r];
     }
     w.total = off;
@@ -217,44 +203,9 @@ static inline int fr_max_images(int H, int W) {
     return (int)n;
 }
 
-/* ---- addresses -------------------------------------------------------------------------------------------------------------------
- * first element of the receptive field of output pixel (img, y, x) in the padded NHWC input [n, Hp, Wp, cinp] */
-SN_HD size_t fr_field_base(int img, int y, int x, int stride, int Hp, int Wp, int cinp) {
-    return (((size_t)img * Hp + (size_t)y * stride) * Wp + (size_t)x * stride) * cinp;
-}
-
-/* the stem: offset of flattened k (< 147) from the field's base in [n, Hp, Wp, 3] */
-SN_HD size_t fr_stem_offset(int k, int Wp) {
-    const int ky = k / FR_STEM_ROW;
-    return (size_t)ky * Wp * 3 + (size_t)(k - ky * FR_STEM_ROW);
-}
-
-/* the stem's packed row k -> (ky, kx, c) */
-SN_HD void fr_stem_tap(int k, int* ky, int* kx, int* c) {
-    *ky = k / FR_STEM_ROW;
-    const int r = k - *ky * FR_STEM_ROW;
-    *kx = r / 3;
-    *c = r - *kx * 3;
-}
-
-/* cell e of a map [n, Hq, Wq] -> (img, yq, xq) */
-SN_HD void fr_cell(size_t e, int Hq, int Wq, int* img, int* yq, int* xq) {
-    *xq = (int)(e % (size_t)Wq);
-    const size_t t = e / (size_t)Wq;
-    *yq = (int)(t % (size_t)Hq);
-    *img = (int)(t / (size_t)Hq);
-}
-
-/* the 3 x 3 / 2 max pool with padding 1: output pixel o takes input pixels [*a, *b) of `in` along one axis; never empty */
-SN_HD void fr_pool_range(int o, int in, int* a, int* b) {
-    const int lo = 2 * o - 1, hi = 2 * o + 2;
-    *a = lo < 0 ? 0 : lo;
-    *b = hi > in ? in : hi;
-}
-
 /* ---- the alignment prologue, float64 ---------------------------------------------------------------------------------------------
  * PIL's bicubic filter, a = -0.5 */
-SN_HD double fr_cubic(double x) {
+CN_HD double fr_cubic(double x) {
     const double a = -0.5;
     if (x < 0.0) x = -x;
     if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
@@ -264,7 +215,7 @@ SN_HD double fr_cubic(double x) {
 
 /* PIL's resample along one axis of `in` source samples to `out`: output index o takes source samples [*lo, *hi) with weights
  * fr_cubic((x - *center + 0.5) / *fs), normalised by their sum */
-SN_HD void fr_taps(int o, int in, int out, int* lo, int* hi, double* center, double* fs) {
+CN_HD void fr_taps(int o, int in, int out, int* lo, int* hi, double* center, double* fs) {
     const double scale = (double)in / (double)out;
     const double f = scale < 1.0 ? 1.0 : scale;
     const double support = 2.0 * f, c = ((double)o + 0.5) * scale;
@@ -278,7 +229,7 @@ SN_HD void fr_taps(int o, int in, int out, int* lo, int* hi, double* center, dou
 }
 
 /* truncation toward zero as astype(int32) does it, for a finite value inside the int range (the status test comes first) */
-SN_HD int fr_trunc(double v) {
+CN_HD int fr_trunc(double v) {
     if (!(v > -2.0e9)) v = -2.0e9;
     if (v > 2.0e9) v = 2.0e9;
     return (int)v;
@@ -286,7 +237,7 @@ SN_HD int fr_trunc(double v) {
 
 /* the similarity of one frame: lm5 [5][2] image landmarks with y already flipped, pinv [4][5] the pseudo-inverse of
  * [lm3d_std, 1] -> trans (w0, h0, s, t0, t1), geom (w, h, left, up); returns the status (0: fine) */
-SN_HD int fr_similarity(const double lm5[5][2], const double* pinv, int W0, int H0, double trans[5], int geom[4]) {
+CN_HD int fr_similarity(const double lm5[5][2], const double* pinv, int W0, int H0, double trans[5], int geom[4]) {
     double k[2][4];
     int finite = 1;
     for (int a = 0; a < 2; ++a)

@@ -25,6 +25,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "fan_core.h"
 #include "n3dt_launch.h"
 
@@ -68,39 +69,9 @@ static FanLayout fan_layout(int modules, int N) {
     return L;
 }
 
-// eval-mode BatchNorm2d's scale, float64
-__device__ __forceinline__ double fan_bn_scale(const float* gamma, const float* var, int n) {
-    return (double)gamma[n] / sqrt((double)var[n] + FAN_BN_EPS);
-}
-
-// W [cout, wc, k, k] (wc >= cin channels: a CoordConv's weight also holds the coordinate channels) -> B [K][np], row
-// k = tap * cinp + ci (the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero); rows of padded channels and columns from cout on are
-// zero; each weight times its column's folded BatchNorm scale (post) in float64, rounded once to fp32, then split
-__global__ __launch_bounds__(256) void fan_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma, const float* __restrict__ var,
-                                                       int post, int wc, int cin, int cinp, int cout, int np, int taps, int K, int stem,
-                                                       __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)K * np) return;
-    int k, n;
-    cf_pack_decode(e, np / 32, &k, &n);
-    float w = 0.0f;
-    if (n < cout) {
-        const double s = post ? fan_bn_scale(gamma, var, n) : 1.0;
-        if (stem) {
-            if (k < FAN_STEM_K) {
-                int ky, kx, c;
-                fan_stem_tap(k, &ky, &kx, &c);
-                w = (float)((double)W[((size_t)n * wc + c) * 49 + ky * 7 + kx] * s);
-            }
-        } else {
-            const int tap = k / cinp, ci = k - tap * cinp;
-            if (ci < cin) w = (float)((double)W[((size_t)n * wc + ci) * taps + tap] * s);
-        }
-    }
-    const __bf16 h = (__bf16)w;
-    hi[e] = h;
-    lo[e] = conv_lo(w, h);
-}
+// The pack is conv_net.hip's: W [cout, wc, k, k] (wc >= cin channels: a CoordConv's weight also holds the coordinate channels) ->
+// B [K][np], row k = tap * cinp + ci (the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero); rows of padded channels and columns
+// from cout on are zero; each weight times its column's folded BatchNorm scale (post) in float64, rounded once to fp32, then split.
 
 // the bias vector [np] -- kind LAST: s (b - mean) + beta; STEM and COORD: 0 (their bias lies in the coordinate map); else the
 // convolution's own bias or 0 -- and the pre-activation's g = gamma / sqrt(var + eps), b = beta - mean g, [2][cinp], 0 past cin
@@ -112,14 +83,14 @@ __global__ __launch_bounds__(256) void fan_vec_kernel(const float* __restrict__ 
         double v = 0.0;
         if (i < cout && bias && kind != FAN_STEM && kind != FAN_COORD) {
             v = (double)bias[i];
-            if (kind == FAN_LAST) v = (v - (double)mean[i]) * fan_bn_scale(gamma, var, i) + (double)beta[i];
+            if (kind == FAN_LAST) v = (v - (double)mean[i]) * conv_bn_scale(gamma, var, FAN_BN_EPS, i) + (double)beta[i];
         }
         dbias[i] = (float)v;
     }
     if (i < cinp) {
         double g = 0.0, b = 0.0;
         if (pre && i < cin) {
-            g = fan_bn_scale(gamma, var, i);
+            g = conv_bn_scale(gamma, var, FAN_BN_EPS, i);
             b = (double)beta[i] - (double)mean[i] * g;
         }
         dpre[i] = (float)g;
@@ -143,7 +114,7 @@ __global__ __launch_bounds__(256) void fan_stem_map_kernel(const float* __restri
                 if (fan_inside(iy, ix, FAN_IMG, FAN_IMG))
                     s += (double)W[((size_t)co * 6 + 3 + c) * 49 + ky * 7 + kx] * (double)coords[((size_t)c * FAN_IMG + iy) * FAN_IMG + ix];
             }
-    map[e] = (float)((s + (double)bias[co] - (double)mean[co]) * fan_bn_scale(gamma, var, co) + (double)beta[co]);
+    map[e] = (float)((s + (double)bias[co] - (double)mean[co]) * conv_bn_scale(gamma, var, FAN_BN_EPS, co) + (double)beta[co]);
 }
 
 // the hourglass CoordConv's coordinate channels: map1 [4096, 256] = W[co][256..258] . (xx, yy, rr) + bias, and (gated) map2 =
@@ -159,27 +130,7 @@ __global__ __launch_bounds__(256) void fan_coord_map_kernel(const float* __restr
     if (map2) map2[e] = (float)((double)w[3] * xx + (double)w[4] * yy);
 }
 
-// ---- layouts -----------------------------------------------------------------------------------------------------------------------
-// src [n, C, H, W] -> dst [n, H, W, cs]: channels C .. cs - 1 zero
-__global__ __launch_bounds__(256) void fan_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int cs, float* __restrict__ dst) {
-    const size_t total = (size_t)n * H * W * cs;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % cs);
-        const size_t cell = e / cs;
-        const size_t hw = (size_t)H * W, img = cell / hw, rem = cell - img * hw;
-        dst[e] = c < C ? src[(img * C + c) * hw + rem] : 0.0f;
-    }
-}
-
-// channels 0 .. C - 1 of src [n, H, W, cs] -> dst [n, C, H, W]
-__global__ __launch_bounds__(256) void fan_to_nchw_kernel(const float* __restrict__ src, int n, int C, int H, int W, int cs, float* __restrict__ dst) {
-    const size_t total = (size_t)n * C * H * W;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const size_t hw = (size_t)H * W, rem = e % hw, t = e / hw;
-        const size_t c = t % C, img = t / C;
-        dst[e] = src[(img * hw + rem) * cs + c];
-    }
-}
+// layouts: conv_net.hip's, with no halo and the channels padded to the map's cs
 
 // ---- implicit-GEMM convolution -----------------------------------------------------------------------------------------------------
 struct FanConvArgs {
@@ -198,26 +149,22 @@ struct FanConvArgs {
     int n, Hi, Wi, Ho, Wo, cin, in_cs, np, cstore, out_cs, skip_cs, raw_cs, k, stride, pad, relu;
 };
 
-// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M pixels x 32 NT columns, the column tile fastest.
+// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes CN_TILE_M pixels x 32 NT columns, the column tile fastest.
 // A k-step is 16 channels of one tap (cin % 16 == 0); STEM: 16 consecutive k of the flattened (tap, channel), those from 147 on
 // zero against zero weight rows.  Kernel size, stride and every map size are run-time arguments; the row index is 64-bit.  Columns
 // from cstore on are not stored (a heat map keeps N + 1 padded to 16 of its 32-padded columns; the padding columns are 0).
 template <int NT, bool STEM>
 __global__ __launch_bounds__(256) void fan_conv_kernel(FanConvArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long M = (long long)a.n * a.Ho * a.Wo;
-    const int ntn = a.np / (32 * NT);
-    const long long tile = (long long)blockIdx.x * 4 + wave;
-    const long long m0 = tile / ntn * SN_TILE_M;
-    if (m0 >= M) return;  // no barriers in this kernel: an idle wave may leave
-    const int nt0 = (int)(tile % ntn) * NT;
+    const ConvWaveTile t = conv_wave_tile<NT>(a.np, a.n, a.Ho, a.Wo);
+    if (t.idle()) return;  // no barriers in this kernel: an idle wave may leave
+    const int lane = t.lane, r = t.r, h = t.h, nt0 = t.nt0(NT);
+    const long long M = t.M, m0 = t.m0;
     const float* base[2];
     int y0[2], x0[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         int img, y, x;
-        sn_row_cell(m0 + mt * 32 + r, M, a.Ho, a.Wo, &img, &y, &x);  // rows past M compute the last pixel again and are never stored
+        cn_row_cell(m0 + mt * 32 + r, M, a.Ho, a.Wo, &img, &y, &x);  // rows past M compute the last pixel again and are never stored
         base[mt] = a.in + (size_t)img * a.Hi * a.Wi * a.in_cs;
         y0[mt] = fan_tap_pixel(y, 0, a.stride, a.pad);
         x0[mt] = fan_tap_pixel(x, 0, a.stride, a.pad);
@@ -227,17 +174,17 @@ __global__ __launch_bounds__(256) void fan_conv_kernel(FanConvArgs a) {
     float av[2][8];
 
     if (STEM) {
-        for (int s = 0; s < FAN_STEM_KP / 16; ++s) {
+        for (int s = 0; s < CN_STEM_KP / 16; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = 16 * s + 8 * h + j;
                 int ky, kx, c;
-                fan_stem_tap(k < FAN_STEM_K ? k : 0, &ky, &kx, &c);
+                cn_stem_tap(k < CN_STEM_K ? k : 0, &ky, &kx, &c);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     const int iy = y0[mt] + ky, ix = x0[mt] + kx;
                     float v = 0.0f;
-                    if (k < FAN_STEM_K && fan_inside(iy, ix, a.Hi, a.Wi)) v = base[mt][((size_t)iy * a.Wi + ix) * 3 + c];
+                    if (k < CN_STEM_K && fan_inside(iy, ix, a.Hi, a.Wi)) v = base[mt][((size_t)iy * a.Wi + ix) * 3 + c];
                     av[mt][j] = v;
                 }
             }
@@ -362,7 +309,7 @@ __global__ __launch_bounds__(256) void fan_gate_kernel(const float* __restrict__
 
 // ---- crops -------------------------------------------------------------------------------------------------------------------------
 // One thread per output pixel (frame, Y, X): the box's rows y1 .. y2 - 1 and columns x1 .. x2 - 1 resampled to 256 x 256 bilinearly
-// with half-pixel centres (syncnet_core.h's sn_bilinear), float64, rounded once; RGB in, BGR out.  A bad box gives zeros.
+// with half-pixel centres (conv_net_core.h's cn_bilinear), float64, rounded once; RGB in, BGR out.  A bad box gives zeros.
 __global__ __launch_bounds__(256) void fan_crop_kernel(int n, int H, int W, const float* __restrict__ frames, const int* __restrict__ boxes,
                                                        float* __restrict__ out) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -377,8 +324,8 @@ __global__ __launch_bounds__(256) void fan_crop_kernel(int n, int H, int W, cons
     }
     int ya, yb, xa, xb;
     double wy, wx;
-    sn_bilinear(Y, box[1] - box[0], FAN_IMG, &ya, &yb, &wy);
-    sn_bilinear(X, box[3] - box[2], FAN_IMG, &xa, &xb, &wx);
+    cn_bilinear(Y, box[1] - box[0], FAN_IMG, &ya, &yb, &wy);
+    cn_bilinear(X, box[3] - box[2], FAN_IMG, &xa, &xb, &wx);
     ya += box[0]; yb += box[0]; xa += box[2]; xb += box[2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -516,8 +463,8 @@ extern "C" void n3dt_launch_fan_pack(const N3dtFanParams* q, void* packed, hipSt
         const int wc = c.kind == FAN_STEM ? 6 : c.kind == FAN_COORD ? (j < FAN_FRONT_CONVS + FAN_STACK_CONVS ? 259 : 261) : c.cin;
         __bf16* hi = (__bf16*)(base + L.w[j]);
         const size_t n = L.elems[j];
-        fan_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q->weight[j], q->bn_weight[j], q->bn_var[j], c.post, wc, c.cin, cinp, c.cout, np,
-                                                                   c.k * c.k, K, c.kind == FAN_STEM, hi, hi + n);
+        conv_net_pack(q->weight[j], c.post ? q->bn_weight[j] : nullptr, q->bn_var[j], FAN_BN_EPS, wc, c.cin, cinp, c.cout, np, c.k * c.k, K,
+                      c.kind == FAN_STEM, hi, hi + n, st);
         const int most = np > cinp ? np : cinp;
         fan_vec_kernel<<<(most + 255) / 256, 256, 0, st>>>(q->bias[j], q->bn_weight[j], q->bn_bias[j], q->bn_mean[j], q->bn_var[j], c.kind, c.pre, c.cin,
                                                          cinp, c.cout, np, (float*)(base + L.bias[j]), (float*)(base + L.pre[j]));
@@ -568,16 +515,16 @@ static void fan_conv_launch(const FanRun* r, const FanLayout* L, const FanStep* 
     a.n = r->n;
     a.Hi = t->H; a.Wi = t->W;
     a.pad = c.k / 2;
-    a.Ho = sn_conv_out(t->H, c.k, c.stride, a.pad);
-    a.Wo = sn_conv_out(t->W, c.k, c.stride, a.pad);
+    a.Ho = cn_conv_out(t->H, c.k, c.stride, a.pad);
+    a.Wo = cn_conv_out(t->W, c.k, c.stride, a.pad);
     a.cin = fan_cinp(&c); a.in_cs = t->in_cs; a.np = fan_np(&c);
-    a.cstore = c.kind == FAN_L ? sn_round16(c.cout) : c.cout;
+    a.cstore = c.kind == FAN_L ? cn_round16(c.cout) : c.cout;
     a.out_cs = t->out_cs; a.skip_cs = t->skip_cs; a.raw_cs = t->raw_cs;
     a.k = c.k; a.stride = c.stride;
     a.relu = c.kind == FAN_STEM || c.kind == FAN_LAST || (c.kind == FAN_L && r->end_relu);
     const long long M = (long long)r->n * a.Ho * a.Wo;
-    const int nt = fan_wave_ntiles(M, a.np);
-    const long long tiles = (M + SN_TILE_M - 1) / SN_TILE_M * (a.np / (32 * nt));
+    const int nt = cn_wave_ntiles(M, a.np);
+    const long long tiles = (M + CN_TILE_M - 1) / CN_TILE_M * (a.np / (32 * nt));
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     if (c.kind == FAN_STEM) {
         if (nt == 1) fan_conv_kernel<1, true><<<grid, 256, 0, st>>>(a);
@@ -607,7 +554,7 @@ extern "C" void n3dt_launch_fan_fwd(int modules, int N, int end_relu, int n, con
     const FanLayout L = fan_layout(modules, N);
     const int slots = modules > 1 ? modules - 1 : 1, hcs = fan_heat_cs(N);
     FanRun r = {modules, N, end_relu, n, (const char*)packed, (float*)workspace, gates, slots, 0};
-    fan_to_nhwc_kernel<<<conv_grid((size_t)n * FAN_IMG * FAN_IMG * 3), 256, 0, st>>>(x, n, 3, FAN_IMG, FAN_IMG, 3, fan_at(&r, p->image));
+    conv_net_to_nhwc(x, n, 3, FAN_IMG, FAN_IMG, 0, 3, fan_at(&r, p->image), 3, st);
     for (int s = 0; s < p->steps; ++s) {
         const FanStep* t = &p->step[s];
         fan_step_launch(&r, &L, t, st);
@@ -616,8 +563,7 @@ extern "C" void n3dt_launch_fan_fwd(int modules, int N, int end_relu, int n, con
             const float* hm = fan_at(&r, p->heat[stack]);
             if (compute_gates && stack < modules - 1)
                 fan_gate_kernel<<<(unsigned)(((size_t)n * FAN_CELLS + 255) / 256), 256, 0, st>>>(hm, n, hcs, N, slots, stack, gates);
-            fan_to_nchw_kernel<<<conv_grid((size_t)n * (N + 1) * FAN_CELLS), 256, 0, st>>>(hm, n, N + 1, FAN_HEAT, FAN_HEAT, hcs,
-                                                                                         heat + (size_t)stack * n * (N + 1) * FAN_CELLS);
+            conv_net_to_nchw(hm, hcs, n, N + 1, FAN_HEAT, FAN_HEAT, 0, heat + (size_t)stack * n * (N + 1) * FAN_CELLS, st);
         }
     }
 }
@@ -632,13 +578,13 @@ extern "C" void n3dt_launch_fan_block(int block, int modules, int N, int end_rel
     const int stack = block < FAN_FRONT_BLOCKS ? 0 : (block - FAN_FRONT_BLOCKS) / FAN_STACK_BLOCKS;
     // the block's gates are handed over as [n, 4096]: one slot, the one its stack takes
     FanRun r = {modules, N, end_relu, n, (const char*)packed, (float*)workspace, gates, 1, stack > 0 ? stack - 1 : 0};
-    fan_to_nhwc_kernel<<<conv_grid((size_t)n * H * W * m.in_cs), 256, 0, st>>>(in, n, k.cin, H, W, m.in_cs, fan_at(&r, m.in));
-    if (skip) fan_to_nhwc_kernel<<<conv_grid((size_t)n * m.Ho * m.Wo * m.out_cs), 256, 0, st>>>(skip, n, k.cout, m.Ho, m.Wo, m.out_cs, fan_at(&r, m.skip));
+    conv_net_to_nhwc(in, n, k.cin, H, W, 0, m.in_cs, fan_at(&r, m.in), m.in_cs, st);
+    if (skip) conv_net_to_nhwc(skip, n, k.cout, m.Ho, m.Wo, 0, m.out_cs, fan_at(&r, m.skip), m.out_cs, st);
     for (int s = 0; s < p->steps; ++s) {
         const FanStep* t = &p->step[s];
         fan_step_launch(&r, &L, t, st);
     }
-    fan_to_nchw_kernel<<<conv_grid((size_t)n * k.cout * m.Ho * m.Wo), 256, 0, st>>>(fan_at(&r, m.out), n, k.cout, m.Ho, m.Wo, m.out_cs, out);
+    conv_net_to_nchw(fan_at(&r, m.out), m.out_cs, n, k.cout, m.Ho, m.Wo, 0, out, st);
 }
 
 extern "C" void n3dt_launch_fan_crops(int n, int H, int W, const float* frames, const int* boxes, float* out, hipStream_t st) {

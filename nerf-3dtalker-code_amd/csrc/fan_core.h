@@ -5,7 +5,7 @@
  *
  * Included by csrc/fan.hip, whose kernels take their sizes and addresses from the functions below, and by tests/fan_core_host.cpp,
  * which walks the same plan and the same functions over the kernels' grids on the CPU under the address and undefined-behaviour
- * sanitizers.  The rows of the implicit GEMM are syncnet_core.h's; the fragment arithmetic is conv_frag.h's.  Compiles as host C++
+ * sanitizers.  The rows of the implicit GEMM, the stem's row order and the wave-tile rule are conv_net_core.h's; the fragment arithmetic is conv_frag.h's.  Compiles as host C++
  * on its own.
  *
  * Maps.  NHWC fp32 WITHOUT halos: the pre-activation relu(g x + b) of a ConvBlock sits in the convolution's A-operand fetch, and a
@@ -21,7 +21,7 @@
 
 #include <stdint.h>
 
-#include "syncnet_core.h"
+#include "conv_net_core.h"
 
 #define FAN_MAX_MODULES 4
 #define FAN_MAX_LANDMARKS 127
@@ -32,9 +32,6 @@
 #define FAN_STEM_HW 128
 #define FAN_HEAT 64
 #define FAN_CELLS 4096
-#define FAN_STEM_K 147
-#define FAN_STEM_KP 160
-#define FAN_STEM_ROW 21
 #define FAN_MAX_IMAGES 1024
 #define FAN_WS_BUDGET ((size_t)4 << 30)
 #define FAN_BN_EPS 1e-5
@@ -87,32 +84,16 @@ static inline int fan_conv_exists(int j, int modules) {
     return s < modules && (t < 45 || s < modules - 1);
 }
 
-SN_HD int fan_round32(int c) { return (c + 31) / 32 * 32; }
 /* channels of the K loop (the stem: its flattened K), rows of the packed matrix, its columns */
-static inline int fan_cinp(const FanConv* c) { return c->kind == FAN_STEM ? 3 : sn_round16(c->cin); }
-static inline int fan_K(const FanConv* c) { return c->kind == FAN_STEM ? FAN_STEM_KP : c->k * c->k * sn_round16(c->cin); }
-static inline int fan_np(const FanConv* c) { return fan_round32(c->cout); }
+static inline int fan_cinp(const FanConv* c) { return c->kind == FAN_STEM ? 3 : cn_round16(c->cin); }
+static inline int fan_K(const FanConv* c) { return c->kind == FAN_STEM ? CN_STEM_KP : c->k * c->k * cn_round16(c->cin); }
+static inline int fan_np(const FanConv* c) { return cn_round32(c->cout); }
 /* channels a heat map is stored with: N + 1 padded to al's K */
-static inline int fan_heat_cs(int N) { return sn_round16(N + 1); }
-
-/* 32-column tiles per wave: two, unless the tile count is odd or that would leave fewer than 1024 waves (DESIGN 3.18's rule) */
-static inline int fan_wave_ntiles(long long M, int np) {
-    const long long mtiles = (M + SN_TILE_M - 1) / SN_TILE_M;
-    if ((np / 32) % 2) return 1;
-    return mtiles * (np / 64) < 1024 ? 1 : 2;
-}
-
-/* the stem's packed row k (< 147) -> (ky, kx, c) */
-SN_HD void fan_stem_tap(int k, int* ky, int* kx, int* c) {
-    *ky = k / FAN_STEM_ROW;
-    const int r = k - *ky * FAN_STEM_ROW;
-    *kx = r / 3;
-    *c = r - *kx * 3;
-}
+static inline int fan_heat_cs(int N) { return cn_round16(N + 1); }
 
 /* input pixel of output pixel o at tap t; whether it lies inside a map of `in` pixels */
-SN_HD int fan_tap_pixel(int o, int t, int stride, int pad) { return o * stride + t - pad; }
-SN_HD int fan_inside(int y, int x, int H, int W) { return y >= 0 && y < H && x >= 0 && x < W; }
+CN_HD int fan_tap_pixel(int o, int t, int stride, int pad) { return o * stride + t - pad; }
+CN_HD int fan_inside(int y, int x, int H, int W) { return y >= 0 && y < H && x >= 0 && x < W; }
 
 /* ---- the plan ----------------------------------------------------------------------------------------------------------------------
  * what a forward (or one block alone) launches, in order.  Offsets are floats PER IMAGE into the workspace, multiples of 64: a
@@ -299,8 +280,8 @@ static inline FanBlockMaps fan_plan_block(FanPlan* p, int b, int N, int H, int W
     p->top = p->peak = 0;
     m.Ho = k.div > 0 ? H / k.div : H * 2;
     m.Wo = k.div > 0 ? W / k.div : W * 2;
-    m.in_cs = k.cin == 3 ? 3 : sn_round16(k.cin);
-    m.out_cs = sn_round16(k.cout);
+    m.in_cs = k.cin == 3 ? 3 : cn_round16(k.cin);
+    m.out_cs = cn_round16(k.cout);
     m.in = fan_alloc(p, (size_t)H * W * m.in_cs);
     m.out = fan_alloc(p, (size_t)m.Ho * m.Wo * m.out_cs);
     m.skip = k.takes_skip ? fan_alloc(p, (size_t)m.Ho * m.Wo * m.out_cs) : FAN_NONE;
@@ -318,7 +299,7 @@ static inline size_t fan_ws_bytes_of(const FanPlan* p, int n) { return p->peak *
 
 /* ---- the decode ----------------------------------------------------------------------------------------------------------------------
  * numpy's argmax order: a NaN beats everything, the first index wins ties */
-SN_HD int fan_better(float v, int i, float bv, int bi) {
+CN_HD int fan_better(float v, int i, float bv, int bi) {
     const int vn = v != v, bn = bv != bv;
     if (vn != bn) return vn;
     if (vn || v == bv) return i < bi;
@@ -326,15 +307,15 @@ SN_HD int fan_better(float v, int i, float bv, int bi) {
 }
 
 /* calculate_points' neighbours of flat index i (i < 4095): literal flat indices, -1 wrapping to the map's last cell */
-SN_HD int fan_x_up(int i) { return i + 1; }
-SN_HD int fan_x_down(int i) { return i == 0 ? FAN_CELLS - 1 : i - 1; }
-SN_HD int fan_y_up(int i, int any_up) { return any_up ? FAN_CELLS - 1 : i + FAN_HEAT; }
-SN_HD int fan_y_down(int i, int any_down) { return any_down ? 0 : i - FAN_HEAT; }
-SN_HD int fan_flag_up(int i) { return i + FAN_HEAT >= FAN_CELLS; }
-SN_HD int fan_flag_down(int i) { return i - FAN_HEAT <= 0; }
-SN_HD double fan_sign(double d) { return d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : d; /* 0 stays 0, NaN stays NaN */ }
+CN_HD int fan_x_up(int i) { return i + 1; }
+CN_HD int fan_x_down(int i) { return i == 0 ? FAN_CELLS - 1 : i - 1; }
+CN_HD int fan_y_up(int i, int any_up) { return any_up ? FAN_CELLS - 1 : i + FAN_HEAT; }
+CN_HD int fan_y_down(int i, int any_down) { return any_down ? 0 : i - FAN_HEAT; }
+CN_HD int fan_flag_up(int i) { return i + FAN_HEAT >= FAN_CELLS; }
+CN_HD int fan_flag_down(int i) { return i - FAN_HEAT <= 0; }
+CN_HD double fan_sign(double d) { return d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : d; /* 0 stays 0, NaN stays NaN */ }
 
 /* a crop box (y1, y2, x1, x2) inside an H x W frame: fine, or the status bit 2 */
-SN_HD int fan_box_ok(const int* box, int H, int W) { return box[0] >= 0 && box[2] >= 0 && box[1] > box[0] && box[3] > box[2] && box[1] <= H && box[3] <= W; }
+CN_HD int fan_box_ok(const int* box, int H, int W) { return box[0] >= 0 && box[2] >= 0 && box[1] > box[0] && box[3] > box[2] && box[1] <= H && box[3] <= W; }
 
 #endif

@@ -22,6 +22,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "head_mask_core.h"
 #include "n3dt_launch.h"
 
@@ -48,37 +49,9 @@ static HmPackLayout hm_layout() {
     return L;
 }
 
-// eval-mode BatchNorm2d as a scale, float64; 1 where the convolution has none
-__device__ __forceinline__ double hm_bn_scale(const float* gamma, const float* var, double eps, int n) {
-    return gamma ? (double)gamma[n] / sqrt((double)var[n] + eps) : 1.0;
-}
-
-// W [cout, cin, k, k] -> B [K][np], row k = tap * cin + ci (the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero), columns from
-// cout on zero; each weight times its column's BatchNorm scale in float64, rounded once to fp32, then split
-__global__ __launch_bounds__(256) void head_mask_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
-                                                             const float* __restrict__ var, double eps, int cin, int cout, int np, int taps, int K,
-                                                             int stem, __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)K * np) return;
-    int k, n;
-    cf_pack_decode(e, np / 32, &k, &n);
-    float w = 0.0f;
-    if (n < cout) {
-        if (stem) {
-            if (k < FR_STEM_K) {
-                int ky, kx, c;
-                fr_stem_tap(k, &ky, &kx, &c);
-                w = (float)((double)W[((size_t)n * 3 + c) * 49 + ky * 7 + kx] * hm_bn_scale(gamma, var, eps, n));
-            }
-        } else {
-            const int tap = k / cin, ci = k - tap * cin;
-            w = (float)((double)W[((size_t)n * cin + ci) * taps + tap] * hm_bn_scale(gamma, var, eps, n));
-        }
-    }
-    const __bf16 h = (__bf16)w;
-    hi[e] = h;
-    lo[e] = conv_lo(w, h);
-}
+// The spatial pack (W [cout, cin, k, k] -> B [K][np], row k = tap * cin + ci; the stem: (ky * 7 + kx) * 3 + ci, rows 147 .. 159 zero;
+// columns from cout on zero), the BatchNorm's scale (1 where the convolution has none) and shift in float64, and the layouts are
+// conv_net.hip's.
 
 // a small convolution: W [cout, cin] -> dst [cin][cout] fp32, folded
 __global__ __launch_bounds__(256) void head_mask_pack_small_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
@@ -87,44 +60,7 @@ __global__ __launch_bounds__(256) void head_mask_pack_small_kernel(const float* 
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= cin * cout) return;
     const int ci = e / cout, co = e - ci * cout;
-    dst[e] = (float)((double)W[(size_t)co * cin + ci] * hm_bn_scale(gamma, var, eps, co));
-}
-
-__global__ __launch_bounds__(256) void head_mask_bias_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const float* __restrict__ mean, const float* __restrict__ var, double eps, int np,
-                                                             float* __restrict__ dst) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n < np) dst[n] = gamma ? (float)((double)beta[n] - (double)mean[n] * hm_bn_scale(gamma, var, eps, n)) : 0.0f;
-}
-
-// ---- layouts ---------------------------------------------------------------------------------------------------------------------
-// src [n, C, H, W] -> dst [n, H + 2 pad, W + 2 pad, C]: zero in the halo.  One thread per element.
-__global__ __launch_bounds__(256) void head_mask_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad,
-                                                                float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * Hp * Wp * C;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        int img, yp, xp;
-        fr_cell(e / C, Hp, Wp, &img, &yp, &xp);
-        float v = 0.0f;
-        if (xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad) v = src[(((size_t)img * C + c) * H + (yp - pad)) * W + (xp - pad)];
-        dst[e] = v;
-    }
-}
-
-// the first C of the Cs channels of src [n, H, W, Cs] -> dst [n, C, H, W]
-__global__ __launch_bounds__(256) void head_mask_to_nchw_kernel(const float* __restrict__ src, int n, int C, int Cs, int H, int W,
-                                                                float* __restrict__ dst) {
-    const size_t total = (size_t)n * C * H * W;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int x = (int)(e % W);
-        size_t t = e / W;
-        const int y = (int)(t % H);
-        t /= H;
-        const int c = (int)(t % C), img = (int)(t / C);
-        dst[e] = src[(((size_t)img * H + y) * W + x) * Cs + c];
-    }
+    dst[e] = (float)((double)W[(size_t)co * cin + ci] * conv_bn_scale(gamma, var, eps, co));
 }
 
 // ---- implicit-GEMM convolution ---------------------------------------------------------------------------------------------------
@@ -146,23 +82,19 @@ struct HmConvArgs {
 #define HM_STEMK 1
 #define HM_XFORM 2
 
-// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M output pixels x 32 NT columns, the column tile
+// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes CN_TILE_M output pixels x 32 NT columns, the column tile
 // fastest.  A k-step is 16 channels of one tap (C_in % 16 == 0); HM_STEMK: 16 consecutive k of the flattened (tap, channel) on the
 // haloed image, those from 147 on read as 0 against zero weight rows.  HM_XFORM: the fetched value v becomes v * scale + (addvec |
 // addmap | v | 0), in fp32, mul then add.  Epilogue: conv + bias (+ skip), then the ReLU -- relu(shortcut + residual).
 template <int NT, int MODE>
 __global__ __launch_bounds__(256) void head_mask_conv_kernel(HmConvArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long M = (long long)a.n * a.Ho * a.Wo;
-    const int ntn = a.np / (32 * NT);
-    const long long tile = (long long)blockIdx.x * 4 + wave;
-    const long long m0 = tile / ntn * SN_TILE_M;
-    if (m0 >= M) return;  // no barriers in this kernel: an idle wave may leave
-    const int nt0 = (int)(tile % ntn) * NT;
+    const ConvWaveTile t = conv_wave_tile<NT>(a.np, a.n, a.Ho, a.Wo);
+    if (t.idle()) return;  // no barriers in this kernel: an idle wave may leave
+    const int lane = t.lane, r = t.r, h = t.h, nt0 = t.nt0(NT);
+    const long long M = t.M, m0 = t.m0;
     int img[2], yo[2], xo[2];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) sn_row_cell(m0 + mt * 32 + r, M, a.Ho, a.Wo, &img[mt], &yo[mt], &xo[mt]);  // rows past M: the last pixel again, never stored
+    for (int mt = 0; mt < 2; ++mt) cn_row_cell(m0 + mt * 32 + r, M, a.Ho, a.Wo, &img[mt], &yo[mt], &xo[mt]);  // rows past M: the last pixel again, never stored
     conv_f32x16 acc[2][NT];
     CONV_ZERO_ACC(acc, NT);
     float av[2][8];
@@ -171,13 +103,13 @@ __global__ __launch_bounds__(256) void head_mask_conv_kernel(HmConvArgs a) {
         const int Wp = a.Wi + 6;
         const float* base[2];
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) base[mt] = a.in + fr_field_base(img[mt], yo[mt], xo[mt], a.stride, a.Hi + 6, Wp, 3);
-        for (int s = 0; s < FR_STEM_KP / 16; ++s) {
+        for (int mt = 0; mt < 2; ++mt) base[mt] = a.in + cn_field_base(img[mt], yo[mt], xo[mt], a.stride, a.Hi + 6, Wp, 3);
+        for (int s = 0; s < CN_STEM_KP / 16; ++s) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = 16 * s + 8 * h + j;
-                const bool real = k < FR_STEM_K;
-                const size_t off = fr_stem_offset(real ? k : 0, Wp);
+                const bool real = k < CN_STEM_K;
+                const size_t off = cn_stem_offset(real ? k : 0, Wp);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     const float v = base[mt][off];
@@ -243,32 +175,7 @@ __global__ __launch_bounds__(256) void head_mask_conv_kernel(HmConvArgs a) {
         }
 }
 
-// ---- pool, the small stage -------------------------------------------------------------------------------------------------------
-// in [n, Hi, Wi, C] -> out [n, Ho, Wo, C], Ho = (Hi - 1) / 2 + 1: the maximum over the taps of the 3 x 3 window that lie inside the
-// map (max_pool2d pads with -inf).  One thread per four channels of an output cell.
-__global__ __launch_bounds__(256) void head_mask_pool_kernel(const float* __restrict__ in, int n, int Hi, int Wi, int C, float* __restrict__ out) {
-    const int Ho = fr_pool_out(Hi), Wo = fr_pool_out(Wi), C4 = C / 4;
-    const size_t total = (size_t)n * Ho * Wo * C4;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % C4) * 4;
-        int img, yo, xo;
-        fr_cell(e / C4, Ho, Wo, &img, &yo, &xo);
-        int ya, yb, xa, xb;
-        fr_pool_range(yo, Hi, &ya, &yb);
-        fr_pool_range(xo, Wi, &xa, &xb);
-        float4 v = *reinterpret_cast<const float4*>(in + (((size_t)img * Hi + ya) * Wi + xa) * C + c);
-        for (int y = ya; y < yb; ++y)
-            for (int x = xa; x < xb; ++x) {
-                const float4 t = *reinterpret_cast<const float4*>(in + (((size_t)img * Hi + y) * Wi + x) * C + c);
-                v.x = fmaxf(v.x, t.x);
-                v.y = fmaxf(v.y, t.y);
-                v.z = fmaxf(v.z, t.z);
-                v.w = fmaxf(v.w, t.w);
-            }
-        *reinterpret_cast<float4*>(out + e * 4) = v;
-    }
-}
-
+// ---- the small stage (the 3 x 3 / 2 max pool is conv_net.hip's) --------------------------------------------------------------------
 // One workgroup per image.  in: image i's HW cells of cin channels start at in + i * in_stride (HW = 1: a vector).  The mean of
 // every channel, summed in float64 in cell order and kept in float64; then out[i][co] = act(sum_ci Wt[ci][co] * mean[ci] + bias[co])
 // with ci ascending, float64, rounded once.  cin <= 512.
@@ -306,7 +213,7 @@ __global__ __launch_bounds__(256) void head_mask_labels_kernel(HmLogits L, int n
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n * H * W) return;
     int img, Y, X;
-    fr_cell(e, H, W, &img, &Y, &X);
+    cn_cell(e, H, W, &img, &Y, &X);
     int y0, y1, x0, x1;
     double wy, wx;
     hm_lerp(Y, L.h, H, &y0, &y1, &wy);
@@ -370,7 +277,7 @@ __global__ __launch_bounds__(256) void head_mask_frames_kernel(const void* __res
     }
 }
 
-// src bytes [n, Hs, Ws, C] -> dst [n, Hd, Wd, C]: bilinear with half-pixel centres (syncnet_core.h's sn_bilinear), float64, rounded to
+// src bytes [n, Hs, Ws, C] -> dst [n, Hd, Wd, C]: bilinear with half-pixel centres (conv_net_core.h's cn_bilinear), float64, rounded to
 // the nearest byte.  An equal size is a copy.  OpenCV's fixed-point INTER_LINEAR is not reproduced.
 __global__ __launch_bounds__(256) void head_mask_resize_kernel(const uint8_t* __restrict__ src, int n, int Hs, int Ws, int C, int Hd, int Wd,
                                                                uint8_t* __restrict__ dst) {
@@ -378,11 +285,11 @@ __global__ __launch_bounds__(256) void head_mask_resize_kernel(const uint8_t* __
     if (e >= (size_t)n * Hd * Wd * C) return;
     const int c = (int)(e % C);
     int img, y, x;
-    fr_cell(e / C, Hd, Wd, &img, &y, &x);
+    cn_cell(e / C, Hd, Wd, &img, &y, &x);
     int y0, y1, x0, x1;
     double wy, wx;
-    sn_bilinear(y, Hs, Hd, &y0, &y1, &wy);
-    sn_bilinear(x, Ws, Wd, &x0, &x1, &wx);
+    cn_bilinear(y, Hs, Hd, &y0, &y1, &wy);
+    cn_bilinear(x, Ws, Wd, &x0, &x1, &wx);
     const uint8_t* p = src + (size_t)img * Hs * Ws * C + c;
     const double v00 = p[((size_t)y0 * Ws + x0) * C], v01 = p[((size_t)y0 * Ws + x1) * C], v10 = p[((size_t)y1 * Ws + x0) * C], v11 = p[((size_t)y1 * Ws + x1) * C];
     const double v = (1.0 - wy) * ((1.0 - wx) * v00 + wx * v01) + wy * ((1.0 - wx) * v10 + wx * v11);
@@ -406,7 +313,7 @@ __global__ __launch_bounds__(256) void head_mask_dilate_kernel(const uint8_t* __
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n * H * W) return;
     int img, y, x;
-    fr_cell(e, H, W, &img, &y, &x);
+    cn_cell(e, H, W, &img, &y, &x);
     const uint8_t* p = src + (size_t)img * H * W;
     int v = 0;
     for (int i = 0; i < eh; ++i) {
@@ -447,7 +354,7 @@ __global__ __launch_bounds__(256) void head_mask_cc_merge_kernel(const uint8_t* 
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n * H * W || !work[e]) return;
     int img, y, x;
-    fr_cell(e, H, W, &img, &y, &x);
+    cn_cell(e, H, W, &img, &y, &x);
     const uint8_t* wk = work + (size_t)img * H * W;
     int* par = parent + (size_t)img * H * W;
     const int dy[4] = {0, -1, -1, -1}, dx[4] = {-1, -1, 0, 1};
@@ -525,7 +432,7 @@ __global__ __launch_bounds__(256) void head_mask_erode_kernel(const uint8_t* __r
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n * H * W) return;
     int img, y, x;
-    fr_cell(e, H, W, &img, &y, &x);
+    cn_cell(e, H, W, &img, &y, &x);
     const uint8_t* p = src + (size_t)img * H * W;
     const int c = p[y * W + x];
     const int sum = (y > 0 ? p[(y - 1) * W + x] : 0) + (y < H - 1 ? p[(y + 1) * W + x] : 0) + (x > 0 ? p[y * W + x - 1] : 0) + (x < W - 1 ? p[y * W + x + 1] : 0);
@@ -567,10 +474,10 @@ extern "C" void n3dt_launch_head_mask_pack(const N3dtHeadMaskParams* p, void* pa
                                                                                          (float*)(base + L.w[j]));
         } else {
             __bf16* hi = (__bf16*)(base + L.w[j]);
-            head_mask_pack_kernel<<<hm_blocks(L.elems[j]), 256, 0, st>>>(p->weight[j], gamma, p->bn_var[j], p->bn_eps, t.cin, cout, np, t.k * t.k, hm_K(j),
-                                                                         t.kind == HM_STEM, hi, hi + L.elems[j]);
+            conv_net_pack(p->weight[j], gamma, p->bn_var[j], p->bn_eps, t.cin, t.cin, t.cin, cout, np, t.k * t.k, hm_K(j), t.kind == HM_STEM, hi,
+                          hi + L.elems[j], st);
         }
-        head_mask_bias_kernel<<<(np + 255) / 256, 256, 0, st>>>(gamma, p->bn_bias[j], p->bn_mean[j], p->bn_var[j], p->bn_eps, np, (float*)(base + L.bias[j]));
+        conv_net_shift_bn(gamma, p->bn_bias[j], p->bn_mean[j], p->bn_var[j], p->bn_eps, np, (float*)(base + L.bias[j]), st);
     }
 }
 
@@ -591,8 +498,8 @@ static void hm_conv_launch(int j, int n, const HmStep& t, const void* packed, co
     a.cin = c.cin; a.csplit = in2 ? c.cin / 2 : c.cin; a.np = hm_np(j); a.k = c.k; a.stride = c.stride; a.pad = c.pad;
     a.relu = c.act == HM_RELU; a.addself = t.addself; a.vstride = vstride;
     const size_t M = (size_t)n * a.Ho * a.Wo;
-    const int nt = hm_wave_ntiles(a.np, M);
-    const size_t tiles = (M + SN_TILE_M - 1) / SN_TILE_M * (a.np / (32 * nt));
+    const int nt = cn_wave_ntiles((long long)M, a.np);
+    const size_t tiles = (M + CN_TILE_M - 1) / CN_TILE_M * (a.np / (32 * nt));
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     if (c.kind == HM_STEM) {
         if (nt == 1) head_mask_conv_kernel<1, HM_STEMK><<<grid, 256, 0, st>>>(a);
@@ -629,14 +536,13 @@ extern "C" void n3dt_launch_head_mask_fwd(int n, int H, int W, int n_classes, co
     float* region[HM_REGIONS];
     for (int r = 0; r < HM_REGIONS; ++r) region[r] = (float*)(ws + w.region[r]);
     float* vec = region[HM_R_VEC];
-    head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * (H + 6) * (W + 6) * 3), 256, 0, st>>>(x, n, 3, H, W, 3, region[HM_R_IMG]);
+    conv_net_to_nhwc(x, n, 3, H, W, 3, 3, region[HM_R_IMG], 3, st);
     HmStep steps[HM_MAX_STEPS];
     const int count = hm_chain(H, W, outputs, steps);
     for (int s = 0; s < count; ++s) {
         const HmStep t = steps[s];
         if (t.block == HM_POOL_BLOCK) {
-            const size_t work = (size_t)n * fr_pool_out(t.Hi) * fr_pool_out(t.Wi) * (64 / 4);
-            head_mask_pool_kernel<<<conv_grid(work), 256, 0, st>>>(region[t.in], n, t.Hi, t.Wi, 64, region[t.out]);
+            conv_net_max_pool(region[t.in], n, t.Hi, t.Wi, 64, region[t.out], st);
         } else if (HM_TABLE[t.block].kind == HM_SMALL) {
             if (t.invec >= 0) hm_small_launch(t.block, n, n_classes, packed, vec + t.invec, 1, HM_VEC, vec + t.out, HM_VEC, st);
             else hm_small_launch(t.block, n, n_classes, packed, region[t.in], t.Hi * t.Wi, (size_t)t.Hi * t.Wi * HM_TABLE[t.block].cin, vec + t.out, HM_VEC, st);
@@ -652,7 +558,7 @@ extern "C" void n3dt_launch_head_mask_fwd(int n, int H, int W, int n_classes, co
         hm_logit_hw(H, W, o, &h, &wd);
         const float* lg = region[HM_R_LOG0 + o];
         if (upsample) head_mask_upsample_kernel<<<conv_grid((size_t)n * n_classes * H * W), 256, 0, st>>>(hm_nhwc_logits(lg, n_classes, h, wd), n, H, W, out[o]);
-        else head_mask_to_nchw_kernel<<<conv_grid((size_t)n * n_classes * h * wd), 256, 0, st>>>(lg, n, n_classes, HM_MAX_CLASSES, h, wd, out[o]);
+        else conv_net_to_nchw(lg, HM_MAX_CLASSES, n, n_classes, h, wd, 0, out[o], st);
     }
 }
 
@@ -667,15 +573,14 @@ extern "C" void n3dt_launch_head_mask_block(int block, int n, int Hi, int Wi, in
     float* map1 = (float*)((char*)workspace + w.aux);
     float* map2 = (float*)((char*)workspace + w.out);
     if (block == HM_POOL_BLOCK) {
-        head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Hi * Wi * 64), 256, 0, st>>>(in, n, 64, Hi, Wi, 0, map0);
-        const int Ho = fr_pool_out(Hi), Wo = fr_pool_out(Wi);
-        head_mask_pool_kernel<<<conv_grid((size_t)n * Ho * Wo * 16), 256, 0, st>>>(map0, n, Hi, Wi, 64, map2);
-        head_mask_to_nchw_kernel<<<conv_grid((size_t)n * 64 * Ho * Wo), 256, 0, st>>>(map2, n, 64, 64, Ho, Wo, out);
+        conv_net_to_nhwc(in, n, 64, Hi, Wi, 0, 64, map0, 64, st);
+        conv_net_max_pool(map0, n, Hi, Wi, 64, map2, st);
+        conv_net_to_nchw(map2, 64, n, 64, cn_pool_out(Hi), cn_pool_out(Wi), 0, out, st);
         return;
     }
     const HmConv c = HM_TABLE[block];
     if (c.kind == HM_SMALL) {
-        head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Hi * Wi * c.cin), 256, 0, st>>>(in, n, c.cin, Hi, Wi, 0, map0);
+        conv_net_to_nhwc(in, n, c.cin, Hi, Wi, 0, c.cin, map0, c.cin, st);
         hm_small_launch(block, n, n_classes, packed, map0, Hi * Wi, (size_t)Hi * Wi * c.cin, out, c.cout, st);
         return;
     }
@@ -683,26 +588,26 @@ extern "C" void n3dt_launch_head_mask_block(int block, int n, int Hi, int Wi, in
     const int Ho = hm_out_h(block, Hi), Wo = hm_out_h(block, Wi), np = hm_np(block), cout = hm_cout(block, n_classes);
     const float *in2 = nullptr, *skip = nullptr, *addmap = nullptr;
     if (c.kind == HM_STEM) {
-        head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * (Hi + 6) * (Wi + 6) * 3), 256, 0, st>>>(in, n, 3, Hi, Wi, 3, map0);
+        conv_net_to_nhwc(in, n, 3, Hi, Wi, 3, 3, map0, 3, st);
     } else {
         t.Hs = Hs;
         t.Ws = Ws;
         const int cin0 = block == HM_FFM_BLK ? c.cin / 2 : c.cin;
-        head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Hs * Ws * cin0), 256, 0, st>>>(in, n, cin0, Hs, Ws, 0, map0);
+        conv_net_to_nhwc(in, n, cin0, Hs, Ws, 0, cin0, map0, cin0, st);
         if (block == HM_FFM_BLK) {
-            head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Hs * Ws * cin0), 256, 0, st>>>(aux, n, cin0, Hs, Ws, 0, map1);
+            conv_net_to_nhwc(aux, n, cin0, Hs, Ws, 0, cin0, map1, cin0, st);
             in2 = map1;
         } else if (hm_takes_skip(block)) {
-            head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Ho * Wo * np), 256, 0, st>>>(aux, n, np, Ho, Wo, 0, map1);
+            conv_net_to_nhwc(aux, n, np, Ho, Wo, 0, np, map1, np, st);
             skip = map1;
         } else if (block == HM_HEAD16 && scale && aux) {
-            head_mask_to_nhwc_kernel<<<conv_grid((size_t)n * Hs * Ws * c.cin), 256, 0, st>>>(aux, n, c.cin, Hs, Ws, 0, map1);
+            conv_net_to_nhwc(aux, n, c.cin, Hs, Ws, 0, c.cin, map1, c.cin, st);
             addmap = map1;
         }
         t.addself = block == HM_OUT && scale;
     }
     hm_conv_launch(block, n, t, packed, map0, in2, skip, addmap, scale, addvec, c.cin, map2, st);
-    head_mask_to_nchw_kernel<<<conv_grid((size_t)n * cout * Ho * Wo), 256, 0, st>>>(map2, n, cout, np, Ho, Wo, out);
+    conv_net_to_nchw(map2, np, n, cout, Ho, Wo, 0, out, st);
 }
 
 extern "C" void n3dt_launch_head_mask_frames(int n, int H, int W, const void* frames, int is_float, uint8_t* rgb, float* x, hipStream_t st) {

@@ -4,8 +4,8 @@
  * DataProcess/Gen_HeadMask.py and correct_head_mask.py behind it.
  *
  * Included by csrc/head_mask.hip, whose kernels take their sizes and addresses from the functions below, and by
- * tests/head_mask_core_host.cpp, which walks the same functions over the kernels' grids on the CPU.  The rows of the implicit GEMM
- * are syncnet_core.h's, the stem's gather and the pool's window face_recon_core.h's, the fragment arithmetic conv_frag.h's.
+ * tests/head_mask_core_host.cpp, which walks the same functions over the kernels' grids on the CPU.  The rows of the implicit GEMM,
+ * the stem's gather, the pool's window and the wave-tile rule are conv_net_core.h's, the fragment arithmetic conv_frag.h's.
  * Compiles as host C++ on its own.
  *
  * Blocks.  37 of them: 0..35 the convolutions in state-dict order (cp.resnet: conv1, then per BasicBlock conv1, conv2 and, where
@@ -24,7 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "face_recon_core.h"
+#include "conv_net_core.h"
 
 #define HM_CONVS 36
 #define HM_BLOCKS 37
@@ -73,22 +73,16 @@ enum {
 /* the packed matrix's columns: a head's n_classes padded to one 32-column tile */
 static inline int hm_np(int j) { return HM_TABLE[j].cout ? HM_TABLE[j].cout : HM_MAX_CLASSES; }
 static inline int hm_cout(int j, int n_classes) { return HM_TABLE[j].cout ? HM_TABLE[j].cout : n_classes; }
-static inline int hm_K(int j) { return HM_TABLE[j].kind == HM_STEM ? FR_STEM_KP : HM_TABLE[j].k * HM_TABLE[j].k * HM_TABLE[j].cin; }
+static inline int hm_K(int j) { return HM_TABLE[j].kind == HM_STEM ? CN_STEM_KP : HM_TABLE[j].k * HM_TABLE[j].k * HM_TABLE[j].cin; }
 /* a BasicBlock's second convolution adds the shortcut in front of its ReLU */
 static inline int hm_takes_skip(int j) { return j == 2 || j == 4 || j == 6 || j == 9 || j == 11 || j == 14 || j == 16 || j == 19; }
 
-SN_HD int hm_hw_ok(int H, int W) { return H >= HM_MIN_HW && W >= HM_MIN_HW && H <= SN_MAX_FRAME_HW && W <= SN_MAX_FRAME_HW; }
-
-/* 32-column tiles per wave: one for a head's single tile and where two would leave fewer than 1024 waves; else two */
-static inline int hm_wave_ntiles(int np, size_t M) {
-    const size_t mtiles = (M + SN_TILE_M - 1) / SN_TILE_M;
-    return (np == 32 || mtiles * (size_t)(np / 64) < 1024) ? 1 : 2;
-}
+CN_HD int hm_hw_ok(int H, int W) { return H >= HM_MIN_HW && W >= HM_MIN_HW && H <= CN_MAX_FRAME_HW && W <= CN_MAX_FRAME_HW; }
 
 /* ---- addresses -------------------------------------------------------------------------------------------------------------------
  * F.interpolate(mode='nearest'): destination index dst of `out` reads source index min(int(floorf(dst * float(in) / out)), in - 1),
  * in float32 as torch computes it; an equal size is the identity */
-SN_HD int hm_nearest(int dst, int in, int out) {
+CN_HD int hm_nearest(int dst, int in, int out) {
     if (in == out) return dst;
     const float scale = (float)in / (float)out;
     const int s = (int)floorf((float)dst * scale);
@@ -97,7 +91,7 @@ SN_HD int hm_nearest(int dst, int in, int out) {
 
 /* tap (ky, kx) = (tap / k, tap % k) of output pixel (yo, xo): the pixel (iy, ix) = (yo stride + ky - pad, ..) of the Hi x Wi input,
  * which is cell (hm_nearest(iy), hm_nearest(ix)) of the Hs x Ws source map [n, Hs, Ws]; returns 0 (and no cell) in the padding */
-SN_HD int hm_tap_cell(int img, int yo, int xo, int tap, int k, int stride, int pad, int Hi, int Wi, int Hs, int Ws, long long* cell) {
+CN_HD int hm_tap_cell(int img, int yo, int xo, int tap, int k, int stride, int pad, int Hi, int Wi, int Hs, int Ws, long long* cell) {
     const int ky = tap / k, kx = tap - ky * k;
     const int iy = yo * stride + ky - pad, ix = xo * stride + kx - pad;
     if (iy < 0 || iy >= Hi || ix < 0 || ix >= Wi) return 0;
@@ -106,7 +100,7 @@ SN_HD int hm_tap_cell(int img, int yo, int xo, int tap, int k, int stride, int p
 }
 
 /* F.interpolate(mode='bilinear', align_corners=True) along one axis, float64: src = d (in - 1) / (out - 1) */
-SN_HD void hm_lerp(int d, int in, int out, int* i0, int* i1, double* w1) {
+CN_HD void hm_lerp(int d, int in, int out, int* i0, int* i1, double* w1) {
     const double scale = out > 1 ? (double)(in - 1) / (double)(out - 1) : 0.0;
     const double src = scale * (double)d;
     int a = (int)src;
@@ -118,7 +112,7 @@ SN_HD void hm_lerp(int d, int in, int out, int* i0, int* i1, double* w1) {
 
 /* OpenCV's 8-bit hue of cvtColor(.., COLOR_BGR2HSV) for the bytes it is handed as (b, g, r): range 180, 12 fractional bits, the
  * divisor table rounded to nearest-even as its saturate_cast does */
-SN_HD int hm_hue(int b, int g, int r) {
+CN_HD int hm_hue(int b, int g, int r) {
     int v = b > g ? b : g, vmin = b < g ? b : g;
     if (r > v) v = r;
     if (r < vmin) vmin = r;
@@ -153,7 +147,7 @@ static inline HmStep hm_step(int block, int Hi, int Wi, int in, int out) {
     return s;
 }
 
-static inline int hm_out_h(int j, int Hi) { return sn_conv_out(Hi, HM_TABLE[j].k, HM_TABLE[j].stride, HM_TABLE[j].pad); }
+static inline int hm_out_h(int j, int Hi) { return cn_conv_out(Hi, HM_TABLE[j].k, HM_TABLE[j].stride, HM_TABLE[j].pad); }
 
 /* the sizes of the three feature maps and the stem's and pool's outputs for an H x W image */
 typedef struct HmSizes {
@@ -163,7 +157,7 @@ typedef struct HmSizes {
 static inline HmSizes hm_sizes(int H, int W) {
     HmSizes z;
     z.H2 = hm_out_h(0, H); z.W2 = hm_out_h(0, W);
-    z.H4 = fr_pool_out(z.H2); z.W4 = fr_pool_out(z.W2);
+    z.H4 = cn_pool_out(z.H2); z.W4 = cn_pool_out(z.W2);
     z.H8 = hm_out_h(5, z.H4); z.W8 = hm_out_h(5, z.W4);
     z.H16 = hm_out_h(10, z.H8); z.W16 = hm_out_h(10, z.W8);
     z.H32 = hm_out_h(15, z.H16); z.W32 = hm_out_h(15, z.W16);
@@ -240,7 +234,7 @@ static inline int hm_chain(int H, int W, int outputs, HmStep steps[HM_MAX_STEPS]
 
 /* a step's output map, elements per image (0 for a small step: it writes a vector) */
 static inline size_t hm_step_out_elems(const HmStep* st) {
-    if (st->block == HM_POOL_BLOCK) return (size_t)fr_pool_out(st->Hi) * fr_pool_out(st->Wi) * 64;
+    if (st->block == HM_POOL_BLOCK) return (size_t)cn_pool_out(st->Hi) * cn_pool_out(st->Wi) * 64;
     if (HM_TABLE[st->block].kind == HM_SMALL) return 0;
     return (size_t)hm_out_h(st->block, st->Hi) * hm_out_h(st->block, st->Wi) * hm_np(st->block);
 }
@@ -265,7 +259,7 @@ static inline HmWorkspace hm_workspace(int n, int H, int W) {
     size_t off = 0;
     for (int r = 0; r < HM_REGIONS; ++r) {
         w.region[r] = off;
-        w.bytes[r] = fr_rup256((size_t)n * elems[r] * sizeof(float));
+        w.bytes[r] = cn_rup256((size_t)n * elems[r] * sizeof(float));
         off += w.bytes[r];
     }
     w.total = off;
@@ -289,7 +283,7 @@ static inline HmBlockWs hm_block_ws(int block, int n, int Hi, int Wi, int Hs, in
     size_t in_e, out_e;
     if (block == HM_POOL_BLOCK) {
         in_e = (size_t)Hi * Wi * 64;
-        out_e = (size_t)fr_pool_out(Hi) * fr_pool_out(Wi) * 64;
+        out_e = (size_t)cn_pool_out(Hi) * cn_pool_out(Wi) * 64;
     } else if (HM_TABLE[block].kind == HM_STEM) {
         in_e = (size_t)(Hi + 6) * (Wi + 6) * 3;
         out_e = (size_t)hm_out_h(0, Hi) * hm_out_h(0, Wi) * 64;
@@ -302,9 +296,9 @@ static inline HmBlockWs hm_block_ws(int block, int n, int Hi, int Wi, int Hs, in
     }
     HmBlockWs w;
     w.in = 0;
-    w.aux = fr_rup256((size_t)n * in_e * sizeof(float));
-    w.out = w.aux + fr_rup256((size_t)n * (in_e > out_e ? in_e : out_e) * sizeof(float));
-    w.total = w.out + fr_rup256((size_t)n * out_e * sizeof(float));
+    w.aux = cn_rup256((size_t)n * in_e * sizeof(float));
+    w.out = w.aux + cn_rup256((size_t)n * (in_e > out_e ? in_e : out_e) * sizeof(float));
+    w.total = w.out + cn_rup256((size_t)n * out_e * sizeof(float));
     return w;
 }
 
@@ -318,13 +312,13 @@ static inline HmPostWs hm_post_ws(int n, int H, int W) {
     const size_t px = (size_t)n * H * W;
     HmPostWs w;
     size_t off = 0;
-    w.parent = off; off += fr_rup256(px * 4);
-    w.area = off;   off += fr_rup256(px * 4);
-    w.best = off;   off += fr_rup256((size_t)n * 8);
-    w.work = off;   off += fr_rup256(px);
-    w.orig = off;   off += fr_rup256(px);
-    w.a = off;      off += fr_rup256(px);
-    w.b = off;      off += fr_rup256(px);
+    w.parent = off; off += cn_rup256(px * 4);
+    w.area = off;   off += cn_rup256(px * 4);
+    w.best = off;   off += cn_rup256((size_t)n * 8);
+    w.work = off;   off += cn_rup256(px);
+    w.orig = off;   off += cn_rup256(px);
+    w.a = off;      off += cn_rup256(px);
+    w.b = off;      off += cn_rup256(px);
     w.total = off;
     return w;
 }

@@ -31,6 +31,7 @@
 #include "../../include/n3dt.h"
 #include "eval_metrics_core.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "lpips_core.h"
 #include "n3dt_launch.h"
 
@@ -76,11 +77,6 @@ __global__ __launch_bounds__(256) void lpips_pack_kernel(const float* __restrict
     const __bf16 h = (__bf16)w;
     hi[e] = h;
     lo[e] = conv_lo(w, h);
-}
-
-__global__ __launch_bounds__(256) void lpips_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = src[e];
 }
 
 // ---- prologue --------------------------------------------------------------------------------------------------------------------
@@ -334,8 +330,8 @@ extern "C" void n3dt_launch_lpips_pack(const N3dtLpipsParams* p, void* packed, h
         __bf16* hi = (__bf16*)(base + L.w[l]);
         const size_t n = L.elems[l];
         lpips_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p->weight[l], lp_cin(l), lp_cout(l), lp_ksize(l), lp_kp(l), hi, hi + n);
-        lpips_copy_kernel<<<(lp_cout(l) + 255) / 256, 256, 0, st>>>(p->bias[l], lp_cout(l), (float*)(base + L.bias[l]));
-        lpips_copy_kernel<<<(lp_cout(l) + 255) / 256, 256, 0, st>>>(p->lin[l], lp_cout(l), (float*)(base + L.lin[l]));
+        conv_net_copy(p->bias[l], (size_t)lp_cout(l), (float*)(base + L.bias[l]), st);
+        conv_net_copy(p->lin[l], (size_t)lp_cout(l), (float*)(base + L.lin[l]), st);
     }
 }
 

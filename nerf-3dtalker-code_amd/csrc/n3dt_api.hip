@@ -697,7 +697,7 @@ extern "C" int n3dt_mel_windows(int64_t T, const void* mel, int64_t mel_ld, int 
 // lip-sync expert (csrc/syncnet.hip): the limits of include/n3dt.h, checked before anything is enqueued
 static const char* syncnet_windows(int n) { return (n < 1 || n > SN_MAX_WINDOWS) ? "n outside 1..1024" : nullptr; }
 static const char* syncnet_frames(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes) {
-    if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 2..4096";
+    if (height < 2 || width < 2 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) return "height and width must be in 2..4096";
     if (!frames || !boxes) return "NULL pointer";
     if (n_boxes != 1 && n_boxes != n + SN_FACE_FRAMES - 1) return "n_boxes must be 1 or n + 4 (one box per frame)";
     if ((((size_t)frames) | ((size_t)boxes)) & 3) return "frames and boxes must be 4-byte aligned";
@@ -787,7 +787,7 @@ static const char* wav2lip_windows(int n) { return (n < 1 || n > W2L_MAX_WINDOWS
 static const char* wav2lip_frames(int n, int height, int width, const float* frames, const int32_t* boxes, int n_boxes, const float* other,
                                   const float* out) {
     if (n < 1 || n > W2L_MAX_FRAMES) return "n outside 1..4096";
-    if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 2..4096";
+    if (height < 2 || width < 2 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) return "height and width must be in 2..4096";
     if (!frames || !boxes || !out) return "NULL pointer";
     if (n_boxes != 1 && n_boxes != n) return "n_boxes must be 1 or n (one box per frame)";
     if ((((size_t)frames) | ((size_t)boxes) | ((size_t)other)) & 3) return "frames and boxes must be 4-byte aligned";
@@ -958,7 +958,7 @@ extern "C" int n3dt_s3fd_boxes(int n_frames, int height, int width, int max_face
     const char* what = nullptr;
     const int lim = 1 << 20;
     if (n_frames < 1 || n_frames > S3_MAX_CLIP) what = "n_frames outside 1..2^20";
-    else if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
+    else if (height < 2 || width < 2 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
     else if (max_faces < 1 || max_faces > S3_MAX_FACES) what = "max_faces outside 1..64";
     else if (smooth < 0 || smooth > S3_MAX_SMOOTH) what = "smooth outside 0..64";
     else if (pady1 < -lim || pady1 > lim || pady2 < -lim || pady2 > lim || padx1 < -lim || padx1 > lim || padx2 < -lim || padx2 > lim)
@@ -976,7 +976,7 @@ extern "C" int n3dt_s3fd_boxes(int n_frames, int height, int width, int max_face
 static const char* s3fd_block_size(int block, int n, int height, int width) {
     if (block < 0 || block >= S3_BLOCKS) return "block outside 0..32";
     if (n < 1 || n > S3_MAX_IMAGES) return "n outside 1..1024";
-    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW + 4 || width > SN_MAX_FRAME_HW + 4) return "height and width must be in 1..4100";
+    if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW + 4 || width > CN_MAX_FRAME_HW + 4) return "height and width must be in 1..4100";
     const bool pool = block >= S3_FIRST_POOL && block < S3_FIRST_NORM;
     if (pool && (height < 2 || width < 2)) return "a pool needs 2 x 2 pixels";
     if (n3dt_s3fd_block_ws_bytes(block, n, height, width) > S3_WS_BUDGET) return "the block's maps exceed the workspace budget";
@@ -1067,7 +1067,7 @@ extern "C" int n3dt_face_recon_fwd(int n, int height, int width, const void* pac
 static const char* face_recon_block_size(int block, int n, int height, int width) {
     if (block < 0 || block >= FR_BLOCKS) return "block outside 0..55";
     if (n < 1 || n > FR_MAX_IMAGES) return "n outside 1..1024";
-    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) return "height and width must be in 1..4096";
     if (block == 0 && (height < 2 || width < 2)) return "the stem needs 2 x 2 pixels";
     if (block == FR_HEAD_BLOCK && (height != 1 || width != 1)) return "the head takes height = width = 1";
     if (n3dt_face_recon_block_ws_bytes(block, n, height, width) > FR_WS_BUDGET) return "the block's maps exceed the workspace budget";
@@ -1107,7 +1107,7 @@ extern "C" int n3dt_face_recon_align(int n, int height, int width, const float* 
     static const char* who = "n3dt_face_recon_align";
     const char* what = nullptr;
     if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
-    else if (height < 2 || width < 2 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
+    else if (height < 2 || width < 2 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) what = "height and width must be in 2..4096";
     else if (landmarks && points != 68 && points != 5) what = "points must be 68 or 5";
     else if (!frames || !lm3d_std || !pinv || !crops || !trans_params || !geom || !status) what = "NULL pointer";
     else if ((((size_t)landmarks) | ((size_t)lm3d_std) | ((size_t)pinv) | ((size_t)trans_params)) & 7)
@@ -1248,7 +1248,7 @@ extern "C" int n3dt_fan_crops(int n, int height, int width, const float* frames,
     static const char* who = "n3dt_fan_crops";
     const char* what = nullptr;
     if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
-    else if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
+    else if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
     else if (!frames || !boxes || !out) what = "NULL pointer";
     else if ((((size_t)frames) | ((size_t)boxes) | ((size_t)out)) & 3) what = "frames, boxes and out must be 4-byte aligned";
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
@@ -1276,7 +1276,7 @@ extern "C" int n3dt_fan_tail(int n, int num_landmarks, int points_out, int heigh
     if (n < 1 || n > (1 << 20)) what = "n outside 1..2^20";
     else if (num_landmarks < 1 || num_landmarks > FAN_MAX_LANDMARKS) what = "num_landmarks outside 1..127";
     else if (points_out < 1 || points_out > 1024 || (!table && points_out != num_landmarks)) what = "points_out outside 1..1024, or not num_landmarks without a table";
-    else if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
+    else if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) what = "height and width must be in 1..4096";
     else if (!pts || !decode_status || !boxes || !out || !status) what = "NULL pointer";
     else if ((((size_t)pts) | ((size_t)out)) & 7) what = "pts and out must be 8-byte aligned";
     if (what) return failf(N3DT_EINVAL, "%s: %s", who, what);
@@ -1292,7 +1292,7 @@ static const char* head_mask_size(int n, int height, int width) {
 }
 
 static const char* head_mask_pixels(int n, int height, int width) {
-    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) return "height and width must be in 1..4096";
     if (n < 1 || (size_t)n * height * width > ((size_t)1 << 30)) return "n outside 1..2^30 / (height width)";
     return nullptr;
 }
@@ -1354,7 +1354,7 @@ extern "C" int n3dt_head_mask_fwd(int n, int height, int width, int n_classes, c
 static const char* head_mask_block_size(int block, int n, int height, int width, int src_height, int src_width) {
     if (block < 0 || block >= HM_BLOCKS) return "block outside 0..36";
     if (n < 1 || n > HM_MAX_IMAGES) return "n outside 1..1024";
-    if (height < 1 || width < 1 || height > SN_MAX_FRAME_HW || width > SN_MAX_FRAME_HW) return "height and width must be in 1..4096";
+    if (height < 1 || width < 1 || height > CN_MAX_FRAME_HW || width > CN_MAX_FRAME_HW) return "height and width must be in 1..4096";
     if (src_height < 1 || src_width < 1 || src_height > height || src_width > width) return "src_height and src_width must be in 1..height, 1..width";
     const bool resamples = block == HM_HEAD32 || block == HM_HEAD16;
     if (!resamples && (src_height != height || src_width != width)) return "only blocks 24 and 25 read through the nearest upsample";
@@ -1431,7 +1431,7 @@ extern "C" int n3dt_head_mask_labels(int n, int n_classes, int h, int w, int hei
     const char* what = head_mask_pixels(n, height, width);
     if (!what) {
         if (n_classes < 1 || n_classes > 256) what = "n_classes outside 1..256";
-        else if (h < 1 || w < 1 || h > SN_MAX_FRAME_HW || w > SN_MAX_FRAME_HW) what = "h and w must be in 1..4096";
+        else if (h < 1 || w < 1 || h > CN_MAX_FRAME_HW || w > CN_MAX_FRAME_HW) what = "h and w must be in 1..4096";
         else if (!logits || !labels) what = "NULL pointer";
         else if (((size_t)logits) & 3) what = "logits must be 4-byte aligned";
     }

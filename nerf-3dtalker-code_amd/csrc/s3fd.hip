@@ -21,6 +21,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "s3fd_core.h"
 #include "n3dt_launch.h"
 
@@ -77,11 +78,6 @@ __global__ __launch_bounds__(256) void s3fd_bias_kernel(const float* __restrict_
     if (n < np) dst[n] = n < c0 ? b0[n] : n < c0 + c1 ? b1[n - c0] : 0.0f;
 }
 
-__global__ __launch_bounds__(256) void s3fd_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 // ---- prologue and layouts ------------------------------------------------------------------------------------------------------
 // frames [n,3,H,W] fp32 RGB in [0,1] -> dst [n, H + 2 pad, W + 2 pad, 16]: channel c = 255 u - mean[c] with the Caffe means
 // (104, 117, 123) on R, G, B in that order (api.py:65 reverses BGR to RGB, detect.py:59 subtracts the BGR means: the
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(256) void s3fd_frames_kernel(const float* __restric
     const size_t total = (size_t)n * Hp * Wp, plane = (size_t)H * W;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         int img, yp, xp;
-        s3_cell(e, Hp, Wp, &img, &yp, &xp);
+        cn_cell(e, Hp, Wp, &img, &yp, &xp);
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad) {
             const double mean[3] = {104.0, 117.0, 123.0};
@@ -109,27 +105,12 @@ __global__ __launch_bounds__(256) void s3fd_frames_kernel(const float* __restric
     }
 }
 
-// src [n, C, H, W] -> dst [n, H + 2 pad, W + 2 pad, Cp]: zero in the halo and in channels C .. Cp - 1.  One thread per element.
-__global__ __launch_bounds__(256) void s3fd_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad, int Cp,
-                                                           float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * Hp * Wp * Cp;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % Cp);
-        int img, yp, xp;
-        s3_cell(e / Cp, Hp, Wp, &img, &yp, &xp);
-        float v = 0.0f;
-        if (c < C && xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad)
-            v = src[(((size_t)img * C + c) * H + (yp - pad)) * W + (xp - pad)];
-        dst[e] = v;
-    }
-}
+// the plain layouts [n,C,H,W] <-> padded NHWC are conv_net.hip's
 
-// channels c0 .. c0 + C - 1 of src [n, H + 2 pad, W + 2 pad, Cs] -> dst [n, C, H, W]; maxout: channel 0 = max(max(s0, s1), s2) and
-// channel 1 = s3 of the four source channels (net_s3fd.py:124-127)
-__global__ __launch_bounds__(256) void s3fd_to_nchw_kernel(const float* __restrict__ src, int n, int Cs, int c0, int C, int H, int W, int pad,
-                                                           int maxout, float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
+// level 1's confidences: src [n, H, W, Cs] (no halo) -> dst [n, 2, H, W], channel 0 = max(max(s0, s1), s2) and channel 1 = s3 of the
+// first four source channels (net_s3fd.py:124-127)
+__global__ __launch_bounds__(256) void s3fd_maxout_nchw_kernel(const float* __restrict__ src, int n, int Cs, int H, int W, float* __restrict__ dst) {
+    const int C = 2;
     const size_t total = (size_t)n * C * H * W;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int x = (int)(e % W);
@@ -137,11 +118,8 @@ __global__ __launch_bounds__(256) void s3fd_to_nchw_kernel(const float* __restri
         const int y = (int)(t % H);
         t /= H;
         const int c = (int)(t % C), img = (int)(t / C);
-        const float* s = src + (((size_t)img * Hp + (y + pad)) * Wp + (x + pad)) * Cs;
-        float v;
-        if (maxout) v = c == 0 ? fmaxf(fmaxf(s[0], s[1]), s[2]) : s[3];
-        else v = s[c0 + c];
-        dst[e] = v;
+        const float* s = src + (((size_t)img * H + y) * W + x) * Cs;
+        dst[e] = c == 0 ? fmaxf(fmaxf(s[0], s[1]), s[2]) : s[3];
     }
 }
 
@@ -155,25 +133,21 @@ struct S3ConvArgs {
     int n, Ho, Wo, Hp, Wp, Hq, Wq, cinp, np, cstore, k, stride, ioff, opad, relu;
 };
 
-// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M cells x 32 NT columns, the column tile fastest.
+// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes CN_TILE_M cells x 32 NT columns, the column tile fastest.
 // A k-step is 16 channels of one tap (cinp % 16 == 0).  Every dimension, stride and halo width is a run-time argument; the row
 // index is 64-bit (n Hq Wq reaches tens of millions at 512 x 512).
 template <int NT>
 __global__ __launch_bounds__(256) void s3fd_conv_kernel(S3ConvArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long Mq = (long long)a.n * a.Hq * a.Wq;
-    const int ntn = a.np / (32 * NT);
-    const long long tile = (long long)blockIdx.x * 4 + wave;
-    const long long m0 = tile / ntn * SN_TILE_M;
-    if (m0 >= Mq) return;  // no barriers in this kernel: an idle wave may leave
-    const int nt0 = (int)(tile % ntn) * NT;
+    const ConvWaveTile t = conv_wave_tile<NT>(a.np, a.n, a.Hq, a.Wq);
+    if (t.idle()) return;  // no barriers in this kernel: an idle wave may leave
+    const int lane = t.lane, r = t.r, h = t.h, nt0 = t.nt0(NT);
+    const long long Mq = t.M, m0 = t.m0;
     const float* base[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         int img, yq, xq;
-        sn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
-        const int y = sn_clampi(yq - a.opad, 0, a.Ho - 1), x = sn_clampi(xq - a.opad, 0, a.Wo - 1);
+        cn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
+        const int y = cn_clampi(yq - a.opad, 0, a.Ho - 1), x = cn_clampi(xq - a.opad, 0, a.Wo - 1);
         base[mt] = a.in + s3_field_base(img, y, x, a.stride, a.ioff, a.Hp, a.Wp, a.cinp);
     }
     conv_f32x16 acc[2][NT];
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(256) void s3fd_conv_kernel(S3ConvArgs a) {
 
     int s = 0;
     for (int tap = 0; tap < a.k * a.k; ++tap) {
-        const size_t toff = sn_tap_offset(tap, a.k, a.Wp, a.cinp) + 8 * h;
+        const size_t toff = cn_tap_offset(tap, a.k, a.Wp, a.cinp) + 8 * h;
         for (int c0 = 0; c0 < a.cinp; c0 += 16, ++s) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
@@ -199,8 +173,8 @@ __global__ __launch_bounds__(256) void s3fd_conv_kernel(S3ConvArgs a) {
             const long long m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= Mq) continue;
             int img, yq, xq;
-            sn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
-            const bool inside = sn_interior(yq, xq, a.Ho, a.Wo, a.opad);
+            cn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
+            const bool inside = cn_interior(yq, xq, a.Ho, a.Wo, a.opad);
             float* o = a.out + (size_t)m * a.cstore;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -227,9 +201,9 @@ __global__ __launch_bounds__(256) void s3fd_pool_kernel(const float* __restrict_
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int c = (int)(e % C4) * 4;
         int img, yq, xq;
-        s3_cell(e / C4, Hq, Wq, &img, &yq, &xq);
+        cn_cell(e / C4, Hq, Wq, &img, &yq, &xq);
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (sn_interior(yq, xq, Ho, Wo, opad)) {
+        if (cn_interior(yq, xq, Ho, Wo, opad)) {
             const float* p = in + s3_pool_base(img, yq - opad, xq - opad, Hi, Wi, ihalo, C) + c;
             const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + C);
             const float4 d = *reinterpret_cast<const float4*>(p + row), f = *reinterpret_cast<const float4*>(p + row + C);
@@ -250,9 +224,9 @@ __global__ __launch_bounds__(256) void s3fd_norm_kernel(const float* __restrict_
     const size_t total = (size_t)n * Hq * Wq;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         int img, yq, xq;
-        s3_cell(e, Hq, Wq, &img, &yq, &xq);
+        cn_cell(e, Hq, Wq, &img, &yq, &xq);
         float4* o = reinterpret_cast<float4*>(out + e * C);
-        if (!sn_interior(yq, xq, H, W, 1)) {
+        if (!cn_interior(yq, xq, H, W, 1)) {
             for (int c = 0; c < C / 4; ++c) o[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             continue;
         }
@@ -483,7 +457,7 @@ extern "C" void n3dt_launch_s3fd_pack(const N3dtS3fdParams* p, void* packed, hip
         s3fd_bias_kernel<<<(g.np + 255) / 256, 256, 0, st>>>(b0, c0, b1, c1, g.np, (float*)(base + L.bias[j]));
     }
     for (int l = 0; l < S3_NORMS; ++l)
-        s3fd_copy_kernel<<<(s3_level_c(l) + 255) / 256, 256, 0, st>>>(p->norm_weight[l], s3_level_c(l), (float*)(base + L.norm[l]));
+        conv_net_copy(p->norm_weight[l], (size_t)s3_level_c(l), (float*)(base + L.norm[l]), st);
 }
 
 static void s3_conv(int j, int n, int Hi, int Wi, const void* packed, const float* in, float* out, hipStream_t st) {
@@ -501,8 +475,8 @@ static void s3_conv(int j, int n, int Hi, int Wi, const void* packed, const floa
     a.cinp = g.cinp; a.np = g.np; a.cstore = g.cstore; a.k = g.k; a.stride = g.stride;
     a.ioff = g.ioff; a.opad = g.opad; a.relu = g.relu;
     const size_t Mq = (size_t)n * g.Hq * g.Wq;
-    const size_t mtiles = (Mq + SN_TILE_M - 1) / SN_TILE_M;
-    const int nt = s3_wave_ntiles(&g, n);
+    const size_t mtiles = (Mq + CN_TILE_M - 1) / CN_TILE_M;
+    const int nt = cn_wave_ntiles((long long)Mq, g.np);
     const size_t tiles = mtiles * (g.np / (32 * nt));
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     if (nt == 1) s3fd_conv_kernel<1><<<grid, 256, 0, st>>>(a);
@@ -570,14 +544,15 @@ extern "C" void n3dt_launch_s3fd_heads(int n, int H, int W, const void* packed, 
                                        hipStream_t st) {
     const S3Workspace w = s3_workspace(n, H, W);
     char* ws = (char*)workspace;
-    s3fd_to_nhwc_kernel<<<conv_grid((size_t)n * (H + 2) * (W + 2) * 16), 256, 0, st>>>(x, n, 3, H, W, 1, 16, (float*)(ws + w.map[0]));
+    conv_net_to_nhwc(x, n, 3, H, W, 1, 16, (float*)(ws + w.map[0]), 16, st);
     s3_chain(n, H, W, packed, ws, w, st);
     const S3Levels L = s3_levels(H, W, ws, w);
     for (int l = 0; l < S3_LEVELS; ++l) {
         const int cols = s3_level_cols(l), conf = s3_level_conf(l);
         const size_t px = (size_t)n * L.lh[l] * L.lw[l];
-        s3fd_to_nchw_kernel<<<conv_grid(px * 2), 256, 0, st>>>(L.head[l], n, cols, 0, 2, L.lh[l], L.lw[l], 0, l == 0, out[2 * l]);
-        s3fd_to_nchw_kernel<<<conv_grid(px * 4), 256, 0, st>>>(L.head[l], n, cols, conf, 4, L.lh[l], L.lw[l], 0, 0, out[2 * l + 1]);
+        if (l == 0) s3fd_maxout_nchw_kernel<<<conv_grid(px * 2), 256, 0, st>>>(L.head[l], n, cols, L.lh[l], L.lw[l], out[2 * l]);
+        else conv_net_to_nchw(L.head[l], cols, n, 2, L.lh[l], L.lw[l], 0, out[2 * l], st);
+        conv_net_to_nchw(L.head[l] + conf, cols, n, 4, L.lh[l], L.lw[l], 0, out[2 * l + 1], st);
     }
 }
 
@@ -644,28 +619,28 @@ static S3BlockShape s3_block_shape(int block, int Hi, int Wi) {
 
 extern "C" size_t n3dt_s3fd_block_ws_bytes(int block, int n, int Hi, int Wi) {
     const S3BlockShape b = s3_block_shape(block, Hi, Wi);
-    return s3_rup256((size_t)n * b.in_elems * sizeof(float)) + s3_rup256((size_t)n * b.out_elems * sizeof(float));
+    return cn_rup256((size_t)n * b.in_elems * sizeof(float)) + cn_rup256((size_t)n * b.out_elems * sizeof(float));
 }
 
 extern "C" void n3dt_launch_s3fd_block(int block, int n, int Hi, int Wi, const void* packed, const float* in, float* out, void* workspace,
                                        hipStream_t st) {
     const S3BlockShape b = s3_block_shape(block, Hi, Wi);
     float* map0 = (float*)workspace;
-    float* map1 = (float*)((char*)workspace + s3_rup256((size_t)n * b.in_elems * sizeof(float)));
+    float* map1 = (float*)((char*)workspace + cn_rup256((size_t)n * b.in_elems * sizeof(float)));
     if (block < S3_FIRST_POOL || block >= S3_FIRST_HEAD) {
         const int j = block < S3_FIRST_POOL ? block : S3_CONVS + block - S3_FIRST_HEAD;
         const S3Geom g = s3_gemm_geom(j, Hi, Wi);
-        s3fd_to_nhwc_kernel<<<conv_grid(s3_in_elems(&g, n)), 256, 0, st>>>(in, n, g.cin, Hi, Wi, g.ihalo, g.cinp, map0);
+        conv_net_to_nhwc(in, n, g.cin, Hi, Wi, g.ihalo, g.cinp, map0, g.cinp, st);
         s3_conv(j, n, Hi, Wi, packed, map0, map1, st);
-        s3fd_to_nchw_kernel<<<conv_grid((size_t)n * g.cstore * g.Ho * g.Wo), 256, 0, st>>>(map1, n, g.cstore, 0, g.cstore, g.Ho, g.Wo, g.opad, 0, out);
+        conv_net_to_nchw(map1, g.cstore, n, g.cstore, g.Ho, g.Wo, g.opad, out, st);
     } else if (block < S3_FIRST_NORM) {
         const int op = b.opad;
-        s3fd_to_nhwc_kernel<<<conv_grid((size_t)n * b.in_elems), 256, 0, st>>>(in, n, b.cin, Hi, Wi, 0, b.cin, map0);
+        conv_net_to_nhwc(in, n, b.cin, Hi, Wi, 0, b.cin, map0, b.cin, st);
         s3_pool(n, Hi, Wi, 0, b.cin, op, map0, map1, st);
-        s3fd_to_nchw_kernel<<<conv_grid((size_t)n * b.cout * b.Ho * b.Wo), 256, 0, st>>>(map1, n, b.cout, 0, b.cout, b.Ho, b.Wo, op, 0, out);
+        conv_net_to_nchw(map1, b.cout, n, b.cout, b.Ho, b.Wo, op, out, st);
     } else {
-        s3fd_to_nhwc_kernel<<<conv_grid((size_t)n * b.in_elems), 256, 0, st>>>(in, n, b.cin, Hi, Wi, 0, b.cin, map0);
+        conv_net_to_nhwc(in, n, b.cin, Hi, Wi, 0, b.cin, map0, b.cin, st);
         s3_norm(block - S3_FIRST_NORM, n, Hi, Wi, packed, map0, map1, st);
-        s3fd_to_nchw_kernel<<<conv_grid((size_t)n * b.cout * Hi * Wi), 256, 0, st>>>(map1, n, b.cout, 0, b.cout, Hi, Wi, 1, 0, out);
+        conv_net_to_nchw(map1, b.cout, n, b.cout, Hi, Wi, 1, out, st);
     }
 }

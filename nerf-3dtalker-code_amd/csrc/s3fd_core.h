@@ -4,7 +4,7 @@
  *
  * Included by csrc/s3fd.hip, whose kernels take their sizes and addresses from the functions below, and by
  * tests/s3fd_core_host.cpp, which walks the same functions over the kernels' grids on the CPU under the address and
- * undefined-behaviour sanitizers.  The rows of the implicit GEMM, the halo test and the tap offsets are syncnet_core.h's; the
+ * undefined-behaviour sanitizers.  The rows of the implicit GEMM, the halo test, the tap offsets and the wave-tile rule are conv_net_core.h's; the
  * fragment arithmetic is conv_frag.h's.  Compiles as host C++ on its own.
  *
  * Blocks.  33 of them: 0..18 the backbone convolutions in state-dict order (conv1_1 .. conv7_2), 19..23 the five 2 x 2 / 2 max
@@ -20,7 +20,7 @@
 
 #include <math.h>
 
-#include "syncnet_core.h"
+#include "conv_net_core.h"
 
 #define S3_CONVS 19
 #define S3_POOLS 5
@@ -72,10 +72,10 @@ static const S3Conv S3_TABLE[S3_CONVS] = {
 
 /* the convolution whose output is level l's (0..5) source, that source's channels, and the conf head's channels */
 static const int S3_LEVEL_CONV[S3_LEVELS] = {6, 9, 12, 14, 16, 18};
-SN_HD int s3_level_c(int l) { return l == 0 ? 256 : l == 3 ? 1024 : l == 5 ? 256 : 512; }
-SN_HD int s3_level_conf(int l) { return l == 0 ? 4 : 2; }
-SN_HD int s3_level_cols(int l) { return s3_level_conf(l) + 4; } /* stored columns of the head pair's 32 */
-SN_HD int s3_level_stride(int l) { return 4 << l; }
+CN_HD int s3_level_c(int l) { return l == 0 ? 256 : l == 3 ? 1024 : l == 5 ? 256 : 512; }
+CN_HD int s3_level_conf(int l) { return l == 0 ? 4 : 2; }
+CN_HD int s3_level_cols(int l) { return s3_level_conf(l) + 4; } /* stored columns of the head pair's 32 */
+CN_HD int s3_level_stride(int l) { return 4 << l; }
 
 /* halo of convolution c's input and output maps in the chain */
 static inline int s3_conv_ohalo(int c) {
@@ -99,8 +99,8 @@ static inline S3Geom s3_geom_make(int Hi, int Wi, int cin, int np, int cstore, i
     S3Geom g;
     g.Hi = Hi;
     g.Wi = Wi;
-    g.Ho = sn_conv_out(Hi, k, stride, pad);
-    g.Wo = sn_conv_out(Wi, k, stride, pad);
+    g.Ho = cn_conv_out(Hi, k, stride, pad);
+    g.Wo = cn_conv_out(Wi, k, stride, pad);
     g.ihalo = ihalo;
     g.ioff = ihalo - pad;
     g.opad = opad;
@@ -109,7 +109,7 @@ static inline S3Geom s3_geom_make(int Hi, int Wi, int cin, int np, int cstore, i
     g.Hq = g.Ho + 2 * opad;
     g.Wq = g.Wo + 2 * opad;
     g.cin = cin;
-    g.cinp = sn_round16(cin);
+    g.cinp = cn_round16(cin);
     g.np = np;
     g.cstore = cstore;
     g.k = k;
@@ -132,12 +132,6 @@ static inline S3Geom s3_gemm_geom(int j, int Hi, int Wi) {
 static inline size_t s3_in_elems(const S3Geom* g, int n) { return (size_t)n * g->Hp * g->Wp * g->cinp; }
 static inline size_t s3_out_elems(const S3Geom* g, int n) { return (size_t)n * g->Hq * g->Wq * g->cstore; }
 
-/* 32-column tiles per wave: one where the matrix is 32 wide, and where two would leave fewer than 1024 waves; else two */
-static inline int s3_wave_ntiles(const S3Geom* g, int n) {
-    const size_t mtiles = ((size_t)n * g->Hq * g->Wq + SN_TILE_M - 1) / SN_TILE_M;
-    return (g->np % 64 != 0 || mtiles * (size_t)(g->np / 64) < 1024) ? 1 : 2;
-}
-
 /* every map's size from the frame's (H, W): h[c] x w[c] the input of convolution c, lh[l] x lw[l] detection level l */
 typedef struct S3Sizes {
     int h[S3_CONVS], w[S3_CONVS], lh[S3_LEVELS], lw[S3_LEVELS];
@@ -149,8 +143,8 @@ static inline S3Sizes s3_sizes(int H, int W) {
         const S3Conv t = S3_TABLE[c];
         s.h[c] = H;
         s.w[c] = W;
-        H = sn_conv_out(H, t.k, t.stride, t.pad);
-        W = sn_conv_out(W, t.k, t.stride, t.pad);
+        H = cn_conv_out(H, t.k, t.stride, t.pad);
+        W = cn_conv_out(W, t.k, t.stride, t.pad);
         if (t.level) {
             s.lh[t.level - 1] = H;
             s.lw[t.level - 1] = W;
@@ -163,7 +157,7 @@ static inline S3Sizes s3_sizes(int H, int W) {
     return s;
 }
 
-SN_HD int s3_hw_ok(int H, int W) { return H >= S3_MIN_HW && W >= S3_MIN_HW && H <= SN_MAX_FRAME_HW && W <= SN_MAX_FRAME_HW; }
+CN_HD int s3_hw_ok(int H, int W) { return H >= S3_MIN_HW && W >= S3_MIN_HW && H <= CN_MAX_FRAME_HW && W <= CN_MAX_FRAME_HW; }
 
 /* head positions over the six levels, level-major, then y, then x; first[l] = the first position of level l, first[6] = P */
 static inline int s3_positions(const S3Sizes* s, int first[S3_LEVELS + 1]) {
@@ -182,8 +176,6 @@ static inline int s3_positions(const S3Sizes* s, int first[S3_LEVELS + 1]) {
 typedef struct S3Workspace {
     size_t map[2], norm, head[S3_LEVELS], score, box, sup, total;
 } S3Workspace;
-
-static inline size_t s3_rup256(size_t x) { return (x + 255) / 256 * 256; }
 
 static inline size_t s3_max_map_elems(const S3Sizes* s) {
     size_t m = 0;
@@ -205,7 +197,7 @@ static inline S3Workspace s3_workspace(int n, int H, int W) {
     const size_t mm = s3_max_map_elems(&s);
     for (int i = 0; i < 2; ++i) {
         w.map[i] = off;
-        off += s3_rup256((size_t)n * mm * sizeof(float));
+        off += cn_rup256((size_t)n * mm * sizeof(float));
     }
     size_t nm = 0;
     for (int l = 0; l < S3_NORMS; ++l) {
@@ -213,18 +205,18 @@ static inline S3Workspace s3_workspace(int n, int H, int W) {
         if (e > nm) nm = e;
     }
     w.norm = off;
-    off += s3_rup256((size_t)n * nm * sizeof(float));
+    off += cn_rup256((size_t)n * nm * sizeof(float));
     for (int l = 0; l < S3_LEVELS; ++l) {
         w.head[l] = off;
-        off += s3_rup256((size_t)n * s.lh[l] * s.lw[l] * s3_level_cols(l) * sizeof(float));
+        off += cn_rup256((size_t)n * s.lh[l] * s.lw[l] * s3_level_cols(l) * sizeof(float));
     }
     const size_t P = (size_t)s3_positions(&s, 0);
     w.score = off;
-    off += s3_rup256((size_t)n * P * sizeof(double));
+    off += cn_rup256((size_t)n * P * sizeof(double));
     w.box = off;
-    off += s3_rup256((size_t)n * P * 4 * sizeof(double));
+    off += cn_rup256((size_t)n * P * 4 * sizeof(double));
     w.sup = off;
-    off += s3_rup256((size_t)n * P);
+    off += cn_rup256((size_t)n * P);
     w.total = off;
     return w;
 }
@@ -240,26 +232,18 @@ static inline int s3_max_images(int H, int W) {
 
 /* ---- addresses -------------------------------------------------------------------------------------------------------------------
  * first element of the receptive field of output pixel (img, y, x) in the padded NHWC input [n, Hp, Wp, cinp] read at offset ioff */
-SN_HD size_t s3_field_base(int img, int y, int x, int stride, int ioff, int Hp, int Wp, int cinp) {
+CN_HD size_t s3_field_base(int img, int y, int x, int stride, int ioff, int Hp, int Wp, int cinp) {
     return (((size_t)img * Hp + (size_t)y * stride + ioff) * Wp + (size_t)x * stride + ioff) * cinp;
 }
 
 /* the pool: output pixel (y, x) of [n, Ho, Wo] = floor(Hi / 2) x floor(Wi / 2) takes input pixels (2 y + dy, 2 x + dx) of a map
  * [n, Hi + 2 ihalo, Wi + 2 ihalo, C]; where pixel (2 y, 2 x) begins */
-SN_HD size_t s3_pool_base(int img, int y, int x, int Hi, int Wi, int ihalo, int C) {
+CN_HD size_t s3_pool_base(int img, int y, int x, int Hi, int Wi, int ihalo, int C) {
     return (((size_t)img * (Hi + 2 * ihalo) + (size_t)(2 * y + ihalo)) * (Wi + 2 * ihalo) + (size_t)(2 * x + ihalo)) * C;
 }
 
-/* cell e of a padded map [n, Hq, Wq] -> (img, yq, xq) */
-SN_HD void s3_cell(size_t e, int Hq, int Wq, int* img, int* yq, int* xq) {
-    *xq = (int)(e % (size_t)Wq);
-    const size_t t = e / (size_t)Wq;
-    *yq = (int)(t % (size_t)Hq);
-    *img = (int)(t / (size_t)Hq);
-}
-
 /* position p (0 .. P - 1) -> level, y, x */
-SN_HD void s3_position(int p, const int* first, const int* lw, int* l, int* y, int* x) {
+CN_HD void s3_position(int p, const int* first, const int* lw, int* l, int* y, int* x) {
     int lv = 0;
     while (lv + 1 < S3_LEVELS && p >= first[lv + 1]) ++lv;
     const int r = p - first[lv];
@@ -270,7 +254,7 @@ SN_HD void s3_position(int p, const int* first, const int* lw, int* l, int* y, i
 
 /* ---- the tail's arithmetic, float64 --------------------------------------------------------------------------------------------
  * bbox.py:104-108 literally: prior (stride / 2 + x stride, stride / 2 + y stride, 4 stride, 4 stride), variances 0.1 / 0.2 */
-SN_HD void s3_decode(int stride, int y, int x, const double loc[4], double box[4]) {
+CN_HD void s3_decode(int stride, int y, int x, const double loc[4], double box[4]) {
     const double pcx = (double)stride / 2 + (double)x * stride, pcy = (double)stride / 2 + (double)y * stride, ps = (double)stride * 4;
     double cx = pcx + loc[0] * 0.1 * ps, cy = pcy + loc[1] * 0.1 * ps;
     const double w = ps * exp(loc[2] * 0.2), h = ps * exp(loc[3] * 0.2);
@@ -283,14 +267,14 @@ SN_HD void s3_decode(int stride, int y, int x, const double loc[4], double box[4
 }
 
 /* F.softmax over (c0, c1), channel 1 */
-SN_HD double s3_score(double c0, double c1) {
+CN_HD double s3_score(double c0, double c1) {
     const double m = c0 > c1 ? c0 : c1;
     const double e0 = exp(c0 - m), e1 = exp(c1 - m);
     return e1 / (e0 + e1);
 }
 
 /* bbox.py:44-64: the overlap of boxes a and b with the +1 areas */
-SN_HD double s3_overlap(const double* a, const double* b) {
+CN_HD double s3_overlap(const double* a, const double* b) {
     const double aa = (a[2] - a[0] + 1) * (a[3] - a[1] + 1), ab = (b[2] - b[0] + 1) * (b[3] - b[1] + 1);
     const double xx1 = a[0] > b[0] ? a[0] : b[0], yy1 = a[1] > b[1] ? a[1] : b[1];
     const double xx2 = a[2] < b[2] ? a[2] : b[2], yy2 = a[3] < b[3] ? a[3] : b[3];
@@ -302,7 +286,7 @@ SN_HD double s3_overlap(const double* a, const double* b) {
 
 /* ---- crop boxes ------------------------------------------------------------------------------------------------------------------
  * api.py:74-76 and data_loader_xgaze_new.py:156-159: clip at 0, truncate, pad, clamp to the frame -> (x1, y1, x2, y2) */
-SN_HD void s3_pad_box(const double* det, int H, int W, const int* pads, int* out) {
+CN_HD void s3_pad_box(const double* det, int H, int W, const int* pads, int* out) {
     int r[4];
     for (int i = 0; i < 4; ++i) {
         double v = det[i];
@@ -319,7 +303,7 @@ SN_HD void s3_pad_box(const double* det, int H, int W, const int* pads, int* out
 
 /* get_smoothened_boxes: entry i's window [*a, *b) of F boxes.  i + T <= F: [i, i + T).  Else boxes[F - T:], whose negative
  * start numpy counts from the end: [max(0, 2 F - T), F) where F < T. */
-SN_HD void s3_smooth_window(int i, int F, int T, int* a, int* b) {
+CN_HD void s3_smooth_window(int i, int F, int T, int* a, int* b) {
     if (i + T > F) {
         int s = F - T;
         if (s < 0) s = F + s < 0 ? 0 : F + s;
@@ -332,6 +316,6 @@ SN_HD void s3_smooth_window(int i, int F, int T, int* a, int* b) {
 }
 
 /* the mean of integers assigned into an integer array: the sum over the length, truncated toward zero */
-SN_HD int s3_trunc_mean(long long sum, int len) { return (int)(sum / len); }
+CN_HD int s3_trunc_mean(long long sum, int len) { return (int)(sum / len); }
 
 #endif

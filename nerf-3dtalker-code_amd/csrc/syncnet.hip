@@ -23,6 +23,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "syncnet_core.h"
 #include "n3dt_launch.h"
 
@@ -51,32 +52,8 @@ static SnPackLayout sn_layout() {
     return L;
 }
 
-// batch norm folded in float64: s = gamma / sqrt(var + eps), w' = fp32(w s), b' = fp32((b - mean) s + beta)
-__device__ __forceinline__ double sn_bn_scale(const float* gamma, const float* var, int n) {
-    return (double)gamma[n] / sqrt((double)var[n] + SN_BN_EPS);
-}
-
-__global__ __launch_bounds__(256) void syncnet_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
-                                                           const float* __restrict__ var, int cin, int cinp, int cout, int taps, int K,
-                                                           __bf16* __restrict__ hi, __bf16* __restrict__ lo) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)K * cout) return;
-    int k, n;
-    cf_pack_decode(e, cout / 32, &k, &n);
-    const int tap = k / cinp, ci = k - tap * cinp;
-    float w = 0.0f;
-    if (ci < cin) w = (float)((double)W[((size_t)n * cin + ci) * taps + tap] * sn_bn_scale(gamma, var, n));
-    const __bf16 h = (__bf16)w;
-    hi[e] = h;
-    lo[e] = conv_lo(w, h);
-}
-
-__global__ __launch_bounds__(256) void syncnet_bias_kernel(const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, int cout, float* __restrict__ dst) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n < cout) dst[n] = (float)(((double)bias[n] - (double)mean[n]) * sn_bn_scale(gamma, var, n) + (double)beta[n]);
-}
+// batch norm folded in float64 by conv_net.hip's pack and bias kernels: s = gamma / sqrt(var + eps), w' = fp32(w s),
+// b' = fp32((b - mean) s + beta)
 
 // ---- face-window prologue ------------------------------------------------------------------------------------------------------
 // one thread per element of faces [n, 15, 48, 96].  boxes: [n + 4, 4] or, with box_stride 0, one box for every frame.
@@ -92,11 +69,11 @@ __global__ __launch_bounds__(256) void syncnet_faces_kernel(int n, int height, i
         const int ch = (int)(t % SN_FACE_C), win = (int)(t / SN_FACE_C);
         const int frame = win + ch / 3, c = 2 - ch % 3;  // BGR: output channel 0 is the frame's blue
         int y1, h, x1, w;
-        sn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
+        cn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
         int ya, yb, xa, xb;
         double wy, wx;
-        sn_bilinear(SN_CROP - SN_FACE_H + y, h, SN_CROP, &ya, &yb, &wy);
-        sn_bilinear(x, w, SN_CROP, &xa, &xb, &wx);
+        cn_bilinear(SN_CROP - SN_FACE_H + y, h, SN_CROP, &ya, &yb, &wy);
+        cn_bilinear(x, w, SN_CROP, &xa, &xb, &wx);
         const float* src = frames + ((size_t)frame * 3 + c) * plane;
         double v[4];
         const size_t at[4] = {(size_t)(y1 + ya) * width + (x1 + xa), (size_t)(y1 + ya) * width + (x1 + xb),
@@ -113,39 +90,7 @@ __global__ __launch_bounds__(256) void syncnet_faces_kernel(int n, int height, i
     }
 }
 
-// ---- layouts -------------------------------------------------------------------------------------------------------------------
-// src [n, C, H, W] -> dst [n, H + 2 pad, W + 2 pad, Cp]: zero in the halo and in channels C .. Cp - 1.  One thread per element.
-__global__ __launch_bounds__(256) void syncnet_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad, int Cp,
-                                                              float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * Hp * Wp * Cp;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % Cp);
-        size_t t = e / Cp;
-        const int xp = (int)(t % Wp);
-        t /= Wp;
-        const int yp = (int)(t % Hp), img = (int)(t / Hp);
-        float v = 0.0f;
-        if (c < C && xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad)
-            v = src[(((size_t)img * C + c) * H + (yp - pad)) * W + (xp - pad)];
-        dst[e] = v;
-    }
-}
-
-// src [n, H + 2 pad, W + 2 pad, C] -> dst [n, C, H, W]
-__global__ __launch_bounds__(256) void syncnet_to_nchw_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad,
-                                                              float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * C * H * W;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int x = (int)(e % W);
-        size_t t = e / W;
-        const int y = (int)(t % H);
-        t /= H;
-        const int c = (int)(t % C), img = (int)(t / C);
-        dst[e] = src[(((size_t)img * Hp + (y + pad)) * Wp + (x + pad)) * C + c];
-    }
-}
+// layouts: conv_net.hip's -- [n,C,H,W] -> NHWC with C padded to 16 and the first block's zero halo, and back
 
 // ---- implicit-GEMM convolution ---------------------------------------------------------------------------------------------------
 struct SnConvArgs {
@@ -157,25 +102,21 @@ struct SnConvArgs {
     int n, Ho, Wo, Hp, Wp, Hq, Wq, cinp, cout, kh, kw, sh, sw, ipad, opad, residual;
 };
 
-// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes SN_TILE_M cells x 32 NT channels: the tiles are numbered with
+// 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave computes CN_TILE_M cells x 32 NT channels: the tiles are numbered with
 // the channel tile fastest, so the waves of a workgroup share their rows where C_out has several tiles, and a map of a few cells
 // still spreads over C_out / (32 NT) waves.  A k-step is 16 channels of one tap (cinp % 16 == 0).
 template <int NT>
 __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long Mq = (long long)a.n * a.Hq * a.Wq;
-    const int ntn = a.cout / (32 * NT);
-    const long long tile = (long long)blockIdx.x * 4 + wave;
-    const long long m0 = tile / ntn * SN_TILE_M;
-    if (m0 >= Mq) return;  // no barriers in this kernel: an idle wave may leave
-    const int nt0 = (int)(tile % ntn) * NT;
+    const ConvWaveTile t = conv_wave_tile<NT>(a.cout, a.n, a.Hq, a.Wq);
+    if (t.idle()) return;  // no barriers in this kernel: an idle wave may leave
+    const int lane = t.lane, r = t.r, h = t.h, nt0 = t.nt0(NT);
+    const long long Mq = t.M, m0 = t.m0;
     const float* base[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         int img, yq, xq;
-        sn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
-        const int y = sn_clampi(yq - a.opad, 0, a.Ho - 1), x = sn_clampi(xq - a.opad, 0, a.Wo - 1);
+        cn_row_cell(m0 + mt * 32 + r, Mq, a.Hq, a.Wq, &img, &yq, &xq);  // rows past Mq compute the last cell again and are never stored
+        const int y = cn_clampi(yq - a.opad, 0, a.Ho - 1), x = cn_clampi(xq - a.opad, 0, a.Wo - 1);
         base[mt] = a.in + sn_field_base(img, y, x, a.sh, a.sw, a.Hp, a.Wp, a.cinp);
     }
     conv_f32x16 acc[2][NT];
@@ -184,7 +125,7 @@ __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
 
     int s = 0;
     for (int tap = 0; tap < a.kh * a.kw; ++tap) {
-        const size_t toff = sn_tap_offset(tap, a.kw, a.Wp, a.cinp) + 8 * h;
+        const size_t toff = cn_tap_offset(tap, a.kw, a.Wp, a.cinp) + 8 * h;
         for (int c0 = 0; c0 < a.cinp; c0 += 16, ++s) {
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) conv_load8(base[mt] + toff + c0, av[mt]);
@@ -201,8 +142,8 @@ __global__ __launch_bounds__(256) void syncnet_conv_kernel(SnConvArgs a) {
             const long long m = m0 + mt * 32 + cf_acc_row(i, h);
             if (m >= Mq) continue;
             int img, yq, xq;
-            sn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
-            const bool inside = sn_interior(yq, xq, a.Ho, a.Wo, a.opad);
+            cn_row_cell(m, Mq, a.Hq, a.Wq, &img, &yq, &xq);
+            const bool inside = cn_interior(yq, xq, a.Ho, a.Wo, a.opad);
             float* o = a.out + (size_t)m * a.cout;
             const float* res = nullptr;
             if (inside && a.residual) res = a.in + sn_residual_pixel(img, yq - a.opad, xq - a.opad, a.Hp, a.Wp, a.ipad, a.cinp);
@@ -277,10 +218,9 @@ extern "C" void n3dt_launch_syncnet_pack(const N3dtSyncnetParams* p, void* packe
         const SnGeom g = sn_geom(b);
         __bf16* hi = (__bf16*)(base + L.w[b]);
         const size_t n = L.elems[b];
-        syncnet_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p->weight[b], p->bn_weight[b], p->bn_var[b], SN_TABLE[b].cin, g.cinp,
-                                                                         g.cout, g.kh * g.kw, g.K, hi, hi + n);
-        syncnet_bias_kernel<<<(g.cout + 255) / 256, 256, 0, st>>>(p->bias[b], p->bn_weight[b], p->bn_bias[b], p->bn_mean[b], p->bn_var[b], g.cout,
-                                                                  (float*)(base + L.bias[b]));
+        conv_net_pack(p->weight[b], p->bn_weight[b], p->bn_var[b], SN_BN_EPS, SN_TABLE[b].cin, SN_TABLE[b].cin, g.cinp, g.cout, g.cout, g.kh * g.kw, g.K,
+                      0, hi, hi + n, st);
+        conv_net_bias_bn(p->bias[b], p->bn_weight[b], p->bn_bias[b], p->bn_mean[b], p->bn_var[b], SN_BN_EPS, g.cout, (float*)(base + L.bias[b]), st);
     }
 }
 
@@ -304,8 +244,8 @@ static void sn_conv(int block, int n, const void* packed, const float* in, float
     a.cinp = g.cinp; a.cout = g.cout; a.kh = g.kh; a.kw = g.kw; a.sh = g.sh; a.sw = g.sw;
     a.ipad = g.ipad; a.opad = g.opad; a.residual = g.residual;
     const size_t Mq = (size_t)n * g.Hq * g.Wq;
-    const size_t mtiles = (Mq + SN_TILE_M - 1) / SN_TILE_M;
-    const int nt = sn_wave_ntiles(&g, n);
+    const size_t mtiles = (Mq + CN_TILE_M - 1) / CN_TILE_M;
+    const int nt = cn_wave_ntiles((long long)Mq, g.cout);
     const size_t tiles = mtiles * (g.cout / (32 * nt));
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     if (nt == 1) syncnet_conv_kernel<1><<<grid, 256, 0, st>>>(a);
@@ -315,7 +255,7 @@ static void sn_conv(int block, int n, const void* packed, const float* in, float
 // blocks first .. last on `src` [n, C, H, W]; the last block's output (halo 0) goes to `final`
 static void sn_encoder(int first, int last, int n, const void* packed, const float* src, float* map0, float* map1, float* final, hipStream_t st) {
     const SnGeom g0 = sn_geom(first);
-    syncnet_to_nhwc_kernel<<<conv_grid(sn_in_elems(&g0, n)), 256, 0, st>>>(src, n, SN_TABLE[first].cin, g0.Hi, g0.Wi, g0.ipad, g0.cinp, map0);
+    conv_net_to_nhwc(src, n, SN_TABLE[first].cin, g0.Hi, g0.Wi, g0.ipad, g0.cinp, map0, g0.cinp, st);
     float* in = map0;
     float* out = map1;
     for (int b = first; b <= last; ++b) {
@@ -348,7 +288,7 @@ extern "C" void n3dt_launch_syncnet_block(int block, int n, const void* packed, 
     char* ws = (char*)workspace;
     float* map0 = (float*)(ws + w.map[0]);
     float* map1 = (float*)(ws + w.map[1]);
-    syncnet_to_nhwc_kernel<<<conv_grid(sn_in_elems(&g, n)), 256, 0, st>>>(in, n, SN_TABLE[block].cin, g.Hi, g.Wi, g.ipad, g.cinp, map0);
+    conv_net_to_nhwc(in, n, SN_TABLE[block].cin, g.Hi, g.Wi, g.ipad, g.cinp, map0, g.cinp, st);
     sn_conv(block, n, packed, map0, map1, st);
-    syncnet_to_nchw_kernel<<<conv_grid((size_t)n * g.cout * g.Ho * g.Wo), 256, 0, st>>>(map1, n, g.cout, g.Ho, g.Wo, g.opad, out);
+    conv_net_to_nchw(map1, g.cout, n, g.cout, g.Ho, g.Wo, g.opad, out, st);
 }

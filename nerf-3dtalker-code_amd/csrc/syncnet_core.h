@@ -5,8 +5,9 @@
  * Included by csrc/syncnet.hip, whose convolution, layout and prologue kernels take their addresses from the functions below, and
  * by tests/syncnet_core_host.cpp, which walks the very same functions over the convolution kernel's grid on the CPU (under the
  * address and undefined-behaviour sanitizers) for all 31 blocks.  The weight pack's fragment arithmetic and the epilogue's
- * register -> row map are conv_frag.h's, shared with the other convolutions and walked by the same program; the block / wave /
- * lane / K-step nest of the convolution kernel is re-typed there.  Compiles as host C++ on its own; the __host__ __device__
+ * register -> row map are conv_frag.h's, the rows of the GEMM, the halo test, tap offsets, the crop prologue's resample and the
+ * wave-tile rule conv_net_core.h's, shared with the other networks and walked by the same program; the block / wave / lane /
+ * K-step nest of the convolution kernel is re-typed there.  Compiles as host C++ on its own; the __host__ __device__
  * qualifiers exist only under hipcc.
  *
  * Maps.  Every activation is NHWC fp32 with C a multiple of 16 (the two first blocks' 15 and 1 input channels are padded with
@@ -19,11 +20,7 @@
 
 #include <stddef.h>
 
-#ifdef __HIPCC__
-#define SN_HD __host__ __device__ static inline
-#else
-#define SN_HD static inline
-#endif
+#include "conv_net_core.h"
 
 #define SN_BLOCKS 31
 #define SN_FACE_BLOCKS 17      /* blocks 0..16: the face encoder; 17..30: the audio encoder */
@@ -36,8 +33,6 @@
 #define SN_MEL_H 80
 #define SN_MEL_W 16
 #define SN_MAX_WINDOWS 1024
-#define SN_MAX_FRAME_HW 4096
-#define SN_TILE_M 64           /* output cells per wave */
 #define SN_BN_EPS 1e-5
 
 /* C_in, C_out, kernel (h, w), stride (h, w), padding, residual */
@@ -81,9 +76,6 @@ static const SnBlock SN_TABLE[SN_BLOCKS] = {
     {512, 512, 1, 1, 1, 1, 0, 0},
 };
 
-SN_HD int sn_round16(int c) { return (c + 15) / 16 * 16; }
-SN_HD int sn_conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
-
 /* one block's maps: input [n, Hp, Wp, cinp] with halo ipad (its own padding), output [n, Hq, Wq, cout] with halo opad (the next
  * block's padding; 0 behind the last block of an encoder).  K = kh kw cinp is a multiple of 16. */
 typedef struct SnGeom {
@@ -95,22 +87,22 @@ static inline SnGeom sn_geom(int block) {
     const int last = block < SN_FACE_BLOCKS ? SN_FACE_BLOCKS - 1 : SN_BLOCKS - 1;
     int H = block < SN_FACE_BLOCKS ? SN_FACE_H : SN_MEL_H, W = block < SN_FACE_BLOCKS ? SN_FACE_W : SN_MEL_W;
     for (int b = first; b < block; ++b) {
-        H = sn_conv_out(H, SN_TABLE[b].kh, SN_TABLE[b].sh, SN_TABLE[b].pad);
-        W = sn_conv_out(W, SN_TABLE[b].kw, SN_TABLE[b].sw, SN_TABLE[b].pad);
+        H = cn_conv_out(H, SN_TABLE[b].kh, SN_TABLE[b].sh, SN_TABLE[b].pad);
+        W = cn_conv_out(W, SN_TABLE[b].kw, SN_TABLE[b].sw, SN_TABLE[b].pad);
     }
     const SnBlock t = SN_TABLE[block];
     SnGeom g;
     g.Hi = H;
     g.Wi = W;
-    g.Ho = sn_conv_out(H, t.kh, t.sh, t.pad);
-    g.Wo = sn_conv_out(W, t.kw, t.sw, t.pad);
+    g.Ho = cn_conv_out(H, t.kh, t.sh, t.pad);
+    g.Wo = cn_conv_out(W, t.kw, t.sw, t.pad);
     g.ipad = t.pad;
     g.opad = block == last ? 0 : SN_TABLE[block + 1].pad;
     g.Hp = H + 2 * g.ipad;
     g.Wp = W + 2 * g.ipad;
     g.Hq = g.Ho + 2 * g.opad;
     g.Wq = g.Wo + 2 * g.opad;
-    g.cinp = sn_round16(t.cin);
+    g.cinp = cn_round16(t.cin);
     g.cout = t.cout;
     g.kh = t.kh;
     g.kw = t.kw;
@@ -124,12 +116,6 @@ static inline SnGeom sn_geom(int block) {
 static inline size_t sn_in_elems(const SnGeom* g, int n) { return (size_t)n * g->Hp * g->Wp * g->cinp; }
 static inline size_t sn_out_elems(const SnGeom* g, int n) { return (size_t)n * g->Hq * g->Wq * g->cout; }
 
-/* 32-column tiles per wave: one where C_out is 32, and where two would leave fewer than 1024 waves; else two */
-static inline int sn_wave_ntiles(const SnGeom* g, int n) {
-    const size_t mtiles = ((size_t)n * g->Hq * g->Wq + SN_TILE_M - 1) / SN_TILE_M;
-    return (g->cout == 32 || mtiles * (size_t)(g->cout / 64) < 1024) ? 1 : 2;
-}
-
 /* the largest map any block reads or writes, per window */
 static inline size_t sn_max_map_elems(void) {
     size_t m = 0;
@@ -142,58 +128,15 @@ static inline size_t sn_max_map_elems(void) {
     return m;
 }
 
-/* ---- rows of the implicit GEMM -------------------------------------------------------------------------------------------------
- * Row m of Mq = n * Hq * Wq is cell (img, yq, xq) of the padded output map, stored at out + m * cout.  Rows past Mq compute row
- * Mq - 1 again and are never stored. */
-SN_HD void sn_row_cell(long long m, long long Mq, int Hq, int Wq, int* img, int* yq, int* xq) {
-    if (m > Mq - 1) m = Mq - 1;
-    const long long hw = (long long)Hq * Wq;
-    *img = (int)(m / hw);
-    const int rem = (int)(m - (long long)*img * hw);
-    *yq = rem / Wq;
-    *xq = rem - *yq * Wq;
-}
-
-SN_HD int sn_interior(int yq, int xq, int Ho, int Wo, int opad) { return yq >= opad && yq < Ho + opad && xq >= opad && xq < Wo + opad; }
-
-/* a halo cell computes the nearest output pixel (and stores 0) */
-SN_HD int sn_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-/* first element of the receptive field of output pixel (img, y, x) in the padded NHWC input [n, Hp, Wp, cinp] */
-SN_HD size_t sn_field_base(int img, int y, int x, int sh, int sw, int Hp, int Wp, int cinp) {
+/* ---- addresses (the rows of the implicit GEMM, the halo test and the tap offsets are conv_net_core.h's) ----------------------------
+ * first element of the receptive field of output pixel (img, y, x) in the padded NHWC input [n, Hp, Wp, cinp] */
+CN_HD size_t sn_field_base(int img, int y, int x, int sh, int sw, int Hp, int Wp, int cinp) {
     return (((size_t)img * Hp + (size_t)y * sh) * Wp + (size_t)x * sw) * cinp;
 }
 
-/* offset of tap (ky, kx) = (tap / kw, tap % kw), channel 0, from the field's base */
-SN_HD size_t sn_tap_offset(int tap, int kw, int Wp, int cinp) { return ((size_t)(tap / kw) * Wp + (size_t)(tap % kw)) * cinp; }
-
 /* a residual block (stride 1, C_in = C_out, same extent) adds its own input at the same pixel: where that pixel begins */
-SN_HD size_t sn_residual_pixel(int img, int y, int x, int Hp, int Wp, int ipad, int cinp) {
+CN_HD size_t sn_residual_pixel(int img, int y, int x, int Hp, int Wp, int ipad, int cinp) {
     return (((size_t)img * Hp + (size_t)(y + ipad)) * Wp + (size_t)(x + ipad)) * cinp;
-}
-
-/* ---- the face-window prologue -------------------------------------------------------------------------------------------------
- * F.interpolate(mode="bilinear", align_corners=False, antialias=False) along one axis: output index d of `out` from `in` source
- * samples.  src = (d + 0.5) in / out - 0.5, clamped at 0; i0 = floor(src), i1 = min(i0 + 1, in - 1), weight of i1 = src - i0. */
-SN_HD void sn_bilinear(int d, int in, int out, int* i0, int* i1, double* w1) {
-    double src = ((double)in / (double)out) * ((double)d + 0.5) - 0.5;
-    if (src < 0.0) src = 0.0;
-    int a = (int)src;
-    if (a > in - 1) a = in - 1;
-    *i0 = a;
-    *i1 = a + 1 < in ? a + 1 : in - 1;
-    *w1 = src - (double)a;
-}
-
-/* a crop box (y1, y2, x1, x2), rows y1 .. y2 - 1 and columns x1 .. x2 - 1, forced inside an H x W frame: the entry point's
- * callers check their boxes on the host; the kernel clamps so that a bad box on the device cannot read outside the frame */
-SN_HD void sn_clamp_box(const int* box, int H, int W, int* y1, int* h, int* x1, int* w) {
-    const int ya = sn_clampi(box[0], 0, H - 1), yb = sn_clampi(box[1], ya + 1, H);
-    const int xa = sn_clampi(box[2], 0, W - 1), xb = sn_clampi(box[3], xa + 1, W);
-    *y1 = ya;
-    *h = yb - ya;
-    *x1 = xa;
-    *w = xb - xa;
 }
 
 #endif

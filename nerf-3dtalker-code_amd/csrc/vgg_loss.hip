@@ -25,6 +25,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "n3dt_launch.h"
 
 #define VGG_L1_BLOCKS 256
@@ -93,11 +94,6 @@ __global__ __launch_bounds__(256) void vgg_pack_kernel(const float* __restrict__
     const __bf16 h = (__bf16)w;
     hi[e] = h;
     if (split) lo[e] = conv_lo(w, h);
-}
-
-__global__ __launch_bounds__(256) void vgg_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < n) dst[e] = src[e];
 }
 
 // ---- implicit-GEMM 3x3 convolution ---------------------------------------------------------------------------------------------
@@ -460,7 +456,7 @@ extern "C" void n3dt_launch_vgg_pack(int precision, const N3dtVggParams* p, void
             vgg_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p->weight[l], kCin[l], kCout[l], L.kp[l][d], L.np[l][d], d, split, hi,
                                                                         split ? hi + n : hi);
         }
-        vgg_copy_kernel<<<(kCout[l] + 255) / 256, 256, 0, st>>>(p->bias[l], kCout[l], (float*)(base + L.bias[l]));
+        conv_net_copy(p->bias[l], (size_t)kCout[l], (float*)(base + L.bias[l]), st);
     }
 }
 

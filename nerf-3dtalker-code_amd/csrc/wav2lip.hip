@@ -6,7 +6,7 @@
 // weights and the epilogue's register -> row map are conv_mfma.h's and conv_frag.h's, shared with syncnet.hip, unchanged.
 //
 //   face inputs  frames [F,3,H,W] fp32 RGB + crop boxes -> [n,6,96,96]: the target frame's crop, BGR, rows 48..95 zero, then the
-//                reference frame's crop, BGR; bilinear with half-pixel centres in float64 (syncnet_core.h's sn_bilinear)
+//                reference frame's crop, BGR; bilinear with half-pixel centres in float64 (conv_net_core.h's cn_bilinear)
 //   layout       [n,C,H,W] -> NHWC with C padded to 16 and the consumer's zero halo, into a map or a slice of a CAT buffer
 //   conv x50     Conv2d / ConvTranspose2d + folded BatchNorm2d (+ the block's own input) + ReLU as an implicit GEMM on
 //                v_mfma_f32_32x32x16_bf16, both operands split into two bf16s, three products in fp32 (conv_mma_step<true, NT>):
@@ -23,6 +23,7 @@
 
 #include "../../include/n3dt.h"
 #include "conv_mfma.h"
+#include "conv_net.h"
 #include "wav2lip_core.h"
 #include "n3dt_launch.h"
 
@@ -48,10 +49,6 @@ static W2lPackLayout w2l_layout() {
     return L;
 }
 
-__device__ __forceinline__ double w2l_bn_scale(const float* gamma, const float* var, int n) {
-    return (double)gamma[n] / sqrt((double)var[n] + SN_BN_EPS);
-}
-
 // one class of one block.  Conv2d weights are [C_out, C_in, kh, kw], ConvTranspose2d weights [C_in, C_out, kh, kw]; tap `tap` of
 // the class is kernel element kidx[tap] (the tap itself where identity).  Columns cout .. np - 1 and channels cin .. cinp - 1: 0.
 __global__ __launch_bounds__(256) void wav2lip_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
@@ -67,18 +64,11 @@ __global__ __launch_bounds__(256) void wav2lip_pack_kernel(const float* __restri
     float w = 0.0f;
     if (ci < cin && n < cout) {
         const size_t at = tr ? ((size_t)ci * cout + n) * taps_full + kid : ((size_t)n * cin + ci) * taps_full + kid;
-        w = (float)((double)W[at] * w2l_bn_scale(gamma, var, n));
+        w = (float)((double)W[at] * conv_bn_scale(gamma, var, SN_BN_EPS, n));
     }
     const __bf16 h = (__bf16)w;
     hi[e] = h;
     lo[e] = conv_lo(w, h);
-}
-
-__global__ __launch_bounds__(256) void wav2lip_bias_kernel(const float* __restrict__ bias, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, int cout, float* __restrict__ dst) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n < cout) dst[n] = (float)(((double)bias[n] - (double)mean[n]) * w2l_bn_scale(gamma, var, n) + (double)beta[n]);
 }
 
 // the head has no batch norm: weights [3,32,1,1] and bias [3] as they are
@@ -126,11 +116,11 @@ __global__ __launch_bounds__(256) void wav2lip_face_inputs_kernel(int n, int hei
         }
         const int c = 2 - ch % 3;  // BGR: output channel 0 is the frame's blue
         int y1, h, x1, w;
-        sn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
+        cn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
         int ya, yb, xa, xb;
         double wy, wx;
-        sn_bilinear(y, h, W2L_IMG, &ya, &yb, &wy);
-        sn_bilinear(x, w, W2L_IMG, &xa, &xb, &wx);
+        cn_bilinear(y, h, W2L_IMG, &ya, &yb, &wy);
+        cn_bilinear(x, w, W2L_IMG, &xa, &xb, &wx);
         const float* src = (ch < 3 ? frames : ref_frames) + ((size_t)frame * 3 + c) * plane;
         out[e] = (float)w2l_sample(src, width, y1, x1, ya, yb, xa, xb, wy, wx, true);
     }
@@ -148,13 +138,13 @@ __global__ __launch_bounds__(256) void wav2lip_paste_kernel(int n, int height, i
         t /= height;
         const int c = (int)(t % 3), frame = (int)(t / 3);
         int y1, h, x1, w;
-        sn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
+        cn_clamp_box(boxes + (size_t)frame * box_stride, height, width, &y1, &h, &x1, &w);
         float v = frames[e];
         if (y >= y1 && y < y1 + h && x >= x1 && x < x1 + w) {
             int ya, yb, xa, xb;
             double wy, wx;
-            sn_bilinear(y - y1, W2L_IMG, h, &ya, &yb, &wy);
-            sn_bilinear(x - x1, W2L_IMG, w, &xa, &xb, &wx);
+            cn_bilinear(y - y1, W2L_IMG, h, &ya, &yb, &wy);
+            cn_bilinear(x - x1, W2L_IMG, w, &xa, &xb, &wx);
             const float* src = faces + ((size_t)frame * 3 + (2 - c)) * W2L_IMG * W2L_IMG;
             v = (float)w2l_sample(src, W2L_IMG, 0, 0, ya, yb, xa, xb, wy, wx, false);
         }
@@ -162,41 +152,8 @@ __global__ __launch_bounds__(256) void wav2lip_paste_kernel(int n, int height, i
     }
 }
 
-// ---- layouts -------------------------------------------------------------------------------------------------------------------
-// src [n, C, H, W] -> channels 0 .. Cp - 1 of dst [n, H + 2 pad, W + 2 pad, .] with row stride dstride: zero in the halo and in
-// channels C .. Cp - 1.  One thread per element.
-__global__ __launch_bounds__(256) void wav2lip_to_nhwc_kernel(const float* __restrict__ src, int n, int C, int H, int W, int pad, int Cp,
-                                                              float* __restrict__ dst, int dstride) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * Hp * Wp * Cp;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e % Cp);
-        size_t t = e / Cp;
-        const int xp = (int)(t % Wp);
-        const size_t cell = t;
-        t /= Wp;
-        const int yp = (int)(t % Hp), img = (int)(t / Hp);
-        float v = 0.0f;
-        if (c < C && xp >= pad && xp < Wp - pad && yp >= pad && yp < Hp - pad)
-            v = src[(((size_t)img * C + c) * H + (yp - pad)) * W + (xp - pad)];
-        dst[cell * dstride + c] = v;
-    }
-}
-
-// channels 0 .. C - 1 of src [n, H + 2 pad, W + 2 pad, .] with row stride sstride -> dst [n, C, H, W]
-__global__ __launch_bounds__(256) void wav2lip_to_nchw_kernel(const float* __restrict__ src, int sstride, int n, int C, int H, int W, int pad,
-                                                              float* __restrict__ dst) {
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const size_t total = (size_t)n * C * H * W;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int x = (int)(e % W);
-        size_t t = e / W;
-        const int y = (int)(t % H);
-        t /= H;
-        const int c = (int)(t % C), img = (int)(t / C);
-        dst[e] = src[w2l_cell(img, y + pad, x + pad, Hp, Wp, sstride) + c];
-    }
-}
+// layouts: conv_net.hip's -- [n,C,H,W] -> NHWC with C padded to 16 and the consumer's zero halo, into a map or a slice of a CAT
+// buffer (the destination's cell stride is an argument), and back
 
 // ---- implicit-GEMM convolution ---------------------------------------------------------------------------------------------------
 struct W2lConvArgs {
@@ -209,7 +166,7 @@ struct W2lConvArgs {
 };
 
 // 256 threads = 4 waves; wave tile t = 4 blockIdx.x + wave belongs to the class c with cls[c].tile0 <= t < cls[c + 1].tile0 and
-// computes SN_TILE_M of its rows x 32 NT channels, the channel tile fastest.  A k-step is 16 channels of one tap.
+// computes CN_TILE_M of its rows x 32 NT channels, the channel tile fastest.  A k-step is 16 channels of one tap.
 template <int NT>
 __global__ __launch_bounds__(256) void wav2lip_conv_kernel(W2lConvArgs a) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -222,7 +179,7 @@ __global__ __launch_bounds__(256) void wav2lip_conv_kernel(W2lConvArgs a) {
     const long long Mc = w2l_class_rows(&k, a.n);
     const int ntn = a.np / (32 * NT);
     const long long lt = tile - k.tile0;
-    const long long m0 = lt / ntn * SN_TILE_M;
+    const long long m0 = lt / ntn * CN_TILE_M;
     if (m0 >= Mc) return;  // no barriers in this kernel: an idle wave may leave
     const int nt0 = (int)(lt % ntn) * NT;
     const int taps = k.tkh * k.tkw;
@@ -233,7 +190,7 @@ __global__ __launch_bounds__(256) void wav2lip_conv_kernel(W2lConvArgs a) {
     for (int mt = 0; mt < 2; ++mt) {
         int img, yq, xq;
         w2l_row_cell(m0 + mt * 32 + r, Mc, k.oy, k.ox, k.Hc, k.Wc, k.step, &img, &yq, &xq);  // rows past Mc: the last cell again, never stored
-        const int y = sn_clampi(yq - a.opad, 0, a.Ho - 1), x = sn_clampi(xq - a.opad, 0, a.Wo - 1);
+        const int y = cn_clampi(yq - a.opad, 0, a.Ho - 1), x = cn_clampi(xq - a.opad, 0, a.Wo - 1);
         base[mt] = a.in + w2l_cell(img, w2l_in_cell(y, a.tr, a.sh, a.ihalo, a.pad), w2l_in_cell(x, a.tr, a.sw, a.ihalo, a.pad), a.Hp, a.Wp, a.istride);
     }
     conv_f32x16 acc[2][NT];
@@ -260,7 +217,7 @@ __global__ __launch_bounds__(256) void wav2lip_conv_kernel(W2lConvArgs a) {
             if (m >= Mc) continue;
             int img, yq, xq;
             w2l_row_cell(m, Mc, k.oy, k.ox, k.Hc, k.Wc, k.step, &img, &yq, &xq);
-            const bool inside = sn_interior(yq, xq, a.Ho, a.Wo, a.opad);
+            const bool inside = cn_interior(yq, xq, a.Ho, a.Wo, a.opad);
             float* o = a.out + w2l_cell(img, yq, xq, a.Hq, a.Wq, a.ostride);
             const float* res = nullptr;
             if (inside && a.residual) res = a.in + w2l_cell(img, yq - a.opad + a.ihalo, xq - a.opad + a.ihalo, a.Hp, a.Wp, a.istride);
@@ -348,8 +305,7 @@ extern "C" void n3dt_launch_wav2lip_pack(const N3dtWav2lipParams* p, void* packe
             wav2lip_pack_kernel<<<(unsigned)((elems + 255) / 256), 256, 0, st>>>(p->weight[b], p->bn_weight[b], p->bn_var[b], g.tr, g.cin, g.cinp,
                                                                                  g.cout, g.np, g.kh * g.kw, Kc, !g.tr, kidx, hi, hi + elems);
         }
-        wav2lip_bias_kernel<<<(g.cout + 255) / 256, 256, 0, st>>>(p->bias[b], p->bn_weight[b], p->bn_bias[b], p->bn_mean[b], p->bn_var[b], g.cout,
-                                                                  (float*)(base + L.bias[b]));
+        conv_net_bias_bn(p->bias[b], p->bn_weight[b], p->bn_bias[b], p->bn_mean[b], p->bn_var[b], SN_BN_EPS, g.cout, (float*)(base + L.bias[b]), st);
     }
     wav2lip_head_pack_kernel<<<1, 128, 0, st>>>(p->weight[W2L_HEAD], p->bias[W2L_HEAD], (float*)(base + L.w[W2L_HEAD]), (float*)(base + L.bias[W2L_HEAD]));
 }
@@ -404,7 +360,7 @@ extern "C" void n3dt_launch_wav2lip_fwd(int n, const void* packed, const float* 
         const W2lGeom g = w2l_geom(b);
         if (b == 0 || b == W2L_FIRST_AUDIO) {
             cur = map[0];
-            wav2lip_to_nhwc_kernel<<<conv_grid(w2l_in_elems(&g, n)), 256, 0, st>>>(b == 0 ? faces : mel, n, g.cin, g.Hi, g.Wi, g.ihalo, g.cinp, cur, g.cinp);
+            conv_net_to_nhwc(b == 0 ? faces : mel, n, g.cin, g.Hi, g.Wi, g.ihalo, g.cinp, cur, g.cinp, st);
         }
         const float* in = g.in_cat >= 0 ? (const float*)(ws + w.cat[g.in_cat]) + g.in_off : cur;
         float* dst = g.out_cat >= 0 ? (float*)(ws + w.cat[g.out_cat]) + g.out_off : (g.in_cat < 0 && cur == map[0]) ? map[1] : map[0];
@@ -425,7 +381,7 @@ extern "C" void n3dt_launch_wav2lip_block(int block, int n, const void* packed, 
     char* ws = (char*)workspace;
     float* src = g.in_cat >= 0 ? (float*)(ws + w.cat[g.in_cat]) + g.in_off : (float*)(ws + w.map[0]);
     float* map1 = (float*)(ws + w.map[1]);
-    wav2lip_to_nhwc_kernel<<<conv_grid(w2l_in_elems(&g, n)), 256, 0, st>>>(in, n, g.cin, g.Hi, g.Wi, g.ihalo, g.cinp, src, g.istride);
+    conv_net_to_nhwc(in, n, g.cin, g.Hi, g.Wi, g.ihalo, g.cinp, src, g.istride, st);
     if (block == W2L_HEAD) {
         w2l_head(n, packed, src, 0, out, st);
         return;
@@ -433,11 +389,11 @@ extern "C" void n3dt_launch_wav2lip_block(int block, int n, const void* packed, 
     if (skip && block >= W2L_FIRST_DEC && g.out_cat >= 0) {  // these blocks read a map of their own: the CAT buffer is free
         const int j = g.out_cat, C = W2L_CAT_C[j], A = W2L_CAT_A[j];
         float* cat = (float*)(ws + w.cat[j]);
-        wav2lip_to_nhwc_kernel<<<conv_grid((size_t)n * g.Hq * g.Wq * (C - A)), 256, 0, st>>>(skip, n, C - A, g.Ho, g.Wo, g.opad, C - A, cat + A, C);
+        conv_net_to_nhwc(skip, n, C - A, g.Ho, g.Wo, g.opad, C - A, cat + A, C, st);
         w2l_conv(block, n, packed, src, g.istride, cat, C, st);
-        wav2lip_to_nchw_kernel<<<conv_grid((size_t)n * C * g.Ho * g.Wo), 256, 0, st>>>(cat, C, n, C, g.Ho, g.Wo, g.opad, out);
+        conv_net_to_nchw(cat, C, n, C, g.Ho, g.Wo, g.opad, out, st);
         return;
     }
     w2l_conv(block, n, packed, src, g.istride, map1, g.cout, st);
-    wav2lip_to_nchw_kernel<<<conv_grid((size_t)n * g.cout * g.Ho * g.Wo), 256, 0, st>>>(map1, g.cout, n, g.cout, g.Ho, g.Wo, g.opad, out);
+    conv_net_to_nchw(map1, g.cout, n, g.cout, g.Ho, g.Wo, g.opad, out, st);
 }

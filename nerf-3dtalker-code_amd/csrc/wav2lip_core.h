@@ -5,7 +5,7 @@
  * Included by csrc/wav2lip.hip, whose convolution, layout, prologue and paste kernels take their addresses from the functions
  * below, and by tests/wav2lip_core_host.cpp, which walks the very same functions over the convolution kernel's grid on the CPU
  * (under the address and undefined-behaviour sanitizers) for all 51 blocks.  The fragment arithmetic of the packed weights and
- * the epilogue's register -> row map are conv_frag.h's; the resample and the box clamp are syncnet_core.h's.  Compiles as host
+ * the epilogue's register -> row map are conv_frag.h's; the rows' cell map, the resample and the box clamp are conv_net_core.h's.  Compiles as host
  * C++ on its own.
  *
  * Maps.  Every activation is NHWC fp32 with C a multiple of 16 and carries the zero halo its consumer needs.  A block's GEMM has
@@ -27,7 +27,8 @@
 
 #include <stddef.h>
 
-#include "syncnet_core.h"
+#include "conv_net_core.h"
+#include "syncnet_core.h" /* the mel window SN_MEL_H x SN_MEL_W and SN_BN_EPS, which the two Wav2Lip networks share */
 
 #define W2L_BLOCKS 51
 #define W2L_FIRST_AUDIO 18     /* 0..17 the face encoder, 18..30 the audio encoder, 31..48 the decoder, 49..50 the output block */
@@ -112,8 +113,6 @@ static const int W2L_CAT_C[W2L_CATS] = {1024, 1024, 768, 512, 320, 160, 80};
 static const int W2L_CAT_HW[W2L_CATS] = {1, 3, 6, 12, 24, 48, 96};
 static const int W2L_CAT_HALO[W2L_CATS] = {0, 1, 1, 1, 1, 1, 1};
 
-SN_HD int w2l_round32(int c) { return (c + 31) / 32 * 32; }
-
 static inline size_t w2l_cat_elems(int j) {
     const size_t e = (size_t)(W2L_CAT_HW[j] + 2 * W2L_CAT_HALO[j]);
     return e * e * W2L_CAT_C[j];
@@ -129,7 +128,7 @@ typedef struct W2lGeom {
 } W2lGeom;
 
 static inline int w2l_out_extent(const W2lBlock* t, int n, int k, int s) {
-    return t->tr ? (n - 1) * s - 2 * t->pad + k + (s == 2 ? 1 : 0) : sn_conv_out(n, k, s, t->pad);
+    return t->tr ? (n - 1) * s - 2 * t->pad + k + (s == 2 ? 1 : 0) : cn_conv_out(n, k, s, t->pad);
 }
 
 static inline W2lGeom w2l_geom(int block) {
@@ -148,9 +147,9 @@ static inline W2lGeom w2l_geom(int block) {
     g.Ho = w2l_out_extent(&t, H, t.kh, t.sh);
     g.Wo = w2l_out_extent(&t, W, t.kw, t.sw);
     g.cin = t.cin;
-    g.cinp = sn_round16(t.cin);
+    g.cinp = cn_round16(t.cin);
     g.cout = t.cout;
-    g.np = w2l_round32(t.cout);
+    g.np = cn_round32(t.cout);
     g.pad = t.pad;
     g.kh = t.kh;
     g.kw = t.kw;
@@ -219,8 +218,8 @@ typedef struct W2lClass {
     long long woff;
 } W2lClass;
 
-SN_HD long long w2l_class_rows(const W2lClass* c, int n) { return (long long)n * c->Hc * c->Wc; }
-SN_HD long long w2l_class_tiles(const W2lClass* c, int n, int ntn) { return (w2l_class_rows(c, n) + SN_TILE_M - 1) / SN_TILE_M * ntn; }
+CN_HD long long w2l_class_rows(const W2lClass* c, int n) { return (long long)n * c->Hc * c->Wc; }
+CN_HD long long w2l_class_tiles(const W2lClass* c, int n, int ntn) { return (w2l_class_rows(c, n) + CN_TILE_M - 1) / CN_TILE_M * ntn; }
 
 /* the classes of a block for n windows and wave tiles of 32 NT columns; returns their number and the launch's tiles in *tiles */
 static inline int w2l_classes(const W2lGeom* g, int n, int NT, W2lClass* cls, long long* tiles) {
@@ -274,19 +273,19 @@ static inline int w2l_wave_ntiles(const W2lGeom* g, int n) {
 
 /* ---- rows of the implicit GEMM -------------------------------------------------------------------------------------------------
  * Row m of class c is cell (img, yq, xq) of the padded output map; rows past Mc compute row Mc - 1 again and are never stored. */
-SN_HD void w2l_row_cell(long long m, long long Mc, int oy, int ox, int Hc, int Wc, int step, int* img, int* yq, int* xq) {
+CN_HD void w2l_row_cell(long long m, long long Mc, int oy, int ox, int Hc, int Wc, int step, int* img, int* yq, int* xq) {
     int i, j;
-    sn_row_cell(m, Mc, Hc, Wc, img, &i, &j);
+    cn_row_cell(m, Mc, Hc, Wc, img, &i, &j);
     *yq = oy + step * i;
     *xq = ox + step * j;
 }
 
 /* the input cell of tap (0, 0) of output pixel y (one axis): Conv2d y s + (ihalo - pad); the parity classes y / 2 + ihalo (the
  * halo cell behind the last row is what (y + 1) / 2 reads for the last odd y); the 1 x 1 map's only cell */
-SN_HD int w2l_in_cell(int y, int tr, int s, int ihalo, int pad) { return tr ? (s == 2 ? (y >> 1) + ihalo : ihalo) : y * s + ihalo - pad; }
+CN_HD int w2l_in_cell(int y, int tr, int s, int ihalo, int pad) { return tr ? (s == 2 ? (y >> 1) + ihalo : ihalo) : y * s + ihalo - pad; }
 
-SN_HD size_t w2l_cell(int img, int y, int x, int H, int W, int stride) { return (((size_t)img * H + (size_t)y) * W + (size_t)x) * stride; }
+CN_HD size_t w2l_cell(int img, int y, int x, int H, int W, int stride) { return (((size_t)img * H + (size_t)y) * W + (size_t)x) * stride; }
 
-SN_HD size_t w2l_tap_offset(int tap, int tkw, int Wp, int istride) { return ((size_t)(tap / tkw) * Wp + (size_t)(tap % tkw)) * istride; }
+CN_HD size_t w2l_tap_offset(int tap, int tkw, int Wp, int istride) { return ((size_t)(tap / tkw) * Wp + (size_t)(tap % tkw)) * istride; }
 
 #endif

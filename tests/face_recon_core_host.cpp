@@ -64,9 +64,9 @@ static void walk_pack(int j) {
         ++written[e];
         size_t at = src;
         if (g.role == FR_STEM) {
-            if (k < FR_STEM_K) {
+            if (k < CN_STEM_K) {
                 int ky, kx, c;
-                fr_stem_tap(k, &ky, &kx, &c);
+                cn_stem_tap(k, &ky, &kx, &c);
                 CHECK(ky >= 0 && ky < 7 && kx >= 0 && kx < 7 && c >= 0 && c < 3 && (ky * 7 + kx) * 3 + c == k, "stem row %d decodes to (%d, %d, %d)", k, ky, kx, c);
                 at = ((size_t)n * 3 + c) * 49 + ky * 7 + kx;
             }
@@ -74,7 +74,7 @@ static void walk_pack(int j) {
             const int tap = k / g.cin, ci = k - tap * g.cin;
             at = ((size_t)n * g.cin + ci) * (g.k * g.k) + tap;
         }
-        if (g.role != FR_STEM || k < FR_STEM_K) {
+        if (g.role != FR_STEM || k < CN_STEM_K) {
             CHECK(at < src, "pack %d: weight read at %zu of %zu", j, at, src);
             if (at < src) ++taken[at];
         }
@@ -94,10 +94,11 @@ static void walk_pack(int j) {
 // the convolution kernel's grid: loads checked against the `in_floats` live elements of its input, stores counted in `out`
 static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, size_t skip_floats, bool has_skip, Map& out) {
     const FrGeom g = fr_geom(j, Hi, Wi);
-    const int NT = fr_wave_ntiles(&g, n);
     const long long Mq = (long long)n * g.Hq * g.Wq;
+    const int NT = cn_wave_ntiles(Mq, g.cout);
+    CHECK((NT == 1 || NT == 2) && g.cout % (32 * NT) == 0, "conv %d: %d tiles a wave do not divide C_out %d", j, NT, g.cout);
     const int ntn = g.cout / (32 * NT);
-    const size_t mtiles = ((size_t)Mq + SN_TILE_M - 1) / SN_TILE_M, tiles = mtiles * ntn;
+    const size_t mtiles = ((size_t)Mq + CN_TILE_M - 1) / CN_TILE_M, tiles = mtiles * ntn;
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     CHECK(fr_in_elems(&g, n) == in_floats, "conv %d: the input map has %zu elements, what was written %zu", j, fr_in_elems(&g, n), in_floats);
     CHECK((g.role == FR_CONV3) == has_skip, "conv %d: skip", j);
@@ -105,7 +106,7 @@ static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, size_t ski
     for (unsigned block = 0; block < grid; ++block)
         for (int wave = 0; wave < 4; ++wave) {
             const long long tile = (long long)block * 4 + wave;
-            const long long m0 = tile / ntn * SN_TILE_M;
+            const long long m0 = tile / ntn * CN_TILE_M;
             if (m0 >= Mq) continue;
             const int nt0 = (int)(tile % ntn) * NT;
             for (int lane = 0; lane < 64; ++lane) {
@@ -113,18 +114,18 @@ static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, size_t ski
                 if (nt0 == 0)  // the loads do not depend on the column tile
                     for (int mt = 0; mt < 2; ++mt) {
                         int img, yq, xq;
-                        sn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
-                        const int y = sn_clampi(yq - g.opad, 0, g.Ho - 1), x = sn_clampi(xq - g.opad, 0, g.Wo - 1);
-                        const size_t base = fr_field_base(img, y, x, g.stride, g.Hp, g.Wp, g.cinp);
+                        cn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
+                        const int y = cn_clampi(yq - g.opad, 0, g.Ho - 1), x = cn_clampi(xq - g.opad, 0, g.Wo - 1);
+                        const size_t base = cn_field_base(img, y, x, g.stride, g.Hp, g.Wp, g.cinp);
                         if (g.role == FR_STEM) {
-                            for (int s = 0; s < FR_STEM_KP / 16; ++s)
+                            for (int s = 0; s < CN_STEM_KP / 16; ++s)
                                 for (int jj = 0; jj < 8; ++jj) {
                                     const int k = 16 * s + 8 * h + jj;
-                                    const size_t at = base + fr_stem_offset(k < FR_STEM_K ? k : 0, g.Wp);
+                                    const size_t at = base + cn_stem_offset(k < CN_STEM_K ? k : 0, g.Wp);
                                     CHECK(at < in_floats, "stem: load at %zu of %zu", at, in_floats);
-                                    if (k >= FR_STEM_K) continue;
+                                    if (k >= CN_STEM_K) continue;
                                     int ky, kx, c;
-                                    fr_stem_tap(k, &ky, &kx, &c);
+                                    cn_stem_tap(k, &ky, &kx, &c);
                                     const size_t cell = at / 3;
                                     const int xp = (int)(cell % g.Wp), yp = (int)(cell / g.Wp % g.Hp), im = (int)(cell / g.Wp / g.Hp);
                                     CHECK(im == img && yp == y * 2 + ky && xp == x * 2 + kx && (int)(at % 3) == c,
@@ -134,7 +135,7 @@ static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, size_t ski
                         }
                         int s = 0;
                         for (int tap = 0; tap < g.k * g.k; ++tap) {
-                            const size_t toff = sn_tap_offset(tap, g.k, g.Wp, g.cinp) + 8 * h;
+                            const size_t toff = cn_tap_offset(tap, g.k, g.Wp, g.cinp) + 8 * h;
                             for (int c0 = 0; c0 < g.cinp; c0 += 16, ++s) {
                                 const size_t at = base + toff + c0;
                                 CHECK(at + 8 <= in_floats && at % 4 == 0, "conv %d: load at %zu of %zu", j, at, in_floats);
@@ -162,15 +163,15 @@ static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, size_t ski
 }
 
 static void walk_pool(int n, int Hi, int Wi, int C, size_t in_floats, Map& out) {
-    const int Ho = fr_pool_out(Hi), Wo = fr_pool_out(Wi), C4 = C / 4;
+    const int Ho = cn_pool_out(Hi), Wo = cn_pool_out(Wi), C4 = C / 4;
     const size_t total = (size_t)n * Ho * Wo * C4;
     CHECK((size_t)n * Hi * Wi * C == in_floats, "pool: the input map has %zu elements, what was written %zu", (size_t)n * Hi * Wi * C, in_floats);
     for (size_t e = 0; e < total; ++e) {
         const int c = (int)(e % C4) * 4;
         int img, yo, xo, ya, yb, xa, xb;
-        fr_cell(e / C4, Ho, Wo, &img, &yo, &xo);
-        fr_pool_range(yo, Hi, &ya, &yb);
-        fr_pool_range(xo, Wi, &xa, &xb);
+        cn_cell(e / C4, Ho, Wo, &img, &yo, &xo);
+        cn_pool_range(yo, Hi, &ya, &yb);
+        cn_pool_range(xo, Wi, &xa, &xb);
         CHECK(ya < yb && xa < xb && ya >= 0 && yb <= Hi && xa >= 0 && xb <= Wi && ya >= 2 * yo - 1 && yb <= 2 * yo + 2 && xa >= 2 * xo - 1 && xb <= 2 * xo + 2,
               "pool: cell (%d, %d) takes rows [%d, %d) columns [%d, %d)", yo, xo, ya, yb, xa, xb);
         // exactly the taps of the 3 x 3 window at (2 yo - 1, 2 xo - 1) that lie inside the map
@@ -224,7 +225,7 @@ static void walk_chain(int n, int H, int W) {
         Map& out = region[t.out];
         if (t.block == FR_POOL_BLOCK) {
             walk_pool(n, t.Hi, t.Wi, 64, region[t.in].live, out);
-            line(n, H, W, t.block, t.Hi, t.Wi, fr_pool_out(t.Hi), fr_pool_out(t.Wi), 64, out.once((size_t)n * fr_step_out_elems(&t), "pool", t.block));
+            line(n, H, W, t.block, t.Hi, t.Wi, cn_pool_out(t.Hi), cn_pool_out(t.Wi), 64, out.once((size_t)n * fr_step_out_elems(&t), "pool", t.block));
         } else if (t.block == FR_AVG_BLOCK) {
             walk_avg(n, t.Hi * t.Wi, FR_FEAT, region[t.in].live, out);
             line(n, H, W, t.block, t.Hi, t.Wi, 1, 1, FR_FEAT, out.once((size_t)n * FR_FEAT, "average", t.block));

@@ -74,33 +74,34 @@ static void settle(Walk& w, int step, size_t base, size_t cells, int cs, int c0,
 static size_t walk_conv(Walk& w, int s, const FanStep& t, int N, int* Ho_, int* Wo_) {
     const FanConv c = fan_conv(t.conv, N);
     const int n = w.images, pad = c.k / 2, Hi = t.H, Wi = t.W;
-    const int Ho = sn_conv_out(Hi, c.k, c.stride, pad), Wo = sn_conv_out(Wi, c.k, c.stride, pad);
+    const int Ho = cn_conv_out(Hi, c.k, c.stride, pad), Wo = cn_conv_out(Wi, c.k, c.stride, pad);
     *Ho_ = Ho; *Wo_ = Wo;
-    const int cin = fan_cinp(&c), np = fan_np(&c), cstore = c.kind == FAN_L ? sn_round16(c.cout) : c.cout;
+    const int cin = fan_cinp(&c), np = fan_np(&c), cstore = c.kind == FAN_L ? cn_round16(c.cout) : c.cout;
     const long long M = (long long)n * Ho * Wo;
-    const int NT = fan_wave_ntiles(M, np), ntn = np / (32 * NT);
+    const int NT = cn_wave_ntiles(M, np), ntn = np / (32 * NT);
+    CHECK((NT == 1 || NT == 2) && np % (32 * NT) == 0, "step %d: %d tiles a wave do not divide the %d columns", s, NT, np);
     CHECK(np % (32 * NT) == 0 && cin % (c.kind == FAN_STEM ? 1 : 16) == 0, "step %d: tile widths", s);
     const size_t in_lo = w.at(t.in), in_hi = in_lo + (size_t)n * Hi * Wi * t.in_cs;
     const size_t out_lo = w.at(t.out), out_hi = out_lo + (size_t)M * t.out_cs;
     CHECK(t.in_c0 + (c.kind == FAN_STEM ? 3 : cin) <= t.in_cs && t.out_c0 + cstore <= t.out_cs, "step %d: slices wider than their maps", s);
-    const long long tiles = (M + SN_TILE_M - 1) / SN_TILE_M * ntn;
+    const long long tiles = (M + CN_TILE_M - 1) / CN_TILE_M * ntn;
     const long long grid = (tiles + 3) / 4;
     size_t stores = 0;
     for (long long block = 0; block < grid; ++block)
         for (int wave = 0; wave < 4; ++wave) {
-            const long long tile = block * 4 + wave, m0 = tile / ntn * SN_TILE_M;
+            const long long tile = block * 4 + wave, m0 = tile / ntn * CN_TILE_M;
             if (m0 >= M) continue;
             const int nt0 = (int)(tile % ntn) * NT;
             if (nt0 == 0)  // the A fetch does not depend on the column tile: walk it once per row tile
                 for (int mt = 0; mt < 2; ++mt)
                     for (int r = 0; r < 32; ++r) {
                         int img, y, x;
-                        sn_row_cell(m0 + mt * 32 + r, M, Ho, Wo, &img, &y, &x);
+                        cn_row_cell(m0 + mt * 32 + r, M, Ho, Wo, &img, &y, &x);
                         const size_t base = in_lo + (size_t)img * Hi * Wi * t.in_cs + t.in_c0;
                         if (c.kind == FAN_STEM) {
-                            for (int k = 0; k < FAN_STEM_K; ++k) {
+                            for (int k = 0; k < CN_STEM_K; ++k) {
                                 int ky, kx, ch;
-                                fan_stem_tap(k, &ky, &kx, &ch);
+                                cn_stem_tap(k, &ky, &kx, &ch);
                                 const int iy = fan_tap_pixel(y, ky, 2, 3), ix = fan_tap_pixel(x, kx, 2, 3);
                                 if (fan_inside(iy, ix, Hi, Wi)) read_range(w, s, base + ((size_t)iy * Wi + ix) * 3 + ch, 1, in_lo, in_hi, "stem");
                             }
@@ -205,9 +206,9 @@ static void walk_pack(int modules, int N) {
             if (n >= c.cout) continue;
             size_t src;
             if (c.kind == FAN_STEM) {
-                if (k >= FAN_STEM_K) continue;
+                if (k >= CN_STEM_K) continue;
                 int ky, kx, ch;
-                fan_stem_tap(k, &ky, &kx, &ch);
+                cn_stem_tap(k, &ky, &kx, &ch);
                 src = ((size_t)n * wc + ch) * 49 + ky * 7 + kx;
             } else {
                 const int tap = k / cinp, ci = k - tap * cinp;

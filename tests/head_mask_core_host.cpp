@@ -45,9 +45,10 @@ static void walk_conv(const HmStep& t, int n, const Held* held, const HmWorkspac
     const int Ho = hm_out_h(j, t.Hi), Wo = hm_out_h(j, t.Wi), np = hm_np(j);
     const int csplit = t.in2 >= 0 ? c.cin / 2 : c.cin, c2 = c.cin - csplit;
     const long long M = (long long)n * Ho * Wo;
-    const int NT = hm_wave_ntiles(np, (size_t)M);
+    const int NT = cn_wave_ntiles(M, np);
+    CHECK((NT == 1 || NT == 2) && np % (32 * NT) == 0, "block %d: %d tiles a wave do not divide the %d columns", j, NT, np);
     const int ntn = np / (32 * NT);
-    const long long tiles = (M + SN_TILE_M - 1) / SN_TILE_M * ntn;
+    const long long tiles = (M + CN_TILE_M - 1) / CN_TILE_M * ntn;
     const long long grid = (tiles + 3) / 4;
     CHECK((np % (32 * NT) == 0 && c.cin % 16 == 0) || c.kind == HM_STEM, "block %d: np %d cin %d", j, np, c.cin);
     CHECK((size_t)M * np * sizeof(float) <= ws.bytes[t.out], "block %d: output larger than region %d", j, t.out);
@@ -63,20 +64,20 @@ static void walk_conv(const HmStep& t, int n, const Held* held, const HmWorkspac
     for (long long blk = 0; blk < grid; ++blk)
         for (int wave = 0; wave < 4; ++wave) {
             const long long tile = blk * 4 + wave;
-            const long long m0 = tile / ntn * SN_TILE_M;
+            const long long m0 = tile / ntn * CN_TILE_M;
             if (m0 >= M) continue;
             const int nt0 = (int)(tile % ntn) * NT;
             for (int lane = 0; lane < 64; ++lane) {
                 const int r = lane & 31, h = lane >> 5;
                 for (int mt = 0; mt < 2; ++mt) {
                     int img, yo, xo;
-                    sn_row_cell(m0 + mt * 32 + r, M, Ho, Wo, &img, &yo, &xo);
+                    cn_row_cell(m0 + mt * 32 + r, M, Ho, Wo, &img, &yo, &xo);
                     CHECK(img >= 0 && img < n && yo >= 0 && yo < Ho && xo >= 0 && xo < Wo, "block %d: row", j);
                     if (c.kind == HM_STEM) {
-                        const size_t base = fr_field_base(img, yo, xo, c.stride, t.Hi + 6, t.Wi + 6, 3);
-                        for (int k = 8 * h; k < FR_STEM_KP; k += 16)
+                        const size_t base = cn_field_base(img, yo, xo, c.stride, t.Hi + 6, t.Wi + 6, 3);
+                        for (int k = 8 * h; k < CN_STEM_KP; k += 16)
                             for (int jj = 0; jj < 8; ++jj) {
-                                const size_t off = base + fr_stem_offset(k + jj < FR_STEM_K ? k + jj : 0, t.Wi + 6);
+                                const size_t off = base + cn_stem_offset(k + jj < CN_STEM_K ? k + jj : 0, t.Wi + 6);
                                 CHECK(off < in_total, "stem load %zu of %zu", off, in_total);
                                 ++wk->loads;
                             }
@@ -118,15 +119,15 @@ static void walk_conv(const HmStep& t, int n, const Held* held, const HmWorkspac
 }
 
 static void walk_pool(const HmStep& t, int n, const Held* held, const HmWorkspace& ws, Walk* wk) {
-    const int Ho = fr_pool_out(t.Hi), Wo = fr_pool_out(t.Wi);
+    const int Ho = cn_pool_out(t.Hi), Wo = cn_pool_out(t.Wi);
     CHECK(held[t.in].elems == (size_t)t.Hi * t.Wi * 64, "pool input");
     CHECK((size_t)n * Ho * Wo * 64 * sizeof(float) <= ws.bytes[t.out], "pool output");
     const size_t total = (size_t)n * Ho * Wo * 16;
     for (size_t e = 0; e < total; ++e) {
         int img, yo, xo, ya, yb, xa, xb;
-        fr_cell(e / 16, Ho, Wo, &img, &yo, &xo);
-        fr_pool_range(yo, t.Hi, &ya, &yb);
-        fr_pool_range(xo, t.Wi, &xa, &xb);
+        cn_cell(e / 16, Ho, Wo, &img, &yo, &xo);
+        cn_pool_range(yo, t.Hi, &ya, &yb);
+        cn_pool_range(xo, t.Wi, &xa, &xb);
         CHECK(img < n && ya >= 0 && ya < yb && yb <= t.Hi && xa >= 0 && xa < xb && xb <= t.Wi, "pool window");
         ++wk->stores;
     }

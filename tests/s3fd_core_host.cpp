@@ -71,17 +71,18 @@ static void walk_pack(int j) {
 // the convolution kernel's grid: loads checked against `in_floats`, stores counted in `out`
 static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, Map& out) {
     const S3Geom g = s3_gemm_geom(j, Hi, Wi);
-    const int NT = s3_wave_ntiles(&g, n);
     const long long Mq = (long long)n * g.Hq * g.Wq;
+    const int NT = cn_wave_ntiles(Mq, g.np);
+    CHECK((NT == 1 || NT == 2) && g.np % (32 * NT) == 0, "conv %d: %d tiles a wave do not divide the %d columns", j, NT, g.np);
     const int ntn = g.np / (32 * NT);
-    const size_t mtiles = ((size_t)Mq + SN_TILE_M - 1) / SN_TILE_M, tiles = mtiles * ntn;
+    const size_t mtiles = ((size_t)Mq + CN_TILE_M - 1) / CN_TILE_M, tiles = mtiles * ntn;
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     const int pad = g.ihalo - g.ioff;
     CHECK(s3_in_elems(&g, n) <= in_floats, "conv %d: the input map has %zu elements, its region %zu", j, s3_in_elems(&g, n), in_floats);
     for (unsigned block = 0; block < grid; ++block)
         for (int wave = 0; wave < 4; ++wave) {
             const long long tile = (long long)block * 4 + wave;
-            const long long m0 = tile / ntn * SN_TILE_M;
+            const long long m0 = tile / ntn * CN_TILE_M;
             if (m0 >= Mq) continue;
             const int nt0 = (int)(tile % ntn) * NT;
             for (int lane = 0; lane < 64; ++lane) {
@@ -89,12 +90,12 @@ static void walk_conv(int j, int n, int Hi, int Wi, size_t in_floats, Map& out) 
                 if (nt0 == 0)  // the loads do not depend on the column tile
                     for (int mt = 0; mt < 2; ++mt) {
                         int img, yq, xq;
-                        sn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
-                        const int y = sn_clampi(yq - g.opad, 0, g.Ho - 1), x = sn_clampi(xq - g.opad, 0, g.Wo - 1);
+                        cn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
+                        const int y = cn_clampi(yq - g.opad, 0, g.Ho - 1), x = cn_clampi(xq - g.opad, 0, g.Wo - 1);
                         const size_t base = s3_field_base(img, y, x, g.stride, g.ioff, g.Hp, g.Wp, g.cinp);
                         int s = 0;
                         for (int tap = 0; tap < g.k * g.k; ++tap) {
-                            const size_t toff = sn_tap_offset(tap, g.k, g.Wp, g.cinp) + 8 * h;
+                            const size_t toff = cn_tap_offset(tap, g.k, g.Wp, g.cinp) + 8 * h;
                             for (int c0 = 0; c0 < g.cinp; c0 += 16, ++s) {
                                 const size_t at = base + toff + c0;
                                 CHECK(at + 8 <= in_floats && at % 4 == 0, "conv %d: load at %zu of %zu", j, at, in_floats);
@@ -128,8 +129,8 @@ static void walk_pool(int n, int Hi, int Wi, int ihalo, int C, int opad, size_t 
     for (size_t e = 0; e < total; ++e) {
         const int c = (int)(e % C4) * 4;
         int img, yq, xq;
-        s3_cell(e / C4, Hq, Wq, &img, &yq, &xq);
-        if (sn_interior(yq, xq, Ho, Wo, opad)) {
+        cn_cell(e / C4, Hq, Wq, &img, &yq, &xq);
+        if (cn_interior(yq, xq, Ho, Wo, opad)) {
             const size_t p = s3_pool_base(img, yq - opad, xq - opad, Hi, Wi, ihalo, C) + c;
             CHECK(p + row + C + 4 <= in_floats, "pool: load at %zu of %zu", p + row + C, in_floats);
             const size_t cell = p / C;
@@ -146,8 +147,8 @@ static void walk_norm(int n, int H, int W, int C, size_t in_floats, Map& out) {
     const size_t total = (size_t)n * Hq * Wq;
     for (size_t e = 0; e < total; ++e) {
         int img, yq, xq;
-        s3_cell(e, Hq, Wq, &img, &yq, &xq);
-        if (sn_interior(yq, xq, H, W, 1)) {
+        cn_cell(e, Hq, Wq, &img, &yq, &xq);
+        if (cn_interior(yq, xq, H, W, 1)) {
             const size_t at = (((size_t)img * H + (yq - 1)) * W + (xq - 1)) * C;
             CHECK(at + C <= in_floats, "norm: load at %zu of %zu", at, in_floats);
         }

@@ -1,7 +1,7 @@
 // The index arithmetic of csrc/syncnet_core.h walked on the CPU over the grid of csrc/syncnet.hip's convolution kernel, for all 31
 // blocks and the window counts given on the command line (default 1 2 3), and the weight pack of every block against the addresses
 // the MFMA step reads it at.  The loop nest below is RE-TYPED from syncnet_conv_kernel (block / wave / lane / K step), and so is
-// syncnet_pack_kernel's weight lookup: a change there must be made here too.  NOT re-typed, but the very functions the kernels are
+// conv_net_pack_kernel's weight lookup: a change there must be made here too.  NOT re-typed, but the very functions the kernels are
 // compiled from: syncnet_core.h's, and from csrc/conv_frag.h the epilogue's register -> row map (cf_acc_row), the pack kernel's
 // element decode (cf_pack_decode) and the address of the step's weight fragments (cf_frag_group / cf_frag_elem).
 // Built by tests/test_syncnet_cpu.py with the host compiler under -fsanitize=address,undefined: the maps are heap blocks of exactly
@@ -40,13 +40,13 @@ static void walk_conv(int b, int n, int NT, bool print) {
     const long long Mq = (long long)n * g.Hq * g.Wq;
     const int ntn = g.cout / (32 * NT);
     CHECK(g.cout % (32 * NT) == 0, "block %d: C_out %d is no multiple of %d", b, g.cout, 32 * NT);
-    const size_t mtiles = ((size_t)Mq + SN_TILE_M - 1) / SN_TILE_M;
+    const size_t mtiles = ((size_t)Mq + CN_TILE_M - 1) / CN_TILE_M;
     const size_t tiles = mtiles * ntn;
     const unsigned grid = (unsigned)((tiles + 3) / 4);
     for (unsigned block = 0; block < grid; ++block)
         for (int wave = 0; wave < 4; ++wave) {
             const long long tile = (long long)block * 4 + wave;
-            const long long m0 = tile / ntn * SN_TILE_M;
+            const long long m0 = tile / ntn * CN_TILE_M;
             if (m0 >= Mq) continue;
             const int nt0 = (int)(tile % ntn) * NT;
             for (int lane = 0; lane < 64; ++lane) {
@@ -55,15 +55,15 @@ static void walk_conv(int b, int n, int NT, bool print) {
                 int py[2], px[2], pimg[2];
                 for (int mt = 0; mt < 2; ++mt) {
                     int img, yq, xq;
-                    sn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
-                    const int y = sn_clampi(yq - g.opad, 0, g.Ho - 1), x = sn_clampi(xq - g.opad, 0, g.Wo - 1);
+                    cn_row_cell(m0 + mt * 32 + r, Mq, g.Hq, g.Wq, &img, &yq, &xq);
+                    const int y = cn_clampi(yq - g.opad, 0, g.Ho - 1), x = cn_clampi(xq - g.opad, 0, g.Wo - 1);
                     CHECK(img >= 0 && img < n && y >= 0 && y < g.Ho && x >= 0 && x < g.Wo, "block %d: row decodes outside the map", b);
                     base[mt] = sn_field_base(img, y, x, g.sh, g.sw, g.Hp, g.Wp, g.cinp);
                     pimg[mt] = img; py[mt] = y; px[mt] = x;
                 }
                 int s = 0;
                 for (int tap = 0; tap < g.kh * g.kw; ++tap) {
-                    const size_t toff = sn_tap_offset(tap, g.kw, g.Wp, g.cinp) + 8 * h;
+                    const size_t toff = cn_tap_offset(tap, g.kw, g.Wp, g.cinp) + 8 * h;
                     for (int c0 = 0; c0 < g.cinp; c0 += 16, ++s) {
                         for (int mt = 0; mt < 2; ++mt) {
                             const float* p = in + base[mt] + toff + c0;
@@ -88,8 +88,8 @@ static void walk_conv(int b, int n, int NT, bool print) {
                         const long long m = m0 + mt * 32 + cf_acc_row(i, h);
                         if (m >= Mq) continue;
                         int img, yq, xq;
-                        sn_row_cell(m, Mq, g.Hq, g.Wq, &img, &yq, &xq);
-                        const bool inside = sn_interior(yq, xq, g.Ho, g.Wo, g.opad);
+                        cn_row_cell(m, Mq, g.Hq, g.Wq, &img, &yq, &xq);
+                        const bool inside = cn_interior(yq, xq, g.Ho, g.Wo, g.opad);
                         const size_t o = (size_t)m * g.cout;
                         CHECK(o == (((size_t)img * g.Hq + yq) * g.Wq + xq) * g.cout, "block %d: row %lld is not its cell", b, m);
                         const float* res = nullptr;
@@ -122,7 +122,7 @@ static void walk_conv(int b, int n, int NT, bool print) {
     delete[] stored;
 }
 
-// syncnet_pack_kernel for block b -- one thread per element e of the packed matrix -- and then every weight read of the MFMA step
+// conv_net_pack_kernel for block b -- one thread per element e of the packed matrix -- and then every weight read of the MFMA step
 // over the column tiles of syncnet_conv_kernel<NT>.  packed[e] stands for what the kernel stores at e: 1 + the index of
 // w[n][ci][ky][kx], or 0 where it stores zero.  The decode must hit every (k, n) once and use every weight once; the reader must
 // stay inside the matrix, take every element once, and find at the address of (K step s, tile, lane, j) the weight of the k its A
@@ -186,15 +186,15 @@ static void walk_faces(int H, int W, int b0, int b1, int b2, int b3) {
     for (size_t i = 0; i < (size_t)H * W; ++i) frame[i] = 0.5f;
     const int box[4] = {b0, b1, b2, b3};
     int y1, h, x1, w;
-    sn_clamp_box(box, H, W, &y1, &h, &x1, &w);
+    cn_clamp_box(box, H, W, &y1, &h, &x1, &w);
     CHECK(y1 >= 0 && h >= 1 && y1 + h <= H && x1 >= 0 && w >= 1 && x1 + w <= W, "box (%d,%d,%d,%d) clamps outside %dx%d", b0, b1, b2, b3, H, W);
     volatile float sink = 0.0f;
     for (int y = 0; y < SN_FACE_H; ++y)
         for (int x = 0; x < SN_FACE_W; ++x) {
             int ya, yb, xa, xb;
             double wy, wx;
-            sn_bilinear(SN_CROP - SN_FACE_H + y, h, SN_CROP, &ya, &yb, &wy);
-            sn_bilinear(x, w, SN_CROP, &xa, &xb, &wx);
+            cn_bilinear(SN_CROP - SN_FACE_H + y, h, SN_CROP, &ya, &yb, &wy);
+            cn_bilinear(x, w, SN_CROP, &xa, &xb, &wx);
             CHECK(ya >= 0 && ya <= yb && yb < h && xa >= 0 && xa <= xb && xb < w && wy >= 0.0 && wy <= 1.0 && wx >= 0.0 && wx <= 1.0,
                   "bilinear (%d,%d) of a %dx%d crop", y, x, h, w);
             sink = sink + frame[(size_t)(y1 + ya) * W + (x1 + xa)] + frame[(size_t)(y1 + ya) * W + (x1 + xb)] +
@@ -229,7 +229,8 @@ int main(int argc, char** argv) {
         }
         for (int b = 0; b < SN_BLOCKS; ++b) {
             const SnGeom g = sn_geom(b);
-            const int nt = sn_wave_ntiles(&g, n);
+            const int nt = cn_wave_ntiles((long long)n * g.Hq * g.Wq, g.cout);
+            CHECK((nt == 1 || nt == 2) && g.cout % (32 * nt) == 0, "block %d: %d tiles a wave do not divide C_out %d", b, nt, g.cout);
             walk_conv(b, n, nt, true);
             if (n == counts[0] && g.cout % 64 == 0) walk_conv(b, n, 3 - nt, false);  // the other instantiation too, once
         }

@@ -59,7 +59,7 @@ static void walk_conv(int b, int n, int NT, const unsigned char* in, int in_off,
                 if (c < ncls && tile >= cls[c].tile0) k = cls[c];
             const long long Mc = w2l_class_rows(&k, n);
             const long long lt = tile - k.tile0;
-            const long long m0 = lt / ntn * SN_TILE_M;
+            const long long m0 = lt / ntn * CN_TILE_M;
             if (m0 >= Mc) continue;
             const int nt0 = (int)(lt % ntn) * NT;
             const int taps = k.tkh * k.tkw;
@@ -74,9 +74,9 @@ static void walk_conv(int b, int n, int NT, const unsigned char* in, int in_off,
                         int img, yq, xq;
                         w2l_row_cell(m0 + mt * 32 + r, Mc, k.oy, k.ox, k.Hc, k.Wc, k.step, &img, &yq, &xq);
                         CHECK(img >= 0 && img < n && yq >= 0 && yq < g.Hq && xq >= 0 && xq < g.Wq, "block %d: row decodes outside the map", b);
-                        py[mt] = sn_clampi(yq - g.opad, 0, g.Ho - 1);
-                        px[mt] = sn_clampi(xq - g.opad, 0, g.Wo - 1);
-                        pin[mt] = sn_interior(yq, xq, g.Ho, g.Wo, g.opad);
+                        py[mt] = cn_clampi(yq - g.opad, 0, g.Ho - 1);
+                        px[mt] = cn_clampi(xq - g.opad, 0, g.Wo - 1);
+                        pin[mt] = cn_interior(yq, xq, g.Ho, g.Wo, g.opad);
                         base[mt] = w2l_cell(img, w2l_in_cell(py[mt], g.tr, g.sh, g.ihalo, g.pad), w2l_in_cell(px[mt], g.tr, g.sw, g.ihalo, g.pad), g.Hp,
                                             g.Wp, istride);
                     }
@@ -119,7 +119,7 @@ static void walk_conv(int b, int n, int NT, const unsigned char* in, int in_off,
                         if (m >= Mc) continue;
                         int img, yq, xq;
                         w2l_row_cell(m, Mc, k.oy, k.ox, k.Hc, k.Wc, k.step, &img, &yq, &xq);
-                        const bool inside = sn_interior(yq, xq, g.Ho, g.Wo, g.opad);
+                        const bool inside = cn_interior(yq, xq, g.Ho, g.Wo, g.opad);
                         unsigned char* o = outb + w2l_cell(img, yq, xq, g.Hq, g.Wq, ostride);
                         const unsigned char* res = nullptr;
                         if (inside && g.residual) {
@@ -221,7 +221,7 @@ static void walk_frames(int H, int W, int b0, int b1, int b2, int b3) {
     Bytes frame((size_t)H * W, 1), face((size_t)W2L_IMG * W2L_IMG, 1);
     const int box[4] = {b0, b1, b2, b3};
     int y1, h, x1, w;
-    sn_clamp_box(box, H, W, &y1, &h, &x1, &w);
+    cn_clamp_box(box, H, W, &y1, &h, &x1, &w);
     CHECK(y1 >= 0 && h >= 1 && y1 + h <= H && x1 >= 0 && w >= 1 && x1 + w <= W, "box (%d,%d,%d,%d) clamps outside %dx%d", b0, b1, b2, b3, H, W);
     volatile unsigned sink = 0;
     const unsigned char* fr = frame.data();
@@ -230,8 +230,8 @@ static void walk_frames(int H, int W, int b0, int b1, int b2, int b3) {
         for (int x = 0; x < W2L_IMG; ++x) {
             int ya, yb, xa, xb;
             double wy, wx;
-            sn_bilinear(y, h, W2L_IMG, &ya, &yb, &wy);
-            sn_bilinear(x, w, W2L_IMG, &xa, &xb, &wx);
+            cn_bilinear(y, h, W2L_IMG, &ya, &yb, &wy);
+            cn_bilinear(x, w, W2L_IMG, &xa, &xb, &wx);
             CHECK(ya >= 0 && ya <= yb && yb < h && xa >= 0 && xa <= xb && xb < w && wy >= 0.0 && wy <= 1.0 && wx >= 0.0 && wx <= 1.0,
                   "bilinear (%d,%d) of a %dx%d crop", y, x, h, w);
             sink = sink + fr[(size_t)(y1 + ya) * W + (x1 + xa)] + fr[(size_t)(y1 + ya) * W + (x1 + xb)] + fr[(size_t)(y1 + yb) * W + (x1 + xa)] +
@@ -241,8 +241,8 @@ static void walk_frames(int H, int W, int b0, int b1, int b2, int b3) {
         for (int x = x1; x < x1 + w; ++x) {
             int ya, yb, xa, xb;
             double wy, wx;
-            sn_bilinear(y - y1, W2L_IMG, h, &ya, &yb, &wy);
-            sn_bilinear(x - x1, W2L_IMG, w, &xa, &xb, &wx);
+            cn_bilinear(y - y1, W2L_IMG, h, &ya, &yb, &wy);
+            cn_bilinear(x - x1, W2L_IMG, w, &xa, &xb, &wx);
             CHECK(ya >= 0 && yb < W2L_IMG && xa >= 0 && xb < W2L_IMG && wy >= 0.0 && wy <= 1.0 && wx >= 0.0 && wx <= 1.0, "paste (%d,%d) of a %dx%d box", y, x, h, w);
             sink = sink + fa[(size_t)ya * W2L_IMG + xa] + fa[(size_t)ya * W2L_IMG + xb] + fa[(size_t)yb * W2L_IMG + xa] + fa[(size_t)yb * W2L_IMG + xb];
         }
@@ -303,6 +303,7 @@ int main(int argc, char** argv) {
         for (int b = 0; b < W2L_HEAD; ++b) {
             const W2lGeom g = w2l_geom(b);
             const int nt = w2l_wave_ntiles(&g, n);
+            CHECK((nt == 1 || nt == 2) && g.np % (32 * nt) == 0, "block %d: %d tiles a wave do not divide the %d columns", b, nt, g.np);
             for (int pass = 0; pass < 2; ++pass) {  // the chain's instantiation, then (once) the other one
                 const int NT = pass == 0 ? nt : 3 - nt;
                 if (pass == 1 && !(n == counts[0] && g.np % 64 == 0)) continue;
