@@ -21,26 +21,28 @@ import ctypes
 import torch
 
 from . import ops
+from ._host import PackedCache, count_or_raise, gpu_tensor, open_state_dict, pack, take, workspace
 from ._lib import LPIPS_INPUT_MODES, LpipsParams, check, lib
 from .syncnet import SyncMeter, SyncNet  # noqa: F401
 
 
+def _pair(who, pred, gt):
+    """pred and gt as contiguous float32 [B,3,H,W] GPU tensors of one shape on one device (B = 0 is the library's to refuse)"""
+    for name, t in (("pred", pred), ("gt", gt)):
+        gpu_tensor(who, name, t, copy=False)
+        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be float32 [B,3,H,W], got %s %s" % (who, name, t.dtype, tuple(t.shape)))
+    if pred.shape != gt.shape or pred.device != gt.device:
+        raise ValueError("%s: pred %s and gt %s differ in shape or device" % (who, tuple(pred.shape), tuple(gt.shape)))
+    return pred.detach().contiguous(), gt.detach().contiguous()
+
+
 def _metrics(pred, gt):
     """[2, B] float64 on the device: row 0 SSIM, row 1 PSNR.  Enqueues on the current stream, no synchronisation."""
-    for name, t in (("pred", pred), ("gt", gt)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError("image_metrics: %s must be a GPU tensor (there is no CPU path)" % name)
-        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
-            raise ValueError("image_metrics: %s must be float32 [B,3,H,W], got %s %s" % (name, t.dtype, tuple(t.shape)))
-    if pred.shape != gt.shape or pred.device != gt.device:
-        raise ValueError("image_metrics: pred %s and gt %s differ in shape or device" % (tuple(pred.shape), tuple(gt.shape)))
-    pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
+    pred, gt = _pair("image_metrics", pred, gt)
     B, _, H, W = pred.shape
     L = lib()
-    nbytes = L.n3dt_eval_metrics_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        raise ValueError(L.n3dt_last_error().decode())
-    ws = ops.WORKSPACE.get("eval_metrics", nbytes, pred.device)
+    ws = workspace("eval_metrics", L.n3dt_eval_metrics_workspace_bytes(B, H, W), pred.device)
     out = torch.empty(2, B, dtype=torch.float64, device=pred.device)
     check(L.n3dt_eval_metrics(B, H, W, ops._ptr(pred), ops._ptr(gt), ops._ptr(out[0]), ops._ptr(out[1]), ops._ptr(ws),
                               ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_eval_metrics")
@@ -74,25 +76,17 @@ def load_lpips_alex(state_dict):
     as torchvision names them (`features.{0,3,6,8,10}.{weight,bias}`) or as lpips does (`net.slice{1..5}.{0,3,6,8,10}.*`), and the
     linear layers as `lin{k}.model.1.weight` or `lins.{k}.model.1.weight` ([1, C, 1, 1] or [C]).  Other keys (`scaling_layer.*`,
     `classifier.*`) are ignored.  A missing or wrongly shaped tensor is refused with its key."""
-    if not isinstance(state_dict, dict):
-        raise TypeError("load_lpips_alex: expected a state dict, got %s" % type(state_dict).__name__)
+    sd = open_state_dict("load_lpips_alex", state_dict, paths=False)
 
-    def take(names, shapes):
-        name = next((n for n in names if n in state_dict), None)
-        if name is None:
-            raise KeyError("load_lpips_alex: the state dict has no key %r (nor %s)" % (names[0], ", ".join(repr(n) for n in names[1:])))
-        t = state_dict[name]
-        if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
-            raise ValueError("load_lpips_alex: %r has shape %s, expected %s"
-                             % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, shapes[0]))
-        return t.detach().float()
+    def get(names, shapes):
+        return take("load_lpips_alex", sd, names[0], shapes, names[1:]).float()  # a float32 tensor stays the caller's
 
     out = []
     for layer, (idx, cin, cout, k, _, _) in enumerate(ALEXNET_CONVS):
-        w = take([n + ".weight" for n in _lpips_keys(layer, idx)], [(cout, cin, k, k)])
-        b = take([n + ".bias" for n in _lpips_keys(layer, idx)], [(cout,)])
-        lin = take(["lin%d.model.1.weight" % layer, "lins.%d.model.1.weight" % layer], [(1, cout, 1, 1), (cout,)])
-        out.append((w, b, lin.reshape(cout)))
+        w = get([n + ".weight" for n in _lpips_keys(layer, idx)], (cout, cin, k, k))
+        b = get([n + ".bias" for n in _lpips_keys(layer, idx)], (cout,))
+        lin = get(["lin%d.model.1.weight" % layer, "lins.%d.model.1.weight" % layer], [(1, cout, 1, 1), (cout,)])
+        out.append((w, b, lin.reshape(cout)))  # a view of a float32 `lin`: it shares the caller's version counter
     return out
 
 
@@ -104,56 +98,36 @@ class LPIPS(object):
     its authors define it: channels as given, 2 clamp(x, 0, 1) - 1.
     `lpips(pred, gt)`: [B,3,H,W] float32 GPU tensors (any strides; 31 <= H, W <= 2048, B <= 64) -> float64 [B] on the device,
     stream-ordered, no synchronisation, bitwise reproducible; `lpips.layers(pred, gt)` -> the five layer values, [5, B].
-    The weights are packed once per device; call `repack()` after changing them in place."""
+    The weights are packed once per device, and again when a weight tensor's version has changed since (an in-place update);
+    `repack()` forces it."""
 
     def __init__(self, state_dict, input_mode="reference"):
         if input_mode not in LPIPS_INPUT_MODES:
             raise ValueError("LPIPS: input_mode must be 'reference' or 'standard', got %r" % (input_mode,))
         self.input_mode = input_mode
         self.weights = load_lpips_alex(state_dict)
-        self._packed = {}
+        self._packed = PackedCache(lambda: [t for layer in self.weights for t in layer], self._pack)
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
+
+    def _pack(self, device, dev):
+        p = LpipsParams()
+        for i in range(len(self.weights)):
+            p.weight[i], p.bias[i], p.lin[i] = (t.data_ptr() for t in dev[3 * i:3 * i + 3])
+        return pack("n3dt_lpips_pack", lib().n3dt_lpips_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        """The packed weights on `device`.  They are packed on the stream that is current at first use; a call on another stream
-        waits for that pack's event first (under a graph capture torch has already ordered the capture stream behind it)."""
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        if key not in self._packed:
-            dev_w = [tuple(t.to(device).contiguous() for t in layer) for layer in self.weights]
-            p = LpipsParams()
-            for i, (w, b, lin) in enumerate(dev_w):
-                p.weight[i], p.bias[i], p.lin[i] = w.data_ptr(), b.data_ptr(), lin.data_ptr()
-            packed = torch.empty(lib().n3dt_lpips_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_lpips_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_lpips_pack")
-            done = torch.cuda.Event()
-            done.record(stream)
-            # dev_w goes back to the caching allocator here: it was allocated on this stream, which the pack that reads it is on
-            self._packed[key] = (packed, stream.cuda_stream, done)
-        packed, pack_stream, done = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     def _run(self, pred, gt):
         """[6, B] float64: row 0 the score, rows 1..5 the layer values"""
-        for name, t in (("pred", pred), ("gt", gt)):
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise ValueError("LPIPS: %s must be a GPU tensor (there is no CPU path)" % name)
-            if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
-                raise ValueError("LPIPS: %s must be float32 [B,3,H,W], got %s %s" % (name, t.dtype, tuple(t.shape)))
-        if pred.shape != gt.shape or pred.device != gt.device:
-            raise ValueError("LPIPS: pred %s and gt %s differ in shape or device" % (tuple(pred.shape), tuple(gt.shape)))
-        pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
+        pred, gt = _pair("LPIPS", pred, gt)
         B, _, H, W = pred.shape
         L = lib()
-        nbytes = L.n3dt_lpips_workspace_bytes(B, H, W)
-        if nbytes == 0:
-            raise ValueError(L.n3dt_last_error().decode())
+        nbytes = count_or_raise(L.n3dt_lpips_workspace_bytes(B, H, W))  # a size the library refuses is refused before anything is packed
         packed = self._packed_for(pred.device)
-        ws = ops.WORKSPACE.get("lpips", nbytes, pred.device)
+        ws = workspace("lpips", nbytes, pred.device)
         out = torch.empty(6, B, dtype=torch.float64, device=pred.device)
         check(L.n3dt_lpips(B, H, W, LPIPS_INPUT_MODES[self.input_mode], ops._ptr(packed), ops._ptr(pred), ops._ptr(gt), ops._ptr(out[0]),
                            ops._ptr(out[1:]), ops._ptr(ws), ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_lpips")

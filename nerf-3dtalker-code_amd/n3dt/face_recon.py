@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, count_or_raise, gpu_images, gpu_tensor, only_keys, open_state_dict, pack, take, workspace
 from ._lib import FACE_RECON_BLOCKS, FACE_RECON_COEFFS, FaceReconParams, check, lib
 
 LAYERS = (3, 4, 6, 3)
@@ -97,27 +98,15 @@ def load_face_recon(obj):
     state dict with the reference's keys, a dict holding one under 'net_recon', or the path of such a file (loaded onto the CPU).
     Strict: a missing key, a key the network does not have and a wrongly shaped tensor are refused with the key;
     num_batches_tracked is accepted (also absent) and ignored."""
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        obj = torch.load(obj, map_location="cpu")
-    if isinstance(obj, dict) and "net_recon" in obj and isinstance(obj["net_recon"], dict):
-        obj = obj["net_recon"]
-    if not isinstance(obj, dict):
-        raise TypeError("load_face_recon: expected a state dict or a path, got %s" % type(obj).__name__)
+    obj = open_state_dict("load_face_recon", obj, unwrap=("net_recon",))
     want = state_dict_keys()
-    for key in obj:
-        if key not in want:
-            raise KeyError("load_face_recon: unexpected key %r" % (key,))
+    only_keys("load_face_recon", obj, want)
 
-    def take(key):
-        if key not in obj:
-            raise KeyError("load_face_recon: the state dict has no key %r" % key)
-        t = obj[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != want[key]:
-            raise ValueError("load_face_recon: %r has shape %s, expected %s" % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, want[key]))
-        return t.detach().float()  # a float32 tensor stays the caller's: its version counter is watched
+    def get(key):
+        return take("load_face_recon", obj, key, want[key]).float()  # a float32 tensor stays the caller's: its version counter is watched
 
-    convs = [(take(c[0] + ".weight"),) + tuple(take("%s.%s" % (c[1], part)) for part in BN_PARTS) for c in CONVS]
-    heads = [(take("final_layers.%d.weight" % i), take("final_layers.%d.bias" % i)) for i in range(len(HEAD_COLS))]
+    convs = [(get(c[0] + ".weight"),) + tuple(get("%s.%s" % (c[1], part)) for part in BN_PARTS) for c in CONVS]
+    heads = [(get("final_layers.%d.weight" % i), get("final_layers.%d.bias" % i)) for i in range(len(HEAD_COLS))]
     return convs, heads
 
 
@@ -126,16 +115,6 @@ def pos_pinv(lm3d_std):
     pseudo-inverse [4,5], float64, on the host"""
     A = np.concatenate((np.asarray(lm3d_std, dtype=np.float64), np.ones((5, 1))), axis=1)
     return np.linalg.pinv(A)
-
-
-def _gpu_images(who, name, x, min_hw):
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: %s must be float32 [n,3,H,W], got %s %s" % (who, name, x.dtype, tuple(x.shape)))
-    if min(x.shape[2:]) < min_hw or max(x.shape[2:]) > 4096:
-        raise ValueError("%s: %s must be %d..4096 pixels high and wide, got %d x %d" % (who, name, min_hw, x.shape[2], x.shape[3]))
-    return x.detach().contiguous()
 
 
 class FaceRecon(object):
@@ -159,43 +138,24 @@ class FaceRecon(object):
             raise ValueError("FaceRecon: lm3d_std must be a finite [5,3] array, got %s" % (lm.shape,))
         self.lm3d_std = lm
         self.pinv = pos_pinv(lm)
-        self._packed = {}
+        self._packed = PackedCache(lambda: [t for group in self.convs for t in group] + [t for pair in self.heads for t in pair], self._pack)
         self._std = {}
         self.last_geometry = None  # align's integer (w, h, left, up) per frame, int32 [n,4] on the device
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
 
-    def _tensors(self):
-        return [t for group in self.convs for t in group] + [t for pair in self.heads for t in pair]
-
-    def _versions(self):
-        return tuple(t._version for t in self._tensors())
+    def _pack(self, device, dev):
+        p = FaceReconParams()
+        for j in range(N_CONVS):
+            p.weight[j], p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (t.data_ptr() for t in dev[5 * j:5 * j + 5])
+            p.bn_eps[j] = BN_EPS
+        for i in range(len(HEAD_COLS)):
+            p.head_weight[i], p.head_bias[i] = dev[5 * N_CONVS + 2 * i].data_ptr(), dev[5 * N_CONVS + 2 * i + 1].data_ptr()
+        return pack("n3dt_face_recon_pack", lib().n3dt_face_recon_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        versions = self._versions()
-        if key not in self._packed or self._packed[key][3] != versions:
-            dev = [t.to(device).contiguous() for t in self._tensors()]
-            p = FaceReconParams()
-            for j in range(N_CONVS):
-                w, g, b, m, v = dev[5 * j:5 * j + 5]
-                p.weight[j], p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (t.data_ptr() for t in (w, g, b, m, v))
-                p.bn_eps[j] = BN_EPS
-            for i in range(len(HEAD_COLS)):
-                p.head_weight[i], p.head_bias[i] = dev[5 * N_CONVS + 2 * i].data_ptr(), dev[5 * N_CONVS + 2 * i + 1].data_ptr()
-            packed = torch.empty(lib().n3dt_face_recon_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_face_recon_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_face_recon_pack")
-            for t in dev:  # the pack reads them on this stream
-                t.record_stream(stream)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done, versions)
-        packed, pack_stream, done, _ = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     def _std_for(self, device):
         key = (device.type, device.index)
@@ -206,29 +166,19 @@ class FaceRecon(object):
     @staticmethod
     def max_images(H, W):
         """images of H x W one call takes: the library's workspace budget"""
-        n = lib().n3dt_face_recon_max_images(H, W)
-        if n == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return n
+        return count_or_raise(lib().n3dt_face_recon_max_images(H, W))
 
     @torch.no_grad()
     def forward(self, x, chunk=None):
         """x [n,3,H,W] float32, 32 <= H, W <= 4096 -> [n,257].  `chunk` caps the images per call (default: the workspace
         budget); results do not depend on it."""
-        x = _gpu_images("FaceRecon.forward", "x", x, MIN_HW)
+        x = gpu_images("FaceRecon.forward", "x", x, MIN_HW)
         n, _, H, W = x.shape
         dev = x.device
         packed = self._packed_for(dev)
         out = torch.empty(n, COEFFS, dtype=torch.float32, device=dev)
-        cap = self.max_images(H, W)
-        if chunk is not None:
-            cap = max(1, min(cap, int(chunk)))
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
-            nbytes = lib().n3dt_face_recon_workspace_bytes(m, H, W)
-            if nbytes == 0:
-                raise ValueError(lib().n3dt_last_error().decode())
-            ws = ops.WORKSPACE.get("face_recon", nbytes, dev)
+        for i, m in chunks(n, self.max_images(H, W), chunk):
+            ws = workspace("face_recon", lib().n3dt_face_recon_workspace_bytes(m, H, W), dev)
             check(lib().n3dt_face_recon_fwd(m, H, W, ops._ptr(packed), ops._ptr(x[i:]), ops._ptr(out[i:]), ops._ptr(ws), ctypes.c_size_t(ws.numel()),
                                             ops._stream()), "n3dt_face_recon_fwd")
         return out
@@ -248,13 +198,12 @@ class FaceRecon(object):
         (crops [n,3,224,224] float32 in [0,1], trans_params [n,5] float64 = (w0, h0, s, t0, t1), status [n] int32: 1 for non-finite
         landmarks, a resized side < 1 or s outside [1/16, 16]; such a frame's crop is zeros).  quantize=True goes through bytes as
         PIL does (the frame is read as floor(255 u + 0.5), both passes round); False rounds nothing."""
-        frames = _gpu_images("FaceRecon.align", "frames", frames, 2)
+        frames = gpu_images("FaceRecon.align", "frames", frames, 2)
         n, _, H, W = frames.shape
         dev = frames.device
         points = 0
         if landmarks is not None:
-            if not torch.is_tensor(landmarks) or not landmarks.is_cuda:
-                raise ValueError("FaceRecon.align: landmarks must be a GPU tensor (there is no CPU path)")
+            gpu_tensor("FaceRecon.align", "landmarks", landmarks, copy=False)
             if landmarks.dim() != 3 or landmarks.shape[0] != n or landmarks.shape[1] not in (68, 5) or landmarks.shape[2] != 2:
                 raise ValueError("FaceRecon.align: landmarks must be [n,68,2] or [n,5,2], got %s" % (tuple(landmarks.shape),))
             landmarks = landmarks.detach().double().contiguous()
@@ -298,10 +247,7 @@ class FaceRecon(object):
             skip = skip.detach().contiguous()
         x = x.detach().contiguous()
         packed = self._packed_for(x.device)
-        nbytes = lib().n3dt_face_recon_block_workspace_bytes(b, n, Hi, Wi)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        ws = ops.WORKSPACE.get("face_recon_block", nbytes, x.device)
+        ws = workspace("face_recon_block", lib().n3dt_face_recon_block_workspace_bytes(b, n, Hi, Wi), x.device)
         out = torch.empty((n, FACE_RECON_COEFFS) if b == HEAD_BLOCK else (n, cout, Ho, Wo), dtype=torch.float32, device=x.device)
         check(lib().n3dt_face_recon_block(b, n, Hi, Wi, ops._ptr(packed), ops._ptr(x), ops._ptr(skip), ops._ptr(out), ops._ptr(ws),
                                           ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_face_recon_block")

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, count_or_raise, gpu_tensor, only_keys, open_state_dict, pack, take, workspace
 from ._lib import FAN_MAX_CONVS, FanParams, check, lib
 
 IMG = 256
@@ -169,35 +170,11 @@ def load_fan(obj, num_modules=4, num_landmarks=98):
     """{key: float32 tensor} from a state dict with the reference's keys, a dict holding one under 'state_dict', or the path of such
     a file (loaded onto the CPU).  Strict: a missing key, a key the network does not have and a wrongly shaped tensor are refused
     with the key; num_batches_tracked is accepted (also absent) and ignored."""
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        obj = torch.load(obj, map_location="cpu")
-    if isinstance(obj, dict) and "state_dict" in obj and isinstance(obj["state_dict"], dict):
-        obj = obj["state_dict"]
-    if not isinstance(obj, dict):
-        raise TypeError("load_fan: expected a state dict or a path, got %s" % type(obj).__name__)
+    obj = open_state_dict("load_fan", obj, unwrap=("state_dict",))
     want = state_dict_keys(num_modules, num_landmarks)
-    for key in obj:
-        if key not in want:
-            raise KeyError("load_fan: unexpected key %r" % (key,))
-    out = {}
-    for key, shape in want.items():
-        if key.endswith("num_batches_tracked"):
-            continue
-        if key not in obj:
-            raise KeyError("load_fan: the state dict has no key %r" % key)
-        t = obj[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != shape:
-            raise ValueError("load_fan: %r has shape %s, expected %s" % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, shape))
-        out[key] = t.detach().float()
-    return out
-
-
-def _gpu(who, name, x, dtype, shape):
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if x.dtype != dtype or x.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, x.shape)) or x.shape[0] < 1:
-        raise ValueError("%s: %s must be %s %s, got %s %s" % (who, name, dtype, list(shape), x.dtype, tuple(x.shape)))
-    return x.detach().contiguous()
+    only_keys("load_fan", obj, want)
+    # a float32 tensor stays the caller's: its version counter is watched
+    return {key: take("load_fan", obj, key, shape).float() for key, shape in want.items() if not key.endswith("num_batches_tracked")}
 
 
 class FAN(object):
@@ -226,81 +203,59 @@ class FAN(object):
                 raise ValueError("FAN: map98to68 must be [P,2] source indices below num_landmarks")
             map98to68 = m.contiguous()
         self.map98to68 = map98to68
-        self._packed = {}
+        self._packed = PackedCache(lambda: list(self.weights.values()), self._pack)
         self._maps = {}
         self.last_gates = None
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
 
     def block_names(self):
         """the names `block` takes, in the chain's order"""
         return block_names(self.num_modules)
 
-    def _tensors(self):
-        return list(self.weights.values())
+    def _pack(self, device, tensors):
+        dev = dict(zip(self.weights, tensors))
+        c256, c64 = coords(IMG).to(device), coords(HEAT).to(device)
+        p = FanParams()
+        p.num_modules, p.num_landmarks = self.num_modules, self.num_landmarks
+        p.coords256, p.coords64 = c256.data_ptr(), c64.data_ptr()
+        for j, row in enumerate(self.table):
+            if row is None:
+                continue
+            conv, bn, _, _, _, bias, _ = row
+            p.weight[j] = dev[conv + ".weight"].data_ptr()
+            if bias:
+                p.bias[j] = dev[conv + ".bias"].data_ptr()
+            if bn is not None:
+                p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (dev["%s.%s" % (bn, part)].data_ptr() for part in BN_PARTS)
+        nbytes = lib().n3dt_fan_packed_bytes(self.num_modules, self.num_landmarks)
+        return pack("n3dt_fan_pack", nbytes, device, ctypes.byref(p)), tensors + [c256, c64]
 
     def _packed_for(self, device):
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        versions = tuple(t._version for t in self._tensors())
-        if key not in self._packed or self._packed[key][3] != versions:
-            dev = {k: t.to(device).contiguous() for k, t in self.weights.items()}
-            c256, c64 = coords(IMG).to(device), coords(HEAT).to(device)
-            p = FanParams()
-            p.num_modules, p.num_landmarks = self.num_modules, self.num_landmarks
-            p.coords256, p.coords64 = c256.data_ptr(), c64.data_ptr()
-            for j, row in enumerate(self.table):
-                if row is None:
-                    continue
-                conv, bn, _, _, _, bias, _ = row
-                p.weight[j] = dev[conv + ".weight"].data_ptr()
-                if bias:
-                    p.bias[j] = dev[conv + ".bias"].data_ptr()
-                if bn is not None:
-                    p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (dev["%s.%s" % (bn, part)].data_ptr() for part in BN_PARTS)
-            packed = torch.empty(lib().n3dt_fan_packed_bytes(self.num_modules, self.num_landmarks), dtype=torch.uint8, device=device)
-            check(lib().n3dt_fan_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_fan_pack")
-            for t in list(dev.values()) + [c256, c64]:  # the pack reads them on this stream
-                t.record_stream(stream)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done, versions)
-        packed, pack_stream, done, _ = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     def max_images(self):
         """images one call takes: the library's workspace budget"""
-        n = lib().n3dt_fan_max_images(self.num_modules, self.num_landmarks)
-        if n == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return n
+        return count_or_raise(lib().n3dt_fan_max_images(self.num_modules, self.num_landmarks))
 
     @torch.no_grad()
     def forward(self, x, gates=None, chunk=None):
         """x [n,3,256,256] float32 BGR in [0,1] -> [heat maps [n,N+1,64,64]] * num_modules.  gates: uint8 [n,num_modules-1,64,64]
         taken instead of the device's own; either way `last_gates` holds what was used.  `chunk` caps the images per call
         (default: the workspace budget); results do not depend on it."""
-        x = _gpu("FAN.forward", "x", x, torch.float32, (None, 3, IMG, IMG))
+        x = gpu_tensor("FAN.forward", "x", x, torch.float32, (None, 3, IMG, IMG))
         n, dev, M, N = x.shape[0], x.device, self.num_modules, self.num_landmarks
         slots = max(M - 1, 1)
         if gates is not None:
-            used = _gpu("FAN.forward", "gates", gates, torch.uint8, (n, M - 1, HEAT, HEAT)).clone() if M > 1 else None
+            used = gpu_tensor("FAN.forward", "gates", gates, torch.uint8, (n, M - 1, HEAT, HEAT)).clone() if M > 1 else None
         else:
             used = torch.empty(n, M - 1, HEAT, HEAT, dtype=torch.uint8, device=dev) if M > 1 else None
         packed = self._packed_for(dev)
-        cap = self.max_images()
-        if chunk is not None:
-            cap = max(1, min(cap, int(chunk)))
-        heat = None if n <= cap else [torch.empty(n, N + 1, HEAT, HEAT, dtype=torch.float32, device=dev) for _ in range(M)]
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
-            nbytes = lib().n3dt_fan_workspace_bytes(M, N, m)
-            if nbytes == 0:
-                raise ValueError(lib().n3dt_last_error().decode())
-            ws = ops.WORKSPACE.get("fan", nbytes, dev)
+        calls = list(chunks(n, self.max_images(), chunk))
+        heat = None if len(calls) == 1 else [torch.empty(n, N + 1, HEAT, HEAT, dtype=torch.float32, device=dev) for _ in range(M)]
+        for i, m in calls:
+            ws = workspace("fan", lib().n3dt_fan_workspace_bytes(M, N, m), dev)
             g = used[i:i + m] if used is not None else torch.empty(m, slots, CELLS, dtype=torch.uint8, device=dev)
             out = torch.empty(M, m, N + 1, HEAT, HEAT, dtype=torch.float32, device=dev)
             check(lib().n3dt_fan_fwd(M, N, int(self.end_relu), m, ops._ptr(packed), ops._ptr(x[i:]), int(gates is None), ops._ptr(g), ops._ptr(out),
@@ -321,8 +276,7 @@ class FAN(object):
         (x, y) in heat-map cells, status [n] int32: 2 where a landmark's argmax is cell 4095 -- the reference raises IndexError
         there -- and the frame's points are all -1).  A view [:, :N] of a [n,N+1,64,64] tensor is taken as it is."""
         h = heatmaps
-        if not torch.is_tensor(h) or not h.is_cuda:
-            raise ValueError("FAN.points: heatmaps must be a GPU tensor (there is no CPU path)")
+        gpu_tensor("FAN.points", "heatmaps", h, copy=False)
         if h.dtype != torch.float32 or h.dim() != 4 or h.shape[0] < 1 or not 1 <= h.shape[1] <= 127 or tuple(h.shape[2:]) != (HEAT, HEAT):
             raise ValueError("FAN.points: heatmaps must be float32 [n,N,64,64] with N in 1..127, got %s %s" % (h.dtype, tuple(h.shape)))
         h = h.detach()
@@ -338,13 +292,13 @@ class FAN(object):
     def crops(self, frames, boxes=None):
         """frames [F,3,H,W] float32 RGB; boxes int32 [F,4] = (y1, y2, x1, x2), None: the whole frame -> ([F,3,256,256] BGR, the
         boxes used): each box resampled bilinearly with half-pixel centres; a bad box gives zeros"""
-        frames = _gpu("FAN.crops", "frames", frames, torch.float32, (None, 3, None, None))
+        frames = gpu_tensor("FAN.crops", "frames", frames, torch.float32, (None, 3, None, None))
         F, _, H, W = frames.shape
         if not 1 <= H <= 4096 or not 1 <= W <= 4096:
             raise ValueError("FAN.crops: frames must be 1..4096 pixels high and wide")
         if boxes is None:
             boxes = torch.tensor([0, H, 0, W], dtype=torch.int32, device=frames.device).repeat(F, 1)
-        boxes = _gpu("FAN.crops", "boxes", boxes, torch.int32, (F, 4))
+        boxes = gpu_tensor("FAN.crops", "boxes", boxes, torch.int32, (F, 4))
         out = torch.empty(F, 3, IMG, IMG, dtype=torch.float32, device=frames.device)
         check(lib().n3dt_fan_crops(F, H, W, ops._ptr(frames), ops._ptr(boxes), ops._ptr(out), ops._stream()), "n3dt_fan_crops")
         return out, boxes
@@ -354,10 +308,10 @@ class FAN(object):
         """points in heat-map cells -> image pixels: times the box's (w / 64, h / 64), 98 -> 68 through the table (rounded to fp32
         as facexlib's float32 array does, the box's integer origin added in fp32; convert=False: float64 throughout), a failed
         frame -1, the carry-forward -> ([F,P,2] float64, status [F] int32: decode's 2 | 4 for a bad box)"""
-        pts = _gpu("FAN.tail", "pts", pts, torch.float64, (None, self.num_landmarks, 2))
+        pts = gpu_tensor("FAN.tail", "pts", pts, torch.float64, (None, self.num_landmarks, 2))
         F, dev = pts.shape[0], pts.device
-        decode_status = _gpu("FAN.tail", "decode_status", decode_status, torch.int32, (F,))
-        boxes = _gpu("FAN.tail", "boxes", boxes, torch.int32, (F, 4))
+        decode_status = gpu_tensor("FAN.tail", "decode_status", decode_status, torch.int32, (F,))
+        boxes = gpu_tensor("FAN.tail", "boxes", boxes, torch.int32, (F, 4))
         table = None
         if convert:
             if self.map98to68 is None:
@@ -403,16 +357,13 @@ class FAN(object):
         if takes_skip != (skip is not None):
             raise ValueError("%s: upsample_add, bl and al, and no other block, take a skip" % who)
         if skip is not None:
-            skip = _gpu(who, "skip", skip, torch.float32, (n, cout, Ho, Wo))
+            skip = gpu_tensor(who, "skip", skip, torch.float32, (n, cout, Ho, Wo))
         if gates is not None:
-            gates = _gpu(who, "gates", gates, torch.uint8, (n, HEAT, HEAT))
+            gates = gpu_tensor(who, "gates", gates, torch.uint8, (n, HEAT, HEAT))
         x = x.detach().contiguous()
         packed = self._packed_for(x.device)
         M, N = self.num_modules, self.num_landmarks
-        nbytes = lib().n3dt_fan_block_workspace_bytes(idx, M, N, n, Hi, Wi)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        ws = ops.WORKSPACE.get("fan_block", nbytes, x.device)
+        ws = workspace("fan_block", lib().n3dt_fan_block_workspace_bytes(idx, M, N, n, Hi, Wi), x.device)
         out = torch.empty(n, cout, Ho, Wo, dtype=torch.float32, device=x.device)
         check(lib().n3dt_fan_block(idx, M, N, int(self.end_relu), n, Hi, Wi, ops._ptr(packed), ops._ptr(x), ops._ptr(skip), ops._ptr(gates), ops._ptr(out),
                                    ops._ptr(ws), ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_fan_block")

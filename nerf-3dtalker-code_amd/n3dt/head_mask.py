@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, count_or_raise, gpu_images, gpu_tensor, only_keys, open_state_dict, pack, take, workspace
 from ._lib import HEAD_MASK_BLOCKS, HEAD_MASK_CONVS, HEAD_MASK_MAX_CLASSES, HeadMaskParams, check, lib
 
 BN_EPS = 1e-5
@@ -116,24 +117,14 @@ def load_head_mask(obj, n_classes=19):
     dict with the reference's keys or the path of such a file (faceparsing_model.pth, loaded onto the CPU).  Strict: a missing
     key, a key the network does not have and a wrongly shaped tensor are refused with the key; num_batches_tracked is accepted
     (also absent) and ignored."""
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        obj = torch.load(obj, map_location="cpu")
-    if not isinstance(obj, dict):
-        raise TypeError("load_head_mask: expected a state dict or a path, got %s" % type(obj).__name__)
+    obj = open_state_dict("load_head_mask", obj)
     want = state_dict_keys(n_classes)
-    for key in obj:
-        if key not in want:
-            raise KeyError("load_head_mask: unexpected key %r" % (key,))
+    only_keys("load_head_mask", obj, want)
 
-    def take(key):
-        if key not in obj:
-            raise KeyError("load_head_mask: the state dict has no key %r" % key)
-        t = obj[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != want[key]:
-            raise ValueError("load_head_mask: %r has shape %s, expected %s" % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, want[key]))
-        return t.detach().float()
+    def get(key):
+        return take("load_head_mask", obj, key, want[key]).float()  # a float32 tensor stays the caller's: its version counter is watched
 
-    return [(take(c[0] + ".weight"),) + (tuple(take("%s.%s" % (c[1], part)) for part in BN_PARTS) if c[1] else ()) for c in CONVS]
+    return [(get(c[0] + ".weight"),) + (tuple(get("%s.%s" % (c[1], part)) for part in BN_PARTS) if c[1] else ()) for c in CONVS]
 
 
 def ellipse(rows=20, cols=20):
@@ -158,26 +149,8 @@ def default_lut():
     return lut
 
 
-def _gpu(who, name, x):
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    return x.detach().contiguous()
-
-
-def _images(who, x):
-    x = _gpu(who, "x", x)
-    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: x must be float32 [n,3,H,W], got %s %s" % (who, x.dtype, tuple(x.shape)))
-    if min(x.shape[2:]) < MIN_HW or max(x.shape[2:]) > 4096:
-        raise ValueError("%s: x must be %d..4096 pixels high and wide, got %d x %d" % (who, MIN_HW, x.shape[2], x.shape[3]))
-    return x
-
-
 def _bytes(who, name, x, dims):
-    x = _gpu(who, name, x)
-    if x.dtype != torch.uint8 or x.dim() != dims or x.shape[0] < 1:
-        raise ValueError("%s: %s must be a uint8 tensor of %d dimensions, got %s %s" % (who, name, dims, x.dtype, tuple(x.shape)))
-    return x
+    return gpu_tensor(who, name, x, torch.uint8, (None,) * dims, "a uint8 tensor of %d dimensions" % dims)
 
 
 class HeadMask(object):
@@ -218,38 +191,23 @@ class HeadMask(object):
         if lut.shape != (256,) or lut.dtype != np.uint8:
             raise ValueError("HeadMask: lut must be a uint8 array of 256 entries")
         self.lut = lut
-        self._packed, self._consts = {}, {}
+        self._packed, self._consts = PackedCache(lambda: [t for group in self.convs for t in group], self._pack), {}
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
 
-    def _tensors(self):
-        return [t for group in self.convs for t in group]
+    def _pack(self, device, dev):
+        p, at = HeadMaskParams(), 0
+        p.n_classes, p.bn_eps = self.n_classes, BN_EPS
+        for j, group in enumerate(self.convs):
+            p.weight[j] = dev[at].data_ptr()
+            if len(group) > 1:
+                p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (t.data_ptr() for t in dev[at + 1:at + 5])
+            at += len(group)
+        return pack("n3dt_head_mask_pack", lib().n3dt_head_mask_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        versions = tuple(t._version for t in self._tensors())
-        if key not in self._packed or self._packed[key][3] != versions:
-            dev = [[t.to(device).contiguous() for t in group] for group in self.convs]
-            p = HeadMaskParams()
-            p.n_classes, p.bn_eps = self.n_classes, BN_EPS
-            for j, group in enumerate(dev):
-                p.weight[j] = group[0].data_ptr()
-                if len(group) > 1:
-                    p.bn_weight[j], p.bn_bias[j], p.bn_mean[j], p.bn_var[j] = (t.data_ptr() for t in group[1:])
-            packed = torch.empty(lib().n3dt_head_mask_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_head_mask_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_head_mask_pack")
-            for group in dev:  # the pack reads them on this stream
-                for t in group:
-                    t.record_stream(stream)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done, versions)
-        packed, pack_stream, done, _ = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     def _consts_for(self, device):
         key = (device.type, device.index)
@@ -260,10 +218,7 @@ class HeadMask(object):
     @staticmethod
     def max_images(H, W):
         """images of H x W one call takes: the library's workspace budget"""
-        n = lib().n3dt_head_mask_max_images(H, W)
-        if n == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return n
+        return count_or_raise(lib().n3dt_head_mask_max_images(H, W))
 
     def _run(self, x, outputs, upsample, chunk):
         n, _, H, W = x.shape
@@ -274,15 +229,8 @@ class HeadMask(object):
             if outputs & (1 << o):
                 h, w = (H, W) if upsample else logit_size(H, W, o)
                 outs[o] = torch.empty(n, self.n_classes, h, w, dtype=torch.float32, device=dev)
-        cap = self.max_images(H, W)
-        if chunk is not None:
-            cap = max(1, min(cap, int(chunk)))
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
-            nbytes = lib().n3dt_head_mask_workspace_bytes(m, H, W)
-            if nbytes == 0:
-                raise ValueError(lib().n3dt_last_error().decode())
-            ws = ops.WORKSPACE.get("head_mask", nbytes, dev)
+        for i, m in chunks(n, self.max_images(H, W), chunk):
+            ws = workspace("head_mask", lib().n3dt_head_mask_workspace_bytes(m, H, W), dev)
             ptrs = [ops._ptr(None if t is None else t[i:]) for t in outs]
             check(lib().n3dt_head_mask_fwd(m, H, W, self.n_classes, ops._ptr(packed), ops._ptr(x[i:]), outputs, int(upsample), ptrs[0], ptrs[1], ptrs[2],
                                            ops._ptr(ws), ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_head_mask_fwd")
@@ -292,7 +240,7 @@ class HeadMask(object):
     def forward(self, x, chunk=None):
         """x [n,3,H,W] float32, normalised, 32 <= H, W <= 4096 -> (out, out16, out32), each [n,n_classes,H,W]: the class's own
         outputs.  `chunk` caps the images per call; results do not depend on it."""
-        return tuple(self._run(_images("HeadMask.forward", x), 7, True, chunk))
+        return tuple(self._run(gpu_images("HeadMask.forward", "x", x, MIN_HW), 7, True, chunk))
 
     __call__ = forward
 
@@ -303,13 +251,13 @@ class HeadMask(object):
         output = self.output if output is None else output
         if output not in (0, 1, 2):
             raise ValueError("HeadMask.logits: output must be 0, 1 or 2, got %r" % (output,))
-        return self._run(_images("HeadMask.logits", x), 1 << output, False, chunk)[output]
+        return self._run(gpu_images("HeadMask.logits", "x", x, MIN_HW), 1 << output, False, chunk)[output]
 
     @torch.no_grad()
     def frames(self, frames):
         """uint8 [F,H,W,3] RGB or float [F,3,H,W] in [0,1] -> (rgb uint8 [F,H,W,3], x float32 [F,3,H,W] normalised as ToTensor +
         Normalize do)"""
-        frames = _gpu("HeadMask.frames", "frames", frames)
+        frames = gpu_tensor("HeadMask.frames", "frames", frames)
         if frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3:
             F, H, W, is_float = frames.shape[0], frames.shape[1], frames.shape[2], 0
         elif frames.is_floating_point() and frames.dim() == 4 and frames.shape[1] == 3:
@@ -327,7 +275,7 @@ class HeadMask(object):
     @torch.no_grad()
     def labels(self, logits, H, W):
         """low-resolution logits [n,C,h,w] float32 -> uint8 [n,H,W]: the argmax of their bilinear (align_corners) interpolation"""
-        logits = _gpu("HeadMask.labels", "logits", logits)
+        logits = gpu_tensor("HeadMask.labels", "logits", logits)
         if logits.dtype != torch.float32 or logits.dim() != 4 or not 1 <= logits.shape[1] <= 256:
             raise ValueError("HeadMask.labels: logits must be float32 [n,C,h,w] with C <= 256, got %s %s" % (logits.dtype, tuple(logits.shape)))
         n, C, h, w = logits.shape
@@ -338,7 +286,7 @@ class HeadMask(object):
     @torch.no_grad()
     def resize(self, img, H, W):
         """uint8 [F,h,w] or [F,h,w,C] -> the same at H x W: half-pixel bilinear in float64, rounded to the nearest byte"""
-        img = _gpu("HeadMask.resize", "img", img)
+        img = gpu_tensor("HeadMask.resize", "img", img)
         if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[0] < 1 or (img.dim() == 4 and not 1 <= img.shape[3] <= 4):
             raise ValueError("HeadMask.resize: img must be uint8 [F,h,w] or [F,h,w,C] with C <= 4, got %s %s" % (img.dtype, tuple(img.shape)))
         C = img.shape[3] if img.dim() == 4 else 1
@@ -384,10 +332,7 @@ class HeadMask(object):
         lut, element = self._consts_for(dev)
         head = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
         eye = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
-        nbytes = lib().n3dt_head_mask_postprocess_workspace_bytes(F, H, W)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        ws = ops.WORKSPACE.get("head_mask_post", nbytes, dev)
+        ws = workspace("head_mask_post", lib().n3dt_head_mask_postprocess_workspace_bytes(F, H, W), dev)
         check(lib().n3dt_head_mask_postprocess(F, H, W, ops._ptr(labels), ops._ptr(rgb), ops._ptr(lut), ops._ptr(element), self.element.shape[0],
                                                self.element.shape[1], self.anchor[0], self.anchor[1], self.dilations, self.erosion_iters,
                                                self.hue_range[0], self.hue_range[1], ops._ptr(head), ops._ptr(eye), ops._ptr(ws),
@@ -398,20 +343,17 @@ class HeadMask(object):
     def masks(self, frames, chunk=None):
         """frames -> (head, eye), uint8 [F,H,W] with values 0 / 255, left on the device: what the reference writes to `*_mask.png`
         and `*_mask_eye.png`.  Chunked by max_images (or `chunk`); chunking does not change a bit."""
-        frames = _gpu("HeadMask.masks", "frames", frames)
+        frames = gpu_tensor("HeadMask.masks", "frames", frames)
         own = tuple(frames.shape[1:3]) if frames.dtype == torch.uint8 else tuple(frames.shape[2:4])
         rgb, x = self._network_frames(frames)
         F, _, H, W = x.shape
         if H < MIN_HW or W < MIN_HW:
             raise ValueError("HeadMask.masks: frames must be at least 32 x 32")
-        cap = self.max_images(H, W)
-        if chunk is not None:
-            cap = max(1, min(cap, int(chunk)))
         head = torch.empty(F, H, W, dtype=torch.uint8, device=x.device)
         eye = torch.empty(F, H, W, dtype=torch.uint8, device=x.device)
-        for i in range(0, F, cap):
-            lab = self.labels(self.logits(x[i:i + cap]), H, W)
-            head[i:i + cap], eye[i:i + cap] = self.postprocess(lab, rgb[i:i + cap])
+        for i, m in chunks(F, self.max_images(H, W), chunk):
+            lab = self.labels(self.logits(x[i:i + m]), H, W)
+            head[i:i + m], eye[i:i + m] = self.postprocess(lab, rgb[i:i + m])
         if own != (H, W):
             head, eye = self.resize(head, own[0], own[1]), self.resize(eye, own[0], own[1])
         return head, eye
@@ -424,7 +366,7 @@ class HeadMask(object):
         block 30 | 0).  A small block gives [n,C_out]."""
         if not isinstance(b, int) or not 0 <= b < HEAD_MASK_BLOCKS:
             raise ValueError("HeadMask.block: block must be an integer in 0..36, got %r" % (b,))
-        x = _gpu("HeadMask.block", "x", x)
+        x = gpu_tensor("HeadMask.block", "x", x)
         if x.dtype != torch.float32 or x.dim() != 4:
             raise ValueError("HeadMask.block: x must be a float32 GPU tensor [n,C,H,W]")
         n, C, Hs, Ws = x.shape
@@ -436,7 +378,7 @@ class HeadMask(object):
         extra = []
         for name, t, shape in (("aux", aux, None), ("scale", scale, (n, cin)), ("addvec", addvec, (n, cin))):
             if t is not None:
-                t = _gpu("HeadMask.block", name, t)
+                t = gpu_tensor("HeadMask.block", name, t)
                 if t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != shape):
                     raise ValueError("HeadMask.block: %s must be float32 %s" % (name, shape or "[n,C,H,W]"))
             extra.append(t)
@@ -446,10 +388,7 @@ class HeadMask(object):
             if tuple(aux.shape) != want:
                 raise ValueError("HeadMask.block: aux must be %s, got %s" % (want, tuple(aux.shape)))
         packed = self._packed_for(x.device)
-        nbytes = lib().n3dt_head_mask_block_workspace_bytes(b, n, Hi, Wi, Hs, Ws)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        ws = ops.WORKSPACE.get("head_mask_block", nbytes, x.device)
+        ws = workspace("head_mask_block", lib().n3dt_head_mask_block_workspace_bytes(b, n, Hi, Wi, Hs, Ws), x.device)
         out = torch.empty((n, cout) if small else (n, cout, Ho, Wo), dtype=torch.float32, device=x.device)
         check(lib().n3dt_head_mask_block(b, n, Hi, Wi, Hs, Ws, self.n_classes, ops._ptr(packed), ops._ptr(x), ops._ptr(aux), ops._ptr(scale),
                                          ops._ptr(addvec), ops._ptr(out), ops._ptr(ws), ctypes.c_size_t(ws.numel()), ops._stream()),

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._host import PackedCache, gpu_tensor
 from ._lib import check, lib
 
 # wav_hparams.py
@@ -96,8 +97,7 @@ def window_starts(frame_ids, n_mel_frames, fps=25.0, rule="chunk"):
 
 
 def _check_wav(who, wav, min_samples):
-    if not torch.is_tensor(wav) or not wav.is_cuda:
-        raise ValueError("%s: the waveform must be a GPU tensor (there is no CPU path)" % who)
+    gpu_tensor(who, "the waveform", wav, copy=False)
     if wav.dtype != torch.float32 or wav.dim() != 1 or not wav.is_contiguous():
         raise ValueError("%s: the waveform must be float32 [L], contiguous, got %s %s" % (who, wav.dtype, tuple(wav.shape)))
     if wav.shape[0] < min_samples:
@@ -129,32 +129,23 @@ class MelFrontend(object):
         if basis.shape != (N_MELS, N_BINS):
             raise ValueError("MelFrontend: mel_basis must be [%d, %d], got %s" % (N_MELS, N_BINS, basis.shape))
         self.basis = basis
-        self._dev = {}
+        self._dev = PackedCache(lambda: (), self._upload)  # nothing is watched: the tables are constants
 
-    def _on(self, device):
+    def _upload(self, device, _):
         """(basis, table, workspace) on `device`, uploaded on the stream that is current at first use; a call on another stream
-        waits for that upload's event first (under a graph capture torch has already ordered the capture stream behind it).
-        The workspace is written with the same values by every call, so calls on two streams may share it."""
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        if key not in self._dev:
-            basis = torch.from_numpy(self.basis).to(device)
-            table = torch.from_numpy(twiddle_table()).to(device)
-            ws = torch.empty(max(lib().n3dt_mel_workspace_bytes(), 256), dtype=torch.uint8, device=device)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._dev[key] = (basis, table, ws, stream.cuda_stream, done)
-        basis, table, ws, up_stream, done = self._dev[key]
-        if stream.cuda_stream != up_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return basis, table, ws
+        waits for that upload's event first (PackedCache).  The workspace is written with the same values by every call, so calls
+        on two streams may share it."""
+        basis = torch.from_numpy(self.basis).to(device)
+        table = torch.from_numpy(twiddle_table()).to(device)
+        ws = torch.empty(max(lib().n3dt_mel_workspace_bytes(), 256), dtype=torch.uint8, device=device)
+        return (basis, table, ws), ()
 
     def _frames(self, wav, offset, prev, total, first, n, dtype):
         """frames first .. first + n - 1 from the run `wav` (n3dt_mel_spectrogram); enqueues on the current stream"""
         out = torch.empty(N_MELS, n, dtype=dtype, device=wav.device)
         if n == 0:
             return out
-        basis, table, ws = self._on(wav.device)
+        basis, table, ws = self._dev.get(wav.device)
         check(lib().n3dt_mel_spectrogram(wav.shape[0], ops._ptr(wav), offset, ops._ptr(prev), total, first, n, ops._ptr(basis),
                                          ops._ptr(table), ops._ptr(out), n, int(dtype == torch.float64), ops._ptr(ws),
                                          ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_mel_spectrogram")
@@ -172,8 +163,7 @@ class MelFrontend(object):
     def windows(self, mel, frame_ids, fps=25.0, rule="chunk"):
         """mel [80, T] (GPU, fp32 or float64) and video frame ids -> [N, 80, 16] fp32, one window per id (see window_starts for
         the two rules).  Columns outside [0, T - 1] repeat the nearest one.  One small upload of the start table, one launch."""
-        if not torch.is_tensor(mel) or not mel.is_cuda:
-            raise ValueError("windows: mel must be a GPU tensor (there is no CPU path)")
+        gpu_tensor("windows", "mel", mel, copy=False)
         if mel.dtype not in (torch.float32, torch.float64) or mel.dim() != 2 or mel.shape[0] != N_MELS or mel.shape[1] < 1:
             raise ValueError("windows: mel must be float32 or float64 [80, T], got %s %s" % (mel.dtype, tuple(mel.shape)))
         mel = mel.detach().contiguous()

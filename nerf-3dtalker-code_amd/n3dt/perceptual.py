@@ -8,6 +8,8 @@ import ctypes
 
 import torch
 
+from ._host import PackedCache, open_state_dict, pack, take
+
 # torchvision vgg16().features indices of the ten 3x3 convolutions in blocks [:4], [4:9], [9:16], [16:23]
 VGG_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21)
 VGG_CONV_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512))
@@ -17,23 +19,10 @@ def load_vgg16_features(src):
     """The ten (weight [C_out, C_in, 3, 3], bias [C_out]) pairs of `features[:23]` from a torchvision vgg16 state dict (or the path of
     one, read with torch.load).  `classifier.*` and the later feature layers are ignored; a missing or wrongly shaped key is refused
     with its name."""
-    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
-        src = torch.load(src, map_location="cpu")
-    if not isinstance(src, dict):
-        raise TypeError("load_vgg16_features: expected a torchvision vgg16 state dict or a path to one, got %s" % type(src).__name__)
-    out = []
-    for idx, (cin, cout) in zip(VGG_CONV_INDICES, VGG_CONV_CHANNELS):
-        pair = []
-        for name, shape in (("features.%d.weight" % idx, (cout, cin, 3, 3)), ("features.%d.bias" % idx, (cout,))):
-            if name not in src:
-                raise KeyError("load_vgg16_features: the state dict has no key %r" % name)
-            t = src[name]
-            if not torch.is_tensor(t) or tuple(t.shape) != shape:
-                raise ValueError("load_vgg16_features: %r has shape %s, expected %s"
-                                 % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, shape))
-            pair.append(t.detach())
-        out.append(tuple(pair))
-    return out
+    who = "load_vgg16_features"
+    src = open_state_dict(who, src, expected="a torchvision vgg16 state dict or a path to one")
+    return [(take(who, src, "features.%d.weight" % idx, (cout, cin, 3, 3)), take(who, src, "features.%d.bias" % idx, (cout,)))  # not converted
+            for idx, (cin, cout) in zip(VGG_CONV_INDICES, VGG_CONV_CHANNELS)]
 
 
 class _VggLoss(torch.autograd.Function):
@@ -88,7 +77,9 @@ class VGGPerceptualLoss(object):
 
     weights: load_vgg16_features() output, or what it accepts (a torchvision vgg16 state dict or its path).
     precision: "fp32" (split-bf16 operands, three products: the parity mode) or "bf16" (single bf16 operands: the fast mode), the
-    module's train_precision convention.  The weights are packed once per device; call `repack()` after changing them in place."""
+    module's train_precision convention.  The weights are packed once per device, and again when a weight tensor's version has
+    changed since (an in-place update of a float32 tensor, which is held as the caller's); `repack()` forces it.  A call on another
+    stream than the pack's waits for the pack first, and the uploaded fp32 weights are released once it has run."""
 
     def __init__(self, weights, precision="fp32"):
         from ._lib import PRECISIONS, F32, BF16
@@ -104,25 +95,20 @@ class VGGPerceptualLoss(object):
                 raise ValueError("VGGPerceptualLoss: conv %d has weight %s / bias %s, expected (%d, %d, 3, 3) / (%d,)"
                                  % (i, tuple(w.shape), tuple(b.shape), cout, cin, cout))
         self.weights = [(w.detach().float(), b.detach().float()) for w, b in weights]
-        self._packed, self._dev = {}, {}
+        self._packed = PackedCache(lambda: [t for pair in self.weights for t in pair], self._pack)
 
     def repack(self):
-        self._packed, self._dev = {}, {}
+        self._packed.clear()
+
+    def _pack(self, device, dev):
+        from ._lib import lib, VggParams
+        p = VggParams()
+        for i in range(len(self.weights)):
+            p.weight[i], p.bias[i] = dev[2 * i].data_ptr(), dev[2 * i + 1].data_ptr()
+        return pack("n3dt_vgg_pack", lib().n3dt_vgg_packed_bytes(self.prec), device, self.prec, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        from . import ops
-        from ._lib import lib, check, VggParams
-        key = (device.type, device.index)
-        if key not in self._packed:
-            dev_w = [(w.to(device).contiguous(), b.to(device).contiguous()) for w, b in self.weights]
-            p = VggParams()
-            for i, (w, b) in enumerate(dev_w):
-                p.weight[i], p.bias[i] = w.data_ptr(), b.data_ptr()
-            packed = torch.empty(lib().n3dt_vgg_packed_bytes(self.prec), dtype=torch.uint8, device=device)
-            check(lib().n3dt_vgg_pack(self.prec, ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_vgg_pack")
-            self._dev[key] = dev_w  # the pack reads them asynchronously
-            self._packed[key] = packed
-        return self._packed[key]
+        return self._packed.get(device)
 
     def conv_stage(self, layer, x, dgrad=False, gate=None, out=None, out_pad=False):
         """n3dt_vgg_conv_stage: ONE conv of the table on NHWC fp32 device maps (the tests judge the kernel a layer at a time with it).

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, count_or_raise, gpu_images, only_keys, open_state_dict, pack, take, workspace
 from ._lib import S3FD_BLOCKS, S3fdParams, check, lib
 
 # (name, C_in, C_out, kernel, stride, padding, pool behind it, detection level fed) -- csrc/s3fd_core.h holds the same table
@@ -93,35 +94,15 @@ def load_s3fd(obj):
     """([(weight, bias)] x 31, [norm weight] x 3), fp32 wherever they are, from a state dict with the reference's keys or the
     path of such a file (loaded onto the CPU).  Strict: a missing key, a key the detector does not have and a wrongly shaped
     tensor are refused with the key."""
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        obj = torch.load(obj, map_location="cpu")
-    if not isinstance(obj, dict):
-        raise TypeError("load_s3fd: expected a state dict or a path, got %s" % type(obj).__name__)
+    obj = open_state_dict("load_s3fd", obj)
     want = state_dict_keys()
-    for key in obj:
-        if key not in want:
-            raise KeyError("load_s3fd: unexpected key %r" % (key,))
+    only_keys("load_s3fd", obj, want)
 
-    def take(key):
-        if key not in obj:
-            raise KeyError("load_s3fd: the state dict has no key %r" % key)
-        t = obj[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != want[key]:
-            raise ValueError("load_s3fd: %r has shape %s, expected %s" % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, want[key]))
-        return t.detach().float()  # a float32 tensor stays the caller's: its version counter is watched
+    def get(key):
+        return take("load_s3fd", obj, key, want[key]).float()  # a float32 tensor stays the caller's: its version counter is watched
 
     names = [c[0] for c in CONVS] + ["%s_mbox_%s" % (s, part) for s in LEVEL_SOURCES for part in ("conf", "loc")]
-    return [(take(n + ".weight"), take(n + ".bias")) for n in names], [take(n + ".weight") for n in NORMS]
-
-
-def _gpu_images(who, name, x):
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError("%s: %s must be float32 [n,3,H,W], got %s %s" % (who, name, x.dtype, tuple(x.shape)))
-    if min(x.shape[2:]) < MIN_HW or max(x.shape[2:]) > 4096:
-        raise ValueError("%s: %s must be 32..4096 pixels high and wide, got %d x %d" % (who, name, x.shape[2], x.shape[3]))
-    return x.detach().contiguous()
+    return [(get(n + ".weight"), get(n + ".bias")) for n in names], [get(n + ".weight") for n in NORMS]
 
 
 class S3FD(object):
@@ -137,65 +118,41 @@ class S3FD(object):
 
     def __init__(self, weights):
         self.weights, self.norms = load_s3fd(weights)
-        self._packed = {}
+        self._packed = PackedCache(lambda: [t for pair in self.weights for t in pair] + self.norms, self._pack)
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
 
-    def _versions(self):
-        return tuple(t._version for pair in self.weights for t in pair) + tuple(t._version for t in self.norms)
+    def _pack(self, device, dev):
+        p, pairs = S3fdParams(), len(self.weights)
+        for i in range(pairs):
+            p.weight[i], p.bias[i] = dev[2 * i].data_ptr(), dev[2 * i + 1].data_ptr()
+        for i, t in enumerate(dev[2 * pairs:]):
+            p.norm_weight[i] = t.data_ptr()
+        return pack("n3dt_s3fd_pack", lib().n3dt_s3fd_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        versions = self._versions()
-        if key not in self._packed or self._packed[key][3] != versions:
-            dev_w = [tuple(t.to(device).contiguous() for t in pair) for pair in self.weights]
-            dev_n = [t.to(device).contiguous() for t in self.norms]
-            p = S3fdParams()
-            for i, (w, b) in enumerate(dev_w):
-                p.weight[i], p.bias[i] = w.data_ptr(), b.data_ptr()
-            for i, t in enumerate(dev_n):
-                p.norm_weight[i] = t.data_ptr()
-            packed = torch.empty(lib().n3dt_s3fd_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_s3fd_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_s3fd_pack")
-            for t in [t for pair in dev_w for t in pair] + dev_n:  # the pack reads them on this stream
-                t.record_stream(stream)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done, versions)
-        packed, pack_stream, done, _ = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     @staticmethod
     def max_images(H, W):
         """frames of H x W one call takes: the library's workspace budget"""
-        n = lib().n3dt_s3fd_max_images(H, W)
-        if n == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return n
+        return count_or_raise(lib().n3dt_s3fd_max_images(H, W))
 
     @staticmethod
     def _workspace(n, H, W, device):
-        nbytes = lib().n3dt_s3fd_workspace_bytes(n, H, W)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return ops.WORKSPACE.get("s3fd", nbytes, device)
+        return workspace("s3fd", lib().n3dt_s3fd_workspace_bytes(n, H, W), device)
 
     @torch.no_grad()
     def forward(self, x):
-        x = _gpu_images("S3FD.forward", "x", x)
+        x = gpu_images("S3FD.forward", "x", x, MIN_HW)
         n, _, H, W = x.shape
         dev = x.device
         packed = self._packed_for(dev)
         out = []
         for h, w in level_sizes(H, W):
             out += [torch.empty(n, 2, h, w, dtype=torch.float32, device=dev), torch.empty(n, 4, h, w, dtype=torch.float32, device=dev)]
-        cap = self.max_images(H, W)
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
+        for i, m in chunks(n, self.max_images(H, W)):
             ws = self._workspace(m, H, W, dev)
             ptrs = (ctypes.c_void_p * 12)(*[t[i:].data_ptr() for t in out])
             check(lib().n3dt_s3fd_heads(m, H, W, ops._ptr(packed), ops._ptr(x[i:]), ptrs, ops._ptr(ws), ctypes.c_size_t(ws.numel()), ops._stream()),
@@ -210,7 +167,7 @@ class S3FD(object):
         synchronisation; with scores=True also the face score of every head position [n,P] float64 and `left [n]`, the positions
         still standing where max_faces cut the NMS short.  `chunk` caps the frames per call (default: the workspace budget);
         results do not depend on it."""
-        frames = _gpu_images("S3FD.detect", "frames", frames)
+        frames = gpu_images("S3FD.detect", "frames", frames, MIN_HW)
         n, _, H, W = frames.shape
         dev = frames.device
         packed = self._packed_for(dev)
@@ -218,11 +175,7 @@ class S3FD(object):
         count = torch.empty(n, dtype=torch.int32, device=dev)
         left = torch.empty(n, dtype=torch.int32, device=dev)
         sc = torch.empty(n, positions(H, W), dtype=torch.float64, device=dev) if scores else None
-        cap = self.max_images(H, W)
-        if chunk is not None:
-            cap = max(1, min(cap, int(chunk)))
-        for i in range(0, n, cap):
-            m = min(cap, n - i)
+        for i, m in chunks(n, self.max_images(H, W), chunk):
             ws = self._workspace(m, H, W, dev)
             check(lib().n3dt_s3fd_detect(m, H, W, ops._ptr(packed), ops._ptr(frames[i:]), int(max_faces), None if sc is None else ops._ptr(sc[i:]),
                                          ops._ptr(dets[i:]), ops._ptr(count[i:]), ops._ptr(left[i:]), ops._ptr(ws), ctypes.c_size_t(ws.numel()),
@@ -244,7 +197,7 @@ class S3FD(object):
         strict=True synchronises once and raises the reference's ValueError naming the first frame without a face.
         strict=False returns (boxes, found) without a synchronisation; a frame without a face enters the smoothing as the whole
         frame -- NOT the reference's behaviour, which raises."""
-        frames = _gpu_images("S3FD.boxes", "frames", frames)
+        frames = gpu_images("S3FD.boxes", "frames", frames, MIN_HW)
         F, _, H, W = frames.shape
         T = int(smooth or 0)
         pads = [int(p) for p in pads]
@@ -278,10 +231,7 @@ class S3FD(object):
             raise ValueError("S3FD.block: block %d takes [n,%d,H,W] with a non-empty output, got %s" % (b, cin, tuple(x.shape)))
         x = x.detach().contiguous()
         packed = self._packed_for(x.device)
-        nbytes = lib().n3dt_s3fd_block_workspace_bytes(b, n, Hi, Wi)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        ws = ops.WORKSPACE.get("s3fd_block", nbytes, x.device)
+        ws = workspace("s3fd_block", lib().n3dt_s3fd_block_workspace_bytes(b, n, Hi, Wi), x.device)
         out = torch.empty(n, cout, Ho, Wo, dtype=torch.float32, device=x.device)
         check(lib().n3dt_s3fd_block(b, n, Hi, Wi, ops._ptr(packed), ops._ptr(x), ops._ptr(out), ops._ptr(ws), ctypes.c_size_t(ws.numel()),
                                     ops._stream()), "n3dt_s3fd_block")

@@ -15,6 +15,7 @@ import ctypes
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, gpu_tensor, open_state_dict, pack, take, workspace
 from ._lib import SYNCNET_BLOCKS, SyncnetParams, check, lib
 
 # (C_in, C_out, (kh, kw), (sh, sw), padding, residual) of the 31 blocks: 0..16 the face encoder on [15,48,96], 17..30 the audio
@@ -69,37 +70,18 @@ def load_syncnet(state_dict):
     with the reference's keys `face_encoder.{i}.conv_block.0.weight|bias`, `face_encoder.{i}.conv_block.1.weight|bias|running_mean|
     running_var` and the same under `audio_encoder`.  A leading `module.` is dropped, `num_batches_tracked` and any other key is
     ignored.  A missing or wrongly shaped tensor is refused with its key."""
-    if not isinstance(state_dict, dict):
-        raise TypeError("load_syncnet: expected a state dict, got %s" % type(state_dict).__name__)
-    sd = {(k[len("module."):] if isinstance(k, str) and k.startswith("module.") else k): v for k, v in state_dict.items()}
-    out = []
-    for name, (cin, cout, (kh, kw), _, _, _) in zip(block_names(), BLOCKS):
-        tensors = []
-        for part, dims in _PARTS:
-            key = "%s.%s" % (name, part)
-            if key not in sd:
-                raise KeyError("load_syncnet: the state dict has no key %r" % key)
-            want = (cout, cin, kh, kw) if dims is None else (cout,)
-            t = sd[key]
-            if not torch.is_tensor(t) or tuple(t.shape) != want:
-                raise ValueError("load_syncnet: %r has shape %s, expected %s"
-                                 % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, want))
-            tensors.append(t.detach().float())
-        out.append(tuple(tensors))
-    return out
+    who = "load_syncnet"
+    sd = open_state_dict(who, state_dict, strip_module=True, paths=False)
+    # a float32 tensor stays the caller's: its version counter is watched
+    return [tuple(take(who, sd, "%s.%s" % (name, part), (cout, cin, kh, kw) if dims is None else (cout,)).float() for part, dims in _PARTS)
+            for name, (cin, cout, (kh, kw), _, _, _) in zip(block_names(), BLOCKS)]
 
 
 def _gpu_f32(who, name, t, shape):
     """`t` as a contiguous fp32 GPU tensor [n, *shape]; shape[0] == 1 may be left out"""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if t.dtype == torch.float32 and shape[0] == 1 and t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:]):
+    if torch.is_tensor(t) and t.dtype == torch.float32 and shape[0] == 1 and t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:]):
         t = t.unsqueeze(1)
-    if t.dtype != torch.float32 or t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != tuple(shape):
-        raise ValueError("%s: %s must be float32 [n,%s], got %s %s" % (who, name, ",".join(str(s) for s in shape), t.dtype, tuple(t.shape)))
-    if t.shape[0] < 1:
-        raise ValueError("%s: %s holds no window" % (who, name))
-    return t.detach().contiguous()
+    return gpu_tensor(who, name, t, torch.float32, (None,) + tuple(shape), "float32 [n,%s]" % ",".join(str(s) for s in shape), empty="holds no window")
 
 
 def check_boxes(who, boxes, n_frames, height, width):
@@ -128,48 +110,34 @@ class SyncNet(object):
     `net.face_windows(frames, boxes)` is that prologue alone; `net.block(b, x)` runs one block, `net.layers(...)` all 31 in turn.
     Stream-ordered, no synchronisation, capturable after a first call, bitwise reproducible; a window's result depends neither on
     its position in the batch nor on the batch size.  Batch norm is folded into the weights when they are packed, once per
-    device; call `repack()` after changing `weights` in place."""
+    device, and again when a weight tensor's version has changed since (an in-place update); `repack()` forces it."""
 
     def __init__(self, state_dict):
         self.weights = load_syncnet(state_dict)
-        self._packed = {}
+        self._packed = PackedCache(lambda: [t for block in self.weights for t in block], self._pack)
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
+
+    def _pack(self, device, dev):
+        p, at = SyncnetParams(), 0
+        for i, block in enumerate(self.weights):  # dev holds the blocks' tensors one behind the other
+            for (field, _), t in zip(SyncnetParams._fields_, dev[at:at + len(block)]):
+                getattr(p, field)[i] = t.data_ptr()
+            at += len(block)
+        return pack("n3dt_syncnet_pack", lib().n3dt_syncnet_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        """The packed weights on `device`, packed on the stream that is current at first use; a call on another stream waits for
-        that pack's event first (under a graph capture torch has already ordered the capture stream behind it)."""
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        if key not in self._packed:
-            dev_w = [tuple(t.to(device).contiguous() for t in block) for block in self.weights]
-            p = SyncnetParams()
-            for i, block in enumerate(dev_w):
-                for (field, _), t in zip(SyncnetParams._fields_, block):
-                    getattr(p, field)[i] = t.data_ptr()
-            packed = torch.empty(lib().n3dt_syncnet_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_syncnet_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_syncnet_pack")
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done)
-        packed, pack_stream, done = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     @staticmethod
     def _workspace(n, device):
-        nbytes = lib().n3dt_syncnet_workspace_bytes(n)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return ops.WORKSPACE.get("syncnet", nbytes, device)
+        return workspace("syncnet", lib().n3dt_syncnet_workspace_bytes(n), device)
 
     @staticmethod
     def _frames(who, frames, boxes, n=None):
         """(frames contiguous, boxes int32 [k,4] on the device, n windows)"""
-        if not torch.is_tensor(frames) or not frames.is_cuda:
-            raise ValueError("%s: frames must be a GPU tensor (there is no CPU path)" % who)
+        gpu_tensor(who, "frames", frames, copy=False)
         if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 3:
             raise ValueError("%s: frames must be float32 [F,3,H,W], got %s %s" % (who, frames.dtype, tuple(frames.shape)))
         F, _, H, W = frames.shape
@@ -193,8 +161,7 @@ class SyncNet(object):
         frames, dev_boxes, n = self._frames("face_windows", frames, boxes)
         out = torch.empty((n,) + FACE_SHAPE, dtype=torch.float32, device=frames.device)
         H, W = frames.shape[2:]
-        for i in range(0, n, 1024):
-            m = min(1024, n - i)
+        for i, m in chunks(n, 1024):
             bx = dev_boxes if dev_boxes.shape[0] == 1 else dev_boxes[i:i + m + WINDOW_FRAMES - 1]
             check(lib().n3dt_syncnet_face_windows(m, H, W, ops._ptr(frames[i:]), ops._ptr(bx), bx.shape[0], ops._ptr(out[i:]), ops._stream()),
                   "n3dt_syncnet_face_windows")
@@ -222,8 +189,7 @@ class SyncNet(object):
         f_emb = torch.empty(n, EMB, dtype=torch.float32, device=dev)
         cos = torch.empty(n, dtype=torch.float64, device=dev)
         L = lib()
-        for i in range(0, n, MAX_CALL):
-            m = min(MAX_CALL, n - i)
+        for i, m in chunks(n, MAX_CALL):
             ws = self._workspace(m, dev)
             if frames is None:
                 fw, fr, bx, nb, H, W = ops._ptr(faces[i:]), None, None, 0, 0, 0
@@ -313,8 +279,7 @@ class SyncMeter(object):
     def __init__(self, syncnet, mel, fps=25.0, box=None, max_shift=0):
         if not isinstance(syncnet, SyncNet):
             raise TypeError("SyncMeter: syncnet must be a SyncNet, got %s" % type(syncnet).__name__)
-        if not torch.is_tensor(mel) or not mel.is_cuda:
-            raise ValueError("SyncMeter: mel must be a GPU tensor (there is no CPU path)")
+        gpu_tensor("SyncMeter", "mel", mel, copy=False)
         if mel.dtype not in (torch.float32, torch.float64) or mel.dim() != 2 or mel.shape[0] != 80 or mel.shape[1] < 1:
             raise ValueError("SyncMeter: mel must be float32 or float64 [80, T], got %s %s" % (mel.dtype, tuple(mel.shape)))
         if not float(fps) > 0.0:

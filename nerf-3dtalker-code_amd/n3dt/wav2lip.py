@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._host import PackedCache, chunks, gpu_tensor, only_keys, open_state_dict, pack, take, workspace
 from ._lib import WAV2LIP_BLOCKS, Wav2lipParams, check, lib
 from .syncnet import check_boxes
 
@@ -122,41 +123,18 @@ def load_wav2lip(obj):
     state dict with the reference's keys, a checkpoint dict holding one under "state_dict", or the path of such a file (loaded onto
     the CPU).  `module.` is dropped from the keys as the reference's load_model does; `num_batches_tracked` is ignored.  Strict: a
     missing key, a key the generator does not have and a wrongly shaped tensor are refused with the key."""
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        obj = torch.load(obj, map_location="cpu")
-    if not isinstance(obj, dict):
-        raise TypeError("load_wav2lip: expected a state dict, a checkpoint dict or a path, got %s" % type(obj).__name__)
-    if "state_dict" in obj and isinstance(obj["state_dict"], dict):
-        obj = obj["state_dict"]
-    sd = {(k.replace("module.", "") if isinstance(k, str) else k): v for k, v in obj.items()}
+    who = "load_wav2lip"
+    obj = open_state_dict(who, obj, unwrap=("state_dict",), expected="a state dict, a checkpoint dict or a path")
+    sd = {(k.replace("module.", "") if isinstance(k, str) else k): v for k, v in obj.items()}  # anywhere in the key, as load_model does
     want = state_dict_keys()
-    for key in sd:
-        if key not in want and not (isinstance(key, str) and key.endswith("num_batches_tracked")):
-            raise KeyError("load_wav2lip: unexpected key %r" % (key,))
-    out = []
-    for b, name in enumerate(block_names()):
-        tensors = []
-        for part, _ in (_HEAD_PARTS if b == HEAD else _PARTS):
-            key = "%s.%s" % (name, part)
-            if key not in sd:
-                raise KeyError("load_wav2lip: the state dict has no key %r" % key)
-            t = sd[key]
-            if not torch.is_tensor(t) or tuple(t.shape) != want[key]:
-                raise ValueError("load_wav2lip: %r has shape %s, expected %s"
-                                 % (key, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, want[key]))
-            tensors.append(t.detach().float())  # a float32 tensor stays the caller's: its version counter is watched
-        out.append(tuple(tensors))
-    return out
+    only_keys(who, [k for k in sd if not (isinstance(k, str) and k.endswith("num_batches_tracked"))], want)
+    # a float32 tensor stays the caller's: its version counter is watched
+    keys = [["%s.%s" % (name, part) for part, _ in (_HEAD_PARTS if b == HEAD else _PARTS)] for b, name in enumerate(block_names())]
+    return [tuple(take(who, sd, key, want[key]).float() for key in block) for block in keys]
 
 
 def _gpu_f32(who, name, t, shape):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if t.dtype != torch.float32 or t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != tuple(shape):
-        raise ValueError("%s: %s must be float32 [n,%s], got %s %s" % (who, name, ",".join(str(s) for s in shape), t.dtype, tuple(t.shape)))
-    if t.shape[0] < 1:
-        raise ValueError("%s: %s holds no window" % (who, name))
-    return t.detach().contiguous()
+    return gpu_tensor(who, name, t, torch.float32, (None,) + tuple(shape), "float32 [n,%s]" % ",".join(str(s) for s in shape), empty="holds no window")
 
 
 def flatten_sequences(audio_sequences, face_sequences):
@@ -189,43 +167,25 @@ class Wav2Lip(object):
 
     def __init__(self, weights):
         self.weights = load_wav2lip(weights)
-        self._packed = {}
+        self._packed = PackedCache(lambda: [t for block in self.weights for t in block], self._pack)
 
     def repack(self):
-        self._packed = {}
+        self._packed.clear()
 
-    def _versions(self):
-        return tuple(t._version for block in self.weights for t in block)
+    def _pack(self, device, dev):
+        p, at = Wav2lipParams(), 0
+        for i, block in enumerate(self.weights):  # dev holds the blocks' tensors one behind the other; the head has two
+            for (field, _), t in zip(Wav2lipParams._fields_, dev[at:at + len(block)]):
+                getattr(p, field)[i] = t.data_ptr()
+            at += len(block)
+        return pack("n3dt_wav2lip_pack", lib().n3dt_wav2lip_packed_bytes(), device, ctypes.byref(p)), dev
 
     def _packed_for(self, device):
-        key = (device.type, device.index)
-        stream = torch.cuda.current_stream(device)
-        versions = self._versions()
-        if key not in self._packed or self._packed[key][3] != versions:
-            dev_w = [tuple(t.to(device).contiguous() for t in block) for block in self.weights]
-            p = Wav2lipParams()
-            for i, block in enumerate(dev_w):
-                for (field, _), t in zip(Wav2lipParams._fields_, block):
-                    getattr(p, field)[i] = t.data_ptr()
-            packed = torch.empty(lib().n3dt_wav2lip_packed_bytes(), dtype=torch.uint8, device=device)
-            check(lib().n3dt_wav2lip_pack(ctypes.byref(p), ops._ptr(packed), ops._stream()), "n3dt_wav2lip_pack")
-            for block in dev_w:  # the pack reads them on this stream: the allocator must not hand them out before it has run
-                for t in block:
-                    t.record_stream(stream)
-            done = torch.cuda.Event()
-            done.record(stream)
-            self._packed[key] = (packed, stream.cuda_stream, done, versions)
-        packed, pack_stream, done, _ = self._packed[key]
-        if stream.cuda_stream != pack_stream and not torch.cuda.is_current_stream_capturing():
-            stream.wait_event(done)
-        return packed
+        return self._packed.get(device)
 
     @staticmethod
     def _workspace(n, device):
-        nbytes = lib().n3dt_wav2lip_workspace_bytes(n)
-        if nbytes == 0:
-            raise ValueError(lib().n3dt_last_error().decode())
-        return ops.WORKSPACE.get("wav2lip", nbytes, device)
+        return workspace("wav2lip", lib().n3dt_wav2lip_workspace_bytes(n), device)
 
     @torch.no_grad()
     def __call__(self, audio_sequences, face_sequences):
@@ -242,8 +202,7 @@ class Wav2Lip(object):
         dev = mel.device
         packed = self._packed_for(dev)
         out = torch.empty((n,) + OUT_SHAPE, dtype=torch.float32, device=dev)
-        for i in range(0, n, MAX_CALL):
-            m = min(MAX_CALL, n - i)
+        for i, m in chunks(n, MAX_CALL):
             ws = self._workspace(m, dev)
             check(lib().n3dt_wav2lip_fwd(m, ops._ptr(packed), ops._ptr(mel[i:]), ops._ptr(faces[i:]), ops._ptr(out[i:]), ops._ptr(ws),
                                          ctypes.c_size_t(ws.numel()), ops._stream()), "n3dt_wav2lip_fwd")
@@ -296,11 +255,7 @@ class Wav2Lip(object):
 
 
 def _frames(who, name, frames):
-    if not torch.is_tensor(frames) or not frames.is_cuda:
-        raise ValueError("%s: %s must be a GPU tensor (there is no CPU path)" % (who, name))
-    if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 1:
-        raise ValueError("%s: %s must be float32 [F,3,H,W], got %s %s" % (who, name, frames.dtype, tuple(frames.shape)))
-    return frames.detach().contiguous()
+    return gpu_tensor(who, name, frames, torch.float32, (None, 3, None, None), "float32 [F,3,H,W]")
 
 
 def _boxes(who, boxes, frames):
@@ -326,8 +281,7 @@ def face_inputs(frames, boxes, ref_frames=None):
     dev_boxes = _boxes(who, boxes, frames)
     F, _, H, W = frames.shape
     out = torch.empty((F,) + FACE_SHAPE, dtype=torch.float32, device=frames.device)
-    for i in range(0, F, 4096):
-        m = min(4096, F - i)
+    for i, m in chunks(F, 4096):
         bx = dev_boxes if dev_boxes.shape[0] == 1 else dev_boxes[i:i + m]
         check(lib().n3dt_wav2lip_face_inputs(m, H, W, ops._ptr(frames[i:]), None if ref_frames is None else ops._ptr(ref_frames[i:]), ops._ptr(bx),
                                              bx.shape[0], ops._ptr(out[i:]), ops._stream()), "n3dt_wav2lip_face_inputs")
@@ -346,8 +300,7 @@ def paste(faces, frames, boxes):
         raise ValueError("paste: faces %s and frames %s differ in frames or device" % (tuple(faces.shape), tuple(frames.shape)))
     dev_boxes = _boxes(who, boxes, frames)
     out = torch.empty_like(frames)
-    for i in range(0, F, 4096):
-        m = min(4096, F - i)
+    for i, m in chunks(F, 4096):
         bx = dev_boxes if dev_boxes.shape[0] == 1 else dev_boxes[i:i + m]
         check(lib().n3dt_wav2lip_paste(m, H, W, ops._ptr(faces[i:]), ops._ptr(frames[i:]), ops._ptr(bx), bx.shape[0], ops._ptr(out[i:]),
                                        ops._stream()), "n3dt_wav2lip_paste")
@@ -403,8 +356,7 @@ class Wav2LipClip(object):
     def mel_windows(mel, first, n, fps):
         """chunk(mel, i, fps) for i = first .. first + n - 1 as [n,1,80,16] float32: the starts are formed on the device in the
         same float64 arithmetic (IEEE product, truncation), without an upload"""
-        if not torch.is_tensor(mel) or not mel.is_cuda:
-            raise ValueError("Wav2LipClip: mel must be a GPU tensor (there is no CPU path)")
+        gpu_tensor("Wav2LipClip", "mel", mel, copy=False)
         if mel.dtype not in (torch.float32, torch.float64) or mel.dim() != 2 or mel.shape[0] != 80 or mel.shape[1] < MEL_COLS:
             raise ValueError("Wav2LipClip: mel must be float32 or float64 [80, T >= 16], got %s %s" % (mel.dtype, tuple(mel.shape)))
         mel = mel.detach().contiguous()
@@ -424,8 +376,7 @@ class Wav2LipClip(object):
         dev_boxes = _boxes("Wav2LipClip.generate", boxes, frames)
         F = frames.shape[0]
         out = []
-        for i in range(0, F, MAX_CALL):
-            m = min(MAX_CALL, F - i)
+        for i, m in chunks(F, MAX_CALL):
             bx = dev_boxes if dev_boxes.shape[0] == 1 else dev_boxes[i:i + m]
             fr = frames[i:i + m]
             x = face_inputs(fr, bx, None if ref_frames is None else ref_frames[i:i + m])
